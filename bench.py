@@ -1,6 +1,11 @@
 """Headline benchmark: training pairs/sec on BASELINE.json configs[1].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload inbatch|triplet|glove]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload inbatch|triplet|glove] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and exactly K timed steps and prints ONE JSON line (value = units per second
+over the K steps, ms_per_step = one timed step).  --full adds what takes runs of its own: the >= 200-step steady-state
+leg, the per-kernel HIP-event passes and roofline, the CPU baseline and (N = 1 headline) the other configs' legs.
+--dump-outputs DIR writes what the timed path returned after its last step as DIR/<name>.npy (dump_outputs).
 
 A "step" is one full training step of the hot path on one batch of synthetic input that is already
 resident in HBM: id lookup (row gather) -> dot-product scores -> loss -> row gradients -> sort +
@@ -413,6 +418,31 @@ def make_state_and_batches(workload, cfg, dev, n_batches, rank):
 
 
 PRECISION = "auto"
+DUMP_ROWS = 16384  # rows of each table --dump-outputs writes: a fixed, seeded sample (the tables are 0.5 - 1 GB each)
+
+
+def dump_outputs(out_dir, state, loss):
+    """--dump-outputs: what the timed path hands its caller after the last timed step -- the loss it returned and the
+    state's tables and sparse-Adagrad accumulators -- as float32 / float64 .npy files under out_dir.  Every table
+    contributes the same seeded sample of DUMP_ROWS rows (sample_rows_<V>.npy holds their indices), so two builds run
+    with the same arguments can be compared output for output (< 64 MB in all)."""
+    from esrecsys_amd.train_state import tree_leaves_with_path
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([loss], np.float64))
+    params = state.params  # (reading .params first puts rows of the one-pass steps' second buffers back)
+    trees = [((), params)] + [((k,), v) for k, v in sorted(state.opt_state.items())]
+    rows = {}
+    for prefix, tree in trees:
+        for path, t in tree_leaves_with_path(tree):
+            if not torch.is_tensor(t) or t.dim() == 0:
+                continue
+            V = t.shape[0]
+            if V not in rows:
+                rows[V] = np.sort(np.random.default_rng(SEED).choice(V, min(V, DUMP_ROWS), replace=False))
+            sample = t.index_select(0, torch.from_numpy(rows[V]).to(t.device))
+            np.save(os.path.join(out_dir, ".".join(prefix + path) + ".npy"), sample.float().cpu().numpy())
+    for V, r in rows.items():
+        np.save(os.path.join(out_dir, "sample_rows_%d.npy" % V), r.astype(np.float64))
 
 
 def run_step(workload, state, batch, B):
@@ -640,12 +670,13 @@ def kernel_timer():
 
 
 def measure_training(workload, cfg, dev, rank, steps, warmup, kernel_timing=True, graph=False, saturating=True,
-                     prepared=None, then=None):
+                     prepared=None, then=None, dump_dir=None):
     """One leg: W untimed + exactly K timed steps of the whole hot path of `workload` on cfg (inputs resident in HBM),
-    then the same K steps again with a HIP-event pair around every ops.* call.  Returns the fields of a bench line.
-    prepared: (state, batches) made ahead by make_state_and_batches (a leg that must start right behind another leg's
-    timed region: its tables are initialised before that leg runs).  then: called once, right after this leg's timed
-    region (before its HIP-event passes) -- main() runs the short headline leg there."""
+    then (kernel_timing) the same K steps again with a HIP-event pair around every ops.* call.  Returns the fields of a
+    bench line.  prepared: (state, batches) made ahead by make_state_and_batches (a leg that must start right behind
+    another leg's timed region: its tables are initialised before that leg runs).  then: called once, right after this
+    leg's timed region (before its HIP-event passes) -- main() runs the short headline leg there.  dump_dir: the timed
+    path's outputs are written there right after the timed region (dump_outputs)."""
     V, D, B = cfg["V"], cfg["D"], cfg["B"]
     n_batches = steps + warmup
     state, batches = prepared if prepared is not None else make_state_and_batches(workload, cfg, dev, n_batches, rank)
@@ -661,7 +692,7 @@ def measure_training(workload, cfg, dev, rank, steps, warmup, kernel_timing=True
             if D == 128 and B % 128 == 0 else None
         # (kRmSafeBound = 28 in esr_inbatch3.hip; kHBoundSafe = 14 in esr_inbatch2h.hip, fp16's narrower exponent range)
         needs_rowmax = (mq * mc) ** 0.5 * abs(SCALE) * 1.4426950408889634 > (14.0 if path == "f16x2" else 28.0)
-    timer = kernel_timer()
+    timer = kernel_timer() if kernel_timing else None
 
     # ---- timed region: K steps (eager launches; --graph replays the whole step as one hipGraph) ----------------
     graphed, mode = None, "eager"
@@ -815,27 +846,29 @@ def measure_training(workload, cfg, dev, rank, steps, warmup, kernel_timing=True
             dt = time.perf_counter() - t0
         final_loss = float(loss)
     assert np.isfinite(final_loss), "non-finite loss"
+    if dump_dir is not None:
+        dump_outputs(dump_dir, holder["state"] if graphed is not None else state, final_loss)
     if then is not None:
         then()
 
-    # ---- per-kernel HIP-event timing: the same K steps launched eagerly on the same stream (events
-    # cannot be recorded inside a replayed graph; kernel durations are the same either way) ---------
-    # A spin kernel is queued ahead of every step so the host runs ahead of the GPU: otherwise an event pair
-    # around a 10 us kernel also measures the Python launch latency that precedes it.
-    timer.enabled = kernel_timing
-    spin = getattr(torch.cuda, "_sleep", None)
-    for i in range(warmup, n_batches if timer.enabled else warmup):
-        if spin is not None:
-            spin(1_500_000)
-        state, _ = run_step(workload, state, batches[i], B)
-    torch.cuda.synchronize()
-    timer.enabled = False
-
     K = steps
     kernels = {}
-    for g, (ms, calls) in timer.totals_ms(K).items():
-        if calls:
-            kernels[g] = {"ms_per_step": ms / K, "launch_groups_per_step": calls / K}
+    if kernel_timing:
+        # ---- per-kernel HIP-event timing: the same K steps launched eagerly on the same stream (events
+        # cannot be recorded inside a replayed graph; kernel durations are the same either way) ---------
+        # A spin kernel is queued ahead of every step so the host runs ahead of the GPU: otherwise an event pair
+        # around a 10 us kernel also measures the Python launch latency that precedes it.
+        timer.enabled = True
+        spin = getattr(torch.cuda, "_sleep", None)
+        for i in range(warmup, n_batches):
+            if spin is not None:
+                spin(1_500_000)
+            state, _ = run_step(workload, state, batches[i], B)
+        torch.cuda.synchronize()
+        timer.enabled = False
+        for g, (ms, calls) in timer.totals_ms(K).items():
+            if calls:
+                kernels[g] = {"ms_per_step": ms / K, "launch_groups_per_step": calls / K}
     rows = cfg["rows_per_unit"]
     # algorithmic bytes: gather D*4 per row occurrence; sparse Adagrad per updated row
     # grad read D*4 + param RMW 2*D*4 + accumulator RMW 2*D*4
@@ -1066,6 +1099,13 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as one hipGraph (measured slower than eager launches on MI355X: the step "
                          "is GPU-dependency-bound, not host-bound)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the steady-state leg, the per-kernel HIP-event "
+                         "passes and roofline, the CPU baseline and the other configs' legs (the --no-* switches above "
+                         "apply to these; a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned after its last step to DIR/<name>.npy (the loss; a seeded "
+                         "sample of rows of every table and accumulator)")
     args = ap.parse_args()
     global PRECISION
     PRECISION = args.precision
@@ -1073,6 +1113,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and (args.gpus > 1 or args.workload == "retrieve" or os.environ.get("ESR_BENCH_SHARDED") == "1"):
+        ap.error("--dump-outputs: the single-GPU training workloads only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)  # plain `python bench.py --gpus N`: become N ranks under torch.distributed.run
     if args.gpus > 1 and world != args.gpus:
@@ -1119,6 +1161,19 @@ def main():
         watchdog.disarm()
         return run_sharded(args, cfg, dev, rank, world, watchdog)
 
+    def result_line(leg, roofline):
+        return {"metric": "training pairs/sec", "value": leg["value"], "unit": leg["unit"], "n_gpus": 1,
+                "steps": leg["steps"], "warmup": leg["warmup"], "ms_per_step": leg["ms_per_step"],
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                "config": leg["config"], "roofline": roofline}
+
+    if not args.full:
+        # a plain run: set up, W warmup + exactly K timed steps, the outputs if asked for, ONE line -- nothing else
+        leg = measure_training(args.workload, cfg, dev, rank, args.steps, args.warmup, kernel_timing=False,
+                               saturating=False, graph=args.graph, dump_dir=args.dump_outputs)
+        emit(result_line(leg, None))
+        return None
+
     # A short timed region (the driver's --steps 20 --warmup 5 is 6 ms) started on an idle chip sits inside the power
     # manager's transient: the first steps run at boost clock (0.232 ms), the package overshoots its cap, is clamped
     # (0.30 ms per step around step 12) and settles after ~10 ms (profiles/r3/startup_probe_inbatch.jsonl).  Rounds 3-4
@@ -1127,7 +1182,8 @@ def main():
     # its own state; it carries the HIP-event passes) runs FIRST, and the headline leg -- exactly W warmup + K timed steps
     # on ITS OWN state, whose tables were initialised before the steady leg started -- begins right behind the steady
     # leg's timed region.  Both results are on the line (`roofline.legs.steady_state`), `config.order` says what preceded
-    # the timed region, and `roofline.frac` is executed flops / the headline's own ms_per_step.
+    # the timed region, and `roofline.frac` is executed flops / the headline's own ms_per_step.  value / ms_per_step of
+    # the line are the headline leg's, as in a plain run: --steps sets the timed steps they stand for.
     steady = None
     if args.steps < STEADY_STEPS and not args.graph and not args.no_steady:
         prepared = make_state_and_batches(args.workload, cfg, dev, args.steps + args.warmup, rank)
@@ -1135,7 +1191,7 @@ def main():
 
         def headline():
             holder["leg"] = measure_training(args.workload, cfg, dev, rank, args.steps, args.warmup, kernel_timing=False,
-                                             saturating=False, prepared=prepared)
+                                             saturating=False, prepared=prepared, dump_dir=args.dump_outputs)
         steady = measure_training(args.workload, cfg, dev, rank, STEADY_STEPS, max(args.warmup, 20),
                                   kernel_timing=not args.no_kernel_timing, then=headline)
         leg = holder["leg"]
@@ -1149,7 +1205,7 @@ def main():
             leg["roofline"]["timed_over"] = "the steady_state leg's %d steps (HIP events)" % steady["steps"]
     else:
         leg = measure_training(args.workload, cfg, dev, rank, args.steps, args.warmup,
-                               kernel_timing=not args.no_kernel_timing, graph=args.graph)
+                               kernel_timing=not args.no_kernel_timing, graph=args.graph, dump_dir=args.dump_outputs)
     rf = leg["roofline"] or {}
     # the final line stays under 6 KB (the driver keeps the tail of stdout); the full record of the headline leg and of
     # every secondary leg is printed as its own line above it
@@ -1205,9 +1261,8 @@ def main():
                                      "steps": src["steps"], "warmup": src["warmup"],
                                      "frac": _r(roof["frac"] * leg["ms_per_step"] / src["ms_per_step"]) if rf else None}}
     # Flat scalars (round 6: the driver keeps `roofline`'s scalars and drops nested objects and unknown top-level keys).
-    # value / ms_per_step of the LINE are the steady-state leg's when --steps is shorter than it -- the rate a training
-    # run sees; the K-step leg (exactly W warmup + K timed steps right behind the steady leg's timed region, where the
-    # chip still holds its boost clock for a few ms) is printed beside it as k_step_*.
+    # value / ms_per_step of the LINE are the K-step leg's (exactly W warmup + K timed steps; k_step_*); the steady-state
+    # leg's -- the rate a long training run sees -- are printed beside them as steady_*.
     if sat:
         roof["hbm_gather_GBps"] = roof["hbm_gather_scatter"].get("gather_GBps")
         roof["hbm_scatter_GBps"] = roof["hbm_gather_scatter"].get("sparse_adagrad_GBps")
@@ -1225,23 +1280,13 @@ def main():
         roof["dominant_kernel_frac"] = dk[name].get("frac_of_2.5PF", dk[name].get("frac_of_8TBps"))
     for kname, us in (roof.get("per_kernel_us_in_run") or {}).items():  # every kernel of the step, flat
         roof["us_" + kname] = us
-    use_steady = steady is not None
-    if use_steady and rf:  # frac / achieved follow the value they describe
-        ratio = leg["ms_per_step"] / src["ms_per_step"]
-        roof["k_step_frac"] = roof["frac"]
-        roof["frac"] = _r(roof["frac"] * ratio)
-        roof["achieved"] = _r(roof["achieved"] * ratio, 2)
-        roof["step_frac_driver_timed"] = roof["frac"]
-        roof["what"] = roof["what"].replace("THIS line", "THIS line (= the steady_state leg's)")
-    out = {"metric": "training pairs/sec", "value": src["value"] if use_steady else leg["value"], "unit": leg["unit"],
-           "n_gpus": 1, "steps": leg["steps"], "warmup": leg["warmup"],
-           "ms_per_step": src["ms_per_step"] if use_steady else leg["ms_per_step"],
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": leg["config"], "roofline": roof}
-    if use_steady:
-        out["config"]["value_from"] = ("the steady_state leg (%d timed steps behind %d warmup steps, own state); the leg of "
-                                       "exactly --steps / --warmup that follows it: roofline.k_step_value / "
-                                       "k_step_ms_per_step" % (src["steps"], src["warmup"]))
+    if steady is not None and rf:
+        roof["steady_frac"] = roof["legs"]["steady_state"]["frac"]
+    out = result_line(leg, roof)
+    if steady is not None:
+        out["config"]["value_from"] = ("the leg of exactly --steps / --warmup; the steady_state leg (%d timed steps behind "
+                                       "%d warmup steps, own state) that precedes it: roofline.steady_value / "
+                                       "steady_ms_per_step" % (src["steps"], src["warmup"]))
     if not args.no_cpu_baseline:
         cb = cpu_baseline(args.workload, cfg)
         emit_leg("headline_cpu_baseline_full", cb)

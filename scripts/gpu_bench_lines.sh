@@ -1,11 +1,12 @@
-# the driver's command; every JSON line's leg name and size, then the final line
-mkdir -p gpurun_out/r4a
-python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r4a/bench_driver_cmd.out 2> gpurun_out/r4a/bench_driver_cmd.err
+# the full benchmark (the driver's command with --full); every JSON line's leg name and size, then the final line
+OUT=${OUT:-/tmp/bench_lines}
+mkdir -p $OUT
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_full_cmd.out 2> $OUT/bench_full_cmd.err
 echo "rc=$?"
-grep -v amdgpu.ids gpurun_out/r4a/bench_driver_cmd.err | tail -5
-python - <<'P'
-import json
-for line in open("gpurun_out/r4a/bench_driver_cmd.out"):
+grep -v amdgpu.ids $OUT/bench_full_cmd.err | tail -5
+OUT=$OUT python - <<'P'
+import json, os
+for line in open(os.path.join(os.environ["OUT"], "bench_full_cmd.out")):
     if not line.startswith("{"):
         continue
     d = json.loads(line)
