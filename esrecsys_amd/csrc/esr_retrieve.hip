@@ -1012,7 +1012,11 @@ static RetrievePlan retrieve_plan(int64_t nq, int64_t N, int D, int k, int mode)
   // candidates the second chunk fills a list once; after that a list passes the mark every few chunks: ~6 real selects
   // per query at N = 1 M instead of 33 (82 us each).  The list must hold the mark plus a whole chunk.
   p.skip_upto = (int)std::max<int64_t>(3 * (int64_t)k, 1536);
-  p.ppitch = std::max<int64_t>(k, p.skip_upto) + p.chunk;
+  // Mode 3's first-chunk select copies the whole band -- up to every one of the `first` records (a zero query: all
+  // scores tie) -- into the list before it can mark the row exact, so there the list also holds a whole first chunk
+  // (at many queries the later chunk, and with it mark + chunk, is shorter than `first`).  The other modes' first select
+  // writes k records only.
+  p.ppitch = std::max<int64_t>(std::max<int64_t>(k, p.skip_upto) + p.chunk, mode == 3 ? p.first : 0);
   size_t o = 0;
   p.off_A = o; o += align_up((size_t)plane_count(p.P) * p.Mp * p.Dp * 2, 256);
   p.off_B = o; o += align_up((size_t)plane_count(p.P) * p.chunk_pad * p.Dp * 2, 256);
@@ -1264,8 +1268,10 @@ static int retrieve_topk_impl(const float* queries, const float* candidates, con
   ESR_REQUIRE(mode >= 0 && mode <= 3,
               "esr_retrieve_topk: mode %d (0 = exact bf16x3, 1 = bf16, 2 = exact-grade f16x2, 3 = f16 filter + f32 re-score)",
               mode);
-  ESR_REQUIRE(index_step > 0 && (int64_t)index_base + (N - 1) * (int64_t)index_step < ((int64_t)1 << 31),
-              "esr_retrieve_topk: index_base/index_step overflow int32");
+  // (index_base >= 0: the select's tie-break composite holds 0xFFFFFFFF - (uint32)index, and -1 marks an empty slot)
+  ESR_REQUIRE(index_base >= 0 && index_step > 0 &&
+                  (int64_t)index_base + (N - 1) * (int64_t)index_step < ((int64_t)1 << 31),
+              "esr_retrieve_topk: index_base must be >= 0, index_step > 0, and the last index within int32");
   ESR_REQUIRE(queries && candidates && out_scores && out_indices && workspace, "esr_retrieve_topk: null pointer");
   ESR_REQUIRE(mode != 3 || D <= kSelLdsWords, "esr_retrieve_topk: mode 3 takes D <= %d", kSelLdsWords);
   const RetrievePlan p = retrieve_plan(nq, N, D, k, mode);

@@ -900,11 +900,24 @@ def _retrieve_mode(mode):
 
 class PreparedCorpus:
     """What retrieve_prepare made of a candidate matrix: the buffer esr_retrieve_topk_prepared reads, and what it was made
-    for (mode, shape, the matrix's storage) so that a call cannot be handed another corpus's or another mode's planes."""
-    __slots__ = ("blob", "mode", "N", "D", "data_ptr")
+    for (mode, shape, the matrix's storage and its version counter) so that a call cannot be handed another corpus's or
+    another mode's planes, nor planes older than the matrix.  The matrix itself is kept: while it lives, no other tensor
+    gets its address; an in-place update (a training step) bumps its version, and the stale planes and statistics are
+    refused rather than used.  (An inference tensor keeps no version counter: for one, only the address is checked.)"""
+    __slots__ = ("blob", "mode", "N", "D", "data_ptr", "candidates", "version")
 
-    def __init__(self, blob, mode, N, D, data_ptr):
-        self.blob, self.mode, self.N, self.D, self.data_ptr = blob, mode, N, D, data_ptr
+    def __init__(self, blob, mode, candidates):
+        self.blob, self.mode, self.candidates = blob, mode, candidates
+        self.N, self.D = candidates.shape
+        self.data_ptr, self.version = candidates.data_ptr(), _version_of(candidates)
+
+    def matches(self, candidates, mode):
+        return (self.mode, self.N, self.D, self.data_ptr, self.version) == \
+            (mode, candidates.shape[0], candidates.shape[1], candidates.data_ptr(), _version_of(candidates))
+
+
+def _version_of(t):
+    return None if t.is_inference() else t._version
 
 
 def retrieve_prepare(candidates, mode="f16r"):
@@ -920,7 +933,7 @@ def retrieve_prepare(candidates, mode="f16r"):
         raise ValueError("retrieve_prepare: bad shape %s / mode %r" % (tuple(candidates.shape), mode))
     blob = _aligned_bytes(nbytes, candidates.device)
     check(lib.esr_retrieve_prepare(_p(candidates), N, D, m, _p(blob), blob.numel(), _stream()), "esr_retrieve_prepare")
-    return PreparedCorpus(blob, m, N, D, candidates.data_ptr())
+    return PreparedCorpus(blob, m, candidates)
 
 
 def retrieve_topk(queries, candidates, k, mode="exact", index_base=0, index_step=1, prepared=None):
@@ -940,9 +953,9 @@ def retrieve_topk(queries, candidates, k, mode="exact", index_base=0, index_step
     out_i = torch.empty((nq, k), dtype=torch.int32, device=queries.device)
     ws = _ws(_ws_bytes("esr_retrieve_workspace_bytes", nq, N, D, k, m), queries.device)
     if prepared is not None:
-        if not isinstance(prepared, PreparedCorpus) or (prepared.mode, prepared.N, prepared.D, prepared.data_ptr) != \
-                (m, N, D, candidates.data_ptr()):
-            raise ValueError("prepared must be retrieve_prepare(candidates, mode) of THIS candidate matrix and mode")
+        if not isinstance(prepared, PreparedCorpus) or not prepared.matches(candidates, m):
+            raise ValueError("prepared must be retrieve_prepare(candidates, mode) of THIS candidate matrix and mode, "
+                             "made after its last in-place update")
         check(lib.esr_retrieve_topk_prepared(_p(queries), _p(candidates), _p(prepared.blob), nq, N, D, k, m, index_base,
                                              index_step, _p(out_s), _p(out_i), _p(ws), ws.numel(), _stream()),
               "esr_retrieve_topk_prepared")

@@ -437,7 +437,8 @@ int esr_score_topk(const float* queries, const float* candidates, int64_t nq, in
  * :123-132 in one call -- and the eval of spotify/train_spotify.py:120 (top_k(500) over every track):
  *   scores[q, n] = queries[q] . candidates[n];  per query the k best, descending, ties -> lower index.
  * queries f32 [nq, D], candidates f32 [N, D], k <= min(N, 1024).  The reported index of local candidate
- * n is index_base + n * index_step (row-sharded candidates: base = rank, step = world).
+ * n is index_base + n * index_step (row-sharded candidates: base = rank, step = world); index_base >= 0, index_step > 0,
+ * and the last index index_base + (N - 1) * index_step at most 2^31 - 1.
  * mode ESR_RETRIEVE_EXACT: products from three exact bf16 planes per operand (six MFMA cross terms,
  *   f32 accumulate) -- f32-equivalent scores, the brute-force answer.
  * mode ESR_RETRIEVE_BF16: one bf16 plane per operand -- the approximate candidate stage; follow with

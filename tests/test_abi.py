@@ -94,6 +94,55 @@ def test_bad_arguments_are_rejected_without_a_device(lib):
     assert lib.esr_score_topk(16, 16, 1, 10, 4, 11, 16, 16, 16, 1 << 20, None) == EINVAL     # k > N
 
 
+def test_retrieve_arguments_are_rejected_without_a_device(lib):
+    """esr_retrieve_topk / _prepared validate before any launch: with stand-in (non-null, aligned) pointers and no
+    workspace, a bad argument is ESR_EINVAL and a good one gets as far as the workspace check (ESR_EWORKSPACE)."""
+    EINVAL, EWORKSPACE = -1, -3
+    P = 256   # a stand-in device address: never dereferenced, the calls return before any launch
+
+    def plain(nq=4, N=100, D=64, k=10, mode=0, base=0, step=1):
+        return lib.esr_retrieve_topk(P, P, nq, N, D, k, mode, base, step, P, P, P, 0, None)
+
+    def prepared(nq=4, N=100, D=64, k=10, mode=0, base=0, step=1):
+        return lib.esr_retrieve_topk_prepared(P, P, P, nq, N, D, k, mode, base, step, P, P, P, 0, None)
+
+    for call in (plain, prepared):
+        assert call() == EWORKSPACE
+        assert call(k=1025, N=5000) == EINVAL and b"bad sizes" in lib.esr_last_error()      # k above the select's 1024
+        assert call(k=1024, N=5000) == EWORKSPACE
+        assert call(k=101) == EINVAL and b"bad sizes" in lib.esr_last_error()               # k > N
+        assert call(k=100) == EWORKSPACE                                                    # k == N
+        assert call(mode=4) == EINVAL
+        assert call(D=8193, mode=3) == EINVAL and b"D <=" in lib.esr_last_error()           # mode 3's row cache
+        assert call(D=8192, mode=3) == EWORKSPACE
+        assert call(D=8193, mode=0) == EWORKSPACE                                           # (mode 3 only)
+        # the last reported index must fit int32: base + (N - 1) * step = 2^31 is refused, 2^31 - 1 is not
+        N = 1000
+        assert call(N=N, base=2 ** 31 - 1 - (N - 1) * 7 + 1, step=7) == EINVAL
+        assert b"index_base" in lib.esr_last_error()
+        assert call(N=N, base=2 ** 31 - 1 - (N - 1) * 7, step=7) == EWORKSPACE
+        assert call(N=N, base=2 ** 31 - 1 - (N - 1)) == EWORKSPACE
+        assert call(N=N, base=2 ** 31 - (N - 1)) == EINVAL
+        # a negative base would put -1 (an empty slot) and negative indices into the tie-break composite's order
+        assert call(base=-1) == EINVAL and b"index_base" in lib.esr_last_error()
+        assert call(base=-(2 ** 31), step=8) == EINVAL
+        assert call(step=0) == EINVAL and call(step=-1) == EINVAL
+    assert lib.esr_retrieve_topk_prepared(P, P, 16, 4, 100, 64, 10, 0, 0, 1, P, P, P, 0, None) == EINVAL  # misaligned
+
+
+@pytest.mark.parametrize("nq,N,D,k", [(100_000, 40_000, 128, 500), (200_000, 40_000, 128, 500),
+                                      (65_536, 1_000_000, 512, 1024), (41_000, 1_000_000, 512, 1024)])
+def test_retrieve_f16r_workspace_holds_a_whole_first_chunk_per_query(lib, nq, N, D, k):
+    """Mode 3 (f16r) copies the whole error band of the dense first chunk -- every one of its `first` records for a query
+    whose scores all tie -- into the query's list before it can turn the row exact, so the workspace must hold the dense
+    scores S [nq, first] (4 bytes) and a list of `first` records (8 bytes) per query.  The later chunk shrinks with nq
+    (2^29 / nq records), and at these points mark + chunk (the list the other modes need) is below `first`:
+    nq = 100 000 and 200 000 at k = 500 (first = 8192; lists of 6784 and 4096), nq = 65 536 and 41 000 at k = 1024
+    (first = 16 384; 11 264 and 16 128)."""
+    first = min(N, max(8192, 16 * k))
+    assert lib.esr_retrieve_workspace_bytes(nq, N, D, k, 3) >= nq * first * (4 + 8)
+
+
 def test_exchange_entry_points_validate_before_touching_rccl(lib):
     """8e exchange in the C ABI: bad arguments come back as ESR_EINVAL with a message, before any group is opened."""
     EINVAL, ENODEVICE = -1, -4
