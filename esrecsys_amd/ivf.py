@@ -51,15 +51,27 @@ class IVFIndex:
         self.nlist, self.N, self.D = nlist, N, D
         self.max_list = int(longest.item())   # (one read-back, at build time)
 
-    def search(self, queries, k, nprobe):
+    def search(self, queries, k, nprobe, probe_lists=None):
         """([nq, k] scores, [nq, k] candidate rows), best first; exact f32 scores of the candidates in each query's
-        nprobe best lists (entries the lists could not fill: -inf / -1)."""
+        nprobe best lists (entries the lists could not fill: -inf / -1).  The answer is the k best of the union of the
+        probed lists, ties in score ordered by probe slot, then by candidate row.
+
+        probe_lists: int32 [nq, nprobe] device tensor of the lists to look into, in place of the nprobe best centroids
+        (what ``ops.retrieve_topk`` of the queries against the centroids delivers).  Each row must hold distinct lists
+        in [0, nlist); the kernel does not check this."""
         q = ops._req(queries, torch.float32, "queries")
         nq, D = q.shape
         if D != self.D:
             raise ValueError("query width %d != index width %d" % (D, self.D))
-        nprobe = int(min(nprobe, self.nlist))
-        _, lists = ops.retrieve_topk(q, self.centroids, nprobe, mode="exact")
+        if probe_lists is None:
+            nprobe = int(min(nprobe, self.nlist))
+            _, lists = ops.retrieve_topk(q, self.centroids, nprobe, mode="exact")
+        else:
+            lists = ops._req(probe_lists, torch.int32, "probe_lists")
+            nprobe = int(nprobe)
+            if tuple(lists.shape) != (nq, nprobe) or not 1 <= nprobe <= self.nlist:
+                raise ValueError("probe_lists must be [%d, nprobe] with 1 <= nprobe <= %d, got %s for nprobe %d"
+                                 % (nq, self.nlist, tuple(lists.shape), nprobe))
         lib = _lib.load()
         out_s = torch.empty((nq, k), dtype=torch.float32, device=q.device)
         out_i = torch.empty((nq, k), dtype=torch.int32, device=q.device)

@@ -7,6 +7,7 @@ import re
 import pytest
 
 from conftest import ROOT
+from test_gpu_ivf_exact import GEOMETRIES, ivf_geom, ivf_workspace_bytes
 
 
 def _declared_symbols():
@@ -141,6 +142,69 @@ def test_retrieve_f16r_workspace_holds_a_whole_first_chunk_per_query(lib, nq, N,
     (first = 16 384; 11 264 and 16 128)."""
     first = min(N, max(8192, 16 * k))
     assert lib.esr_retrieve_workspace_bytes(nq, N, D, k, 3) >= nq * first * (4 + 8)
+
+
+@pytest.mark.parametrize("name", sorted(GEOMETRIES))
+def test_ivf_workspace_is_the_restated_geometry(lib, name):
+    """test_gpu_ivf_exact.py states esr_ivf.hip's ivf_geom in Python to prove which regime each case reaches (head slots,
+    filter rounds, chunks): the library's workspace query must equal the layout that restatement implies, so a change to
+    the geometry cannot silently turn a case into another one."""
+    (nq, max_list, nprobe, k, nlist), want = GEOMETRIES[name]
+    g = ivf_geom(nq, max_list, nprobe, k, nlist)
+    assert {key: g[key] for key in want} == want
+    assert lib.esr_ivf_search_workspace_bytes(nq, nlist, max_list, nprobe, k) == \
+        ivf_workspace_bytes(g, nprobe, nlist, lib.esr_segment_sort_workspace_bytes)
+
+
+@pytest.mark.parametrize("nq,max_list,nprobe,k,nlist", [(8192, 3000, 8, 10, 1024), (8192, 3000, 128, 500, 1024),
+                                                      (8192, 20_000, 128, 500, 1024), (8192, 900, 64, 500, 4096),
+                                                      (1, 64, 1, 1, 1), (100_000, 10, 32768, 1, 32768)])
+def test_ivf_workspace_restatement_at_bench_points(lib, nq, max_list, nprobe, k, nlist):
+    g = ivf_geom(nq, max_list, nprobe, k, nlist)
+    assert lib.esr_ivf_search_workspace_bytes(nq, nlist, max_list, nprobe, k) == \
+        ivf_workspace_bytes(g, nprobe, nlist, lib.esr_segment_sort_workspace_bytes)
+
+
+def test_ivf_search_arguments_are_rejected_without_a_device(lib):
+    """esr_ivf_search validates everything before its first launch: with stand-in (non-null, aligned) pointers a bad
+    size is ESR_EINVAL with a message, a short or misaligned workspace ESR_EWORKSPACE, and a good call with a big enough
+    stated workspace fails only at the launch (not reached here: every case below stops before it)."""
+    EINVAL, EWORKSPACE = -1, -3
+    P = 256   # a stand-in device address: never dereferenced
+
+    def search(nq=4, D=64, nlist=16, max_list=100, nprobe=4, k=10, ptr=P, ws=P, ws_bytes=0):
+        return lib.esr_ivf_search(ptr, nq, D, P, P, P, nlist, max_list, P, nprobe, k, P, P, ws, ws_bytes, None)
+
+    def einval(msg, **kw):
+        assert search(**kw) == EINVAL, kw
+        assert msg in lib.esr_last_error(), (kw, lib.esr_last_error())
+
+    assert search() == EWORKSPACE and b"workspace" in lib.esr_last_error()
+    einval(b"exceeds 32768", nlist=32769, max_list=10, nprobe=4)
+    assert search(nlist=32768, max_list=10) == EWORKSPACE
+    for D in (2, 30, 101):
+        einval(b"bad sizes", D=D)
+    einval(b"bad sizes", nprobe=17)                            # nprobe > nlist
+    assert search(nprobe=16) == EWORKSPACE
+    einval(b"bad sizes", k=0)
+    einval(b"bad sizes", k=-5)
+    einval(b"bad sizes", k=1025)
+    assert search(k=1024) == EWORKSPACE
+    einval(b"bad sizes", nlist=32768, nprobe=16384, k=1024)    # nprobe k = 2^24: the select's composite
+    assert search(nlist=32768, nprobe=16383, k=1024) == EWORKSPACE
+    for kw in ({"nq": 0}, {"nlist": 0}, {"max_list": 0}, {"nprobe": 0}):
+        einval(b"bad sizes", **kw)
+    # nprobe x pitch >= 2^31 (positions slot * pitch + c no longer fit int32): checked after the workspace, so state one
+    big = 1 << 62
+    ml = (1 << 31) // 4 - 64 + 1                               # pitch = 2^29 at nprobe 4: 2^31
+    einval(b"exceeds 2^31", max_list=ml, ws_bytes=big)
+    assert search(max_list=ml, ws_bytes=0) == EWORKSPACE
+    # the null checks
+    einval(b"null pointer", ptr=None)
+    einval(b"null pointer", ws=None, ws_bytes=big)
+    assert search(ws=P + 8, ws_bytes=big) == EWORKSPACE and b"misaligned" in lib.esr_last_error()
+    need = lib.esr_ivf_search_workspace_bytes(4, 16, 100, 4, 10)
+    assert search(ws_bytes=need - 1) == EWORKSPACE
 
 
 def test_exchange_entry_points_validate_before_touching_rccl(lib):
