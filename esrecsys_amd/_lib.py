@@ -126,6 +126,12 @@ SIGNATURES = {
     "esr_sparse_sgd_scatter": (c_int, [c_vp, c_int, c_i64, c_int, c_i32p, c_i32p, c_i64, c_f32p, c_f32, c_vp]),
     "esr_rows_to_dense": (c_int, [c_f32p, c_i64, c_int, c_i32p, c_i32p, c_i64, c_f32p, c_vp]),
     "esr_dense_adam": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_f32, c_f32, c_f32, c_f32, c_i64, c_vp]),
+    "esr_adam_catchup_rows2": (c_int, [c_f32p, c_f32p, c_f32p, c_i32p, c_i64, c_int, c_i32p, c_i64, c_int,
+                                       c_f32p, c_f32p, c_f32p, c_i32p, c_i64, c_int, c_i32p, c_i64, c_int,
+                                       c_int, c_f32, c_f32, c_f32, c_f32, c_vp]),
+    "esr_sparse_adam_step_lazy": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_i32p, c_i32p, c_i64, c_f32p,
+                                          c_f32, c_f32, c_f32, c_f32, c_int, c_vp]),
+    "esr_adam_flush": (c_int, [c_f32p, c_f32p, c_f32p, c_i32p, c_i64, c_int, c_int, c_f32, c_f32, c_f32, c_f32, c_vp]),
     "esr_score_all": (c_int, [c_f32p, c_i64, c_int, c_i32p, c_int, c_f32p, c_vp]),
     "esr_argsort_columns_workspace_bytes": (c_size, [c_i64, c_int]),
     "esr_argsort_columns": (c_int, [c_f32p, c_i64, c_int, c_i32p, c_vp, c_size, c_vp]),

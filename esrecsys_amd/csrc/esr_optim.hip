@@ -15,13 +15,18 @@
 // produces for nn.Embed (wikipedia/train_cooccurence.py:86-87) and esr_dense_adam applies
 // optax.adam to every element (train_cooccurence.py:99-101,171) [upstream optax 0.1.2].
 #include "esr_common.h"
+#include "esr_adam.h"
 #include "esr_inbatch_mfma.h"
 
 #include <algorithm>
 
 namespace esr {
 
-enum SegOp { kAdagrad = 0, kSgd = 1, kToDense = 2, kMomentum = 3, kMomentumStep = 4, kMomentumStepLazy = 5 };
+enum SegOp { kAdagrad = 0, kSgd = 1, kToDense = 2, kMomentum = 3, kMomentumStep = 4, kMomentumStepLazy = 5, kAdamStepLazy = 6 };
+// what an op needs beyond (lr, eps): nothing, except lazy Adam (its nu / last arrays, betas, bias corrections, step)
+struct NoSegExtra {};
+template <int OP> struct SegExtraT { using type = NoSegExtra; };
+template <> struct SegExtraT<kAdamStepLazy> { using type = AdamLazyArgs; };
 
 template <int VEC, int NCH>
 __device__ __forceinline__ void param_load(RowRegs<VEC, NCH>& r, const void* table, int dtype, int64_t row, int D,
@@ -90,7 +95,8 @@ struct FusedTables {
 // the read-modify-write of one table row with the summed gradient g of its occurrences
 template <int VEC, int NCH, int OP>
 __device__ __forceinline__ void seg_apply(const FusedTables& ft, int dtype, int32_t vid, const RowRegs<VEC, NCH>& g,
-                                          int D, int lig, int G, int nvec, float lr, float eps) {
+                                          int D, int lig, int G, int nvec, float lr, float eps,
+                                          const typename SegExtraT<OP>::type& ex) {
   // select chain with constant indices (a runtime index into the kernarg struct would go through scratch)
   void* table = ft.table[0];
   float* accum = ft.accum[0];
@@ -103,6 +109,39 @@ __device__ __forceinline__ void seg_apply(const FusedTables& ft, int dtype, int3
       base = ft.row_offset[k];
     }
   const int64_t id = (int64_t)vid - base;
+  if constexpr (OP == kAdamStepLazy) {
+    // one WHOLE optax.adam step on a touched row of a lazily stepped table (at most two tables; their nu / last arrays in
+    // `ex`): the row is first brought up from last[row] to step now - 1 (adam_catchup: the zero-gradient steps it missed),
+    // then stepped with its summed gradient -- the run sum kToDense stores, through adam_elem, the dense kernel's
+    // arithmetic -- and marked current with step now
+    const int ti = (1 < ft.n && (int64_t)vid >= ft.row_offset[1]) ? 1 : 0;
+    float* nu = ti ? ex.nu[1] : ex.nu[0];
+    int32_t* last = ti ? ex.last[1] : ex.last[0];
+    RowRegs<VEC, NCH> w, a, b;
+    row_load(w, (const float*)table + id * D, lig, G, nvec);
+    row_load(a, accum + id * D, lig, G, nvec);
+    row_load(b, nu + id * D, lig, G, nvec);
+    adam_catchup(w, a, b, last[id], ex.now - 1, ex, lig, G);
+    const float omb1 = 1.0f - ex.b1, omb2 = 1.0f - ex.b2;
+    const int64_t V = (ti ? ft.row_offset[2] : ft.row_offset[1]) - (ti ? ft.row_offset[1] : ft.row_offset[0]);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        // (a float4 row never reaches the dense kernel's scalar tail: D % 4 == 0 makes numel a multiple of 4)
+        if (VEC == 1 && adam_is_tail(id * D + lig + k * G, V, D))
+          adam_elem_tail(w.v[k][e], a.v[k][e], b.v[k][e], g.v[k][e], ex.lr, ex.b1, ex.b2, omb1, omb2, ex.eps, ex.ibc1[0],
+                         ex.ibc2[0]);
+        else
+          adam_elem(w.v[k][e], a.v[k][e], b.v[k][e], g.v[k][e], ex.lr, ex.b1, ex.b2, omb1, omb2, ex.eps, ex.ibc1[0],
+                    ex.ibc2[0]);
+      }
+    row_store(w, (float*)table + id * D, lig, G, nvec);
+    row_store(a, accum + id * D, lig, G, nvec);
+    row_store(b, nu + id * D, lig, G, nvec);
+    if (lig == 0) last[id] = ex.now;
+    return;
+  }
   if (OP == kToDense) {
     row_store(g, (float*)table + id * D, lig, G, nvec);
   } else if (OP == kMomentum) {
@@ -195,7 +234,8 @@ template <int VEC, int NCH, int OP>
 __global__ __launch_bounds__(kBlock) void segment_update_kernel(FusedTables ft, int dtype, int D, int G,
                                                                const int32_t* __restrict__ sorted_ids,
                                                                const int32_t* __restrict__ perm, int64_t n,
-                                                               float* __restrict__ grad_rows, float lr, float eps) {
+                                                               float* __restrict__ grad_rows, float lr, float eps,
+                                                               typename SegExtraT<OP>::type ex) {
   const int lig = threadIdx.x & (G - 1);
   const int64_t gpb = kBlock / G;
   const int64_t group = (int64_t)blockIdx.x * gpb + threadIdx.x / G;
@@ -246,7 +286,7 @@ __global__ __launch_bounds__(kBlock) void segment_update_kernel(FusedTables ft, 
     }
     const bool ends = run_over || q == n || sorted_ids[q] != id;
     if (head && ends)
-      seg_apply<VEC, NCH, OP>(ft, dtype, id, g, D, lig, G, nvec, lr, eps);
+      seg_apply<VEC, NCH, OP>(ft, dtype, id, g, D, lig, G, nvec, lr, eps, ex);
     else
       row_store(g, grad_rows + (int64_t)perm[p] * D, lig, G, nvec);  // partial sum of a long run
   }
@@ -261,7 +301,7 @@ __global__ __launch_bounds__(kBlock) void segment_long_kernel(FusedTables ft, in
                                                              const int32_t* __restrict__ sorted_ids,
                                                              const int32_t* __restrict__ perm, int64_t n,
                                                              const float* __restrict__ grad_rows, float lr,
-                                                             float eps) {
+                                                             float eps, typename SegExtraT<OP>::type ex) {
   __shared__ float red[kBlock * VEC * NCH];  // [groups][lanes][NCH][VEC]
   constexpr int kPass = 4;                   // chunk boundaries screened per workgroup pass (long runs are then
                                              // spread over many workgroups instead of queueing in a few)
@@ -347,7 +387,7 @@ __global__ __launch_bounds__(kBlock) void segment_long_kernel(FusedTables ft, in
           for (int k = 0; k < NCH; ++k)
 #pragma unroll
             for (int e = 0; e < VEC; ++e) acc.v[k][e] += red[((gg * G + lig) * NCH + k) * VEC + e];
-        seg_apply<VEC, NCH, OP>(ft, dtype, id, acc, D, lig, G, nvec, lr, eps);
+        seg_apply<VEC, NCH, OP>(ft, dtype, id, acc, D, lig, G, nvec, lr, eps, ex);
       }
       __syncthreads();  // red is rewritten by the next long run
     }
@@ -403,7 +443,8 @@ __global__ __launch_bounds__(kBlock) void concat_offset_ids_kernel(IdSegments sg
 template <int OP>
 static int launch_segment_tables(const char* who, const FusedTables& ft, int dtype, int D, const int32_t* sorted_ids,
                                  const int32_t* perm, int64_t n, float* grad_rows, float lr, float eps,
-                                 hipStream_t st, bool skip_long = false) {
+                                 hipStream_t st, bool skip_long = false,
+                                 typename SegExtraT<OP>::type ex = {}) {
   const RowGeom g = row_geom(D);
   if (g.nch > kMaxChunksPerLane) {
     set_error("%s: D=%d not supported", who, D);
@@ -413,10 +454,10 @@ static int launch_segment_tables(const char* who, const FusedTables& ft, int dty
   const int grid2 = (int)std::min<int64_t>(kMaxGrid, cdiv(cdiv(n, kSegChunk), 4));  // 4 chunk boundaries per pass
   ESR_DISPATCH_ROW(g, {
     ESR_KT("segment_update_kernel", st, hipLaunchKernelGGL((segment_update_kernel<VEC, NCH, OP>), dim3(grid), dim3(kBlock), 0, st, ft, dtype, D, g.G,
-                       sorted_ids, perm, n, grad_rows, lr, eps));
+                       sorted_ids, perm, n, grad_rows, lr, eps, ex));
     if (n > kSegChunk && !skip_long)
       ESR_KT("segment_long_kernel", st, hipLaunchKernelGGL((segment_long_kernel<VEC, NCH, OP>), dim3(grid2), dim3(kBlock), 0, st, ft, dtype, D, g.G,
-                         sorted_ids, perm, n, (const float*)grad_rows, lr, eps));
+                         sorted_ids, perm, n, (const float*)grad_rows, lr, eps, ex));
   });
   return check_launch(who);
 }
@@ -444,9 +485,7 @@ __global__ __launch_bounds__(kBlock) void dense_adam_kernel(float* __restrict__ 
                                                            float eps, float inv_bc1, float inv_bc2) {
   const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
   auto upd = [&](float& pv, float& m, float& v, float gv) {
-    m = b1 * m + omb1 * gv;
-    v = b2 * v + omb2 * gv * gv;
-    pv -= lr * (m * inv_bc1) / (sqrtf(v * inv_bc2) + eps);
+    adam_elem(pv, m, v, gv, lr, b1, b2, omb1, omb2, eps, inv_bc1, inv_bc2);
   };
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += stride) {
@@ -464,7 +503,7 @@ __global__ __launch_bounds__(kBlock) void dense_adam_kernel(float* __restrict__ 
   }
   for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < numel; i += stride) {
     float pv = p[i], m = mu[i], v = nu[i];
-    upd(pv, m, v, g[i]);
+    adam_elem_tail(pv, m, v, g[i], lr, b1, b2, omb1, omb2, eps, inv_bc1, inv_bc2);
     p[i] = pv;
     mu[i] = m;
     nu[i] = v;
@@ -984,6 +1023,45 @@ int esr_sparse_adagrad_scatter_multi(void* const* tables, float* const* accums, 
               (long long)row_offsets[ntables]);
   return launch_segment_tables<kAdagrad>("esr_sparse_adagrad_scatter_multi", ft, dtype, D, sorted_vids, perm, n,
                                          grad_rows, lr, eps, as_stream(stream), long_runs == 0);
+}
+
+// lazy optax.adam: the whole step on the touched rows of one or two same-width tables (virtual rows, as
+// esr_sparse_momentum_step_multi), each caught up from last[row] first and marked `step` (kAdamStepLazy)
+int esr_sparse_adam_step_lazy(float* const* tables, float* const* mus, float* const* nus, int32_t* const* lasts,
+                              const int64_t* row_offsets, int ntables, int D, const int32_t* sorted_vids, const int32_t* perm,
+                              int64_t n, float* grad_rows, float lr, float b1, float b2, float eps, int step,
+                              esr_stream_t stream) {
+  ESR_REQUIRE(ntables >= 1 && ntables <= 2 && D > 0 && n >= 0 && step >= 1,
+              "esr_sparse_adam_step_lazy: ntables=%d not in [1, 2] or bad D=%d n=%lld step=%d", ntables, D, (long long)n, step);
+  ESR_REQUIRE(row_geom(D).nch <= kMaxChunksPerLane, "esr_sparse_adam_step_lazy: D=%d not supported", D);
+  ESR_REQUIRE(tables && mus && nus && lasts && row_offsets && sorted_vids && perm && grad_rows,
+              "esr_sparse_adam_step_lazy: null pointer");
+  ESR_REQUIRE((((uintptr_t)sorted_vids | (uintptr_t)perm) & 3) == 0 && ((uintptr_t)grad_rows & 15) == 0,
+              "esr_sparse_adam_step_lazy: misaligned ids or gradient rows");
+  FusedTables ft;
+  ft.n = ntables;
+  AdamLazyArgs ax;
+  adam_lazy_args(ax, lr, b1, b2, eps, step);
+  for (int i = 0; i < kMaxFusedTables; ++i) {
+    ft.table[i] = i < ntables ? tables[i] : nullptr;
+    ft.accum[i] = i < ntables ? mus[i] : nullptr;
+    ft.row_offset[i] = i <= ntables ? row_offsets[i] : row_offsets[ntables];
+    if (i < ntables) {
+      ESR_REQUIRE(tables[i] && mus[i] && nus[i] && lasts[i] && row_offsets[i + 1] > row_offsets[i],
+                  "esr_sparse_adam_step_lazy: bad table %d", i);
+      ESR_REQUIRE((((uintptr_t)tables[i] | (uintptr_t)mus[i] | (uintptr_t)nus[i]) & 15) == 0 && ((uintptr_t)lasts[i] & 3) == 0,
+                  "esr_sparse_adam_step_lazy: table %d: pointers must be 16-byte aligned", i);
+      ax.nu[i] = nus[i];
+      ax.last[i] = lasts[i];
+    }
+  }
+  ESR_REQUIRE(row_offsets[0] == 0, "esr_sparse_adam_step_lazy: row_offsets[0] must be 0");
+  ft.row_offset[kMaxFusedTables] = row_offsets[ntables];
+  ESR_REQUIRE(row_offsets[ntables] < ((int64_t)1 << 31), "esr_sparse_adam_step_lazy: %lld virtual rows >= 2^31",
+              (long long)row_offsets[ntables]);
+  if (n == 0) return ESR_OK;
+  return launch_segment_tables<kAdamStepLazy>("esr_sparse_adam_step_lazy", ft, ESR_F32, D, sorted_vids, perm, n, grad_rows,
+                                              lr, eps, as_stream(stream), false, ax);
 }
 
 int esr_dense_adam(float* param, float* mu, float* nu, const float* grad, int64_t numel, float lr, float b1,

@@ -843,6 +843,64 @@ def dense_adam(param, mu, nu, grad, lr, step, b1=0.9, b2=0.999, eps=1e-8):
                              float(eps), int(step), _stream()), "esr_dense_adam")
 
 
+ADAM_EXACT_STEPS = 8  # include/esr_hip.h ESR_ADAM_EXACT_STEPS: lazy Adam replays gaps up to this long bit-exactly
+
+
+def _adam_table(table, mu, nu, last, what):
+    _req(table, torch.float32, what + " table")
+    _req(mu, torch.float32, what + " mu")
+    _req(nu, torch.float32, what + " nu")
+    _req(last, torch.int32, what + " last")
+    if table.dim() != 2 or mu.shape != table.shape or nu.shape != table.shape or tuple(last.shape) != (table.shape[0],):
+        raise ValueError("%s: table, mu, nu must be the same [V, D] and last [V]" % what)
+
+
+def adam_catchup_rows(tables, step, lr, b1=0.9, b2=0.999, eps=1e-8):
+    """Lazy optax.adam: bring rows up to step - 1 before step `step` reads them.  tables = one or two tuples
+    (table, mu, nu, last, ids, modulus): the rows ids % modulus (modulus 0: ids) of that table; one launch."""
+    lib = _lib.load()
+    if not 1 <= len(tables) <= 2:
+        raise ValueError("adam_catchup_rows takes one or two tables")
+    args = []
+    for k, (table, mu, nu, last, ids, modulus) in enumerate(tables):
+        _adam_table(table, mu, nu, last, "adam_catchup_rows")
+        _req(ids, torch.int32, "ids")
+        args += [_p(table), _p(mu), _p(nu), _p(last), table.shape[0], table.shape[1], _p(ids), ids.numel(), int(modulus)]
+    if len(tables) == 1:
+        args += [0, 0, 0, 0, 0, 0, 0, 0, 0]
+    check(lib.esr_adam_catchup_rows2(*args, int(step), float(lr), float(b1), float(b2), float(eps), _stream()),
+          "esr_adam_catchup_rows2")
+
+
+def sparse_adam_step_lazy(tables, mus, nus, lasts, row_offsets, sorted_vids, perm, grad_rows, lr, step, b1=0.9,
+                          b2=0.999, eps=1e-8):
+    """Lazy optax.adam step `step` on the touched rows of one or two same-width tables (virtual rows row_offsets[t] + id,
+    sorted by segment_sort / segment_sort_multi).  Rows are caught up from their `last` first and marked `step`."""
+    lib = _lib.load()
+    nt = len(tables)
+    if not 1 <= nt <= 2 or not (len(mus) == len(nus) == len(lasts) == nt) or len(row_offsets) != nt + 1:
+        raise ValueError("sparse_adam_step_lazy takes one or two tables")
+    D = tables[0].shape[1]
+    for t, m, v, l in zip(tables, mus, nus, lasts):
+        _adam_table(t, m, v, l, "sparse_adam_step_lazy")
+        if t.shape[1] != D:
+            raise ValueError("sparse_adam_step_lazy: the tables of one launch must share D")
+    _req(grad_rows, torch.float32, "grad_rows")
+    ptrs = lambda ts: (ctypes.c_void_p * nt)(*[t.data_ptr() for t in ts])  # noqa: E731
+    offs = (ctypes.c_int64 * (nt + 1))(*[int(o) for o in row_offsets])
+    check(lib.esr_sparse_adam_step_lazy(ptrs(tables), ptrs(mus), ptrs(nus), ptrs(lasts), offs, nt, D, _p(sorted_vids), _p(perm), sorted_vids.numel(), _p(grad_rows), float(lr),
+                                        float(b1), float(b2), float(eps), int(step), _stream()),
+          "esr_sparse_adam_step_lazy")
+
+
+def adam_flush(table, mu, nu, last, step, lr, b1=0.9, b2=0.999, eps=1e-8):
+    """Lazy optax.adam: every row with last < step brought up to `step` (p, mu and nu); last = step afterwards."""
+    lib = _lib.load()
+    _adam_table(table, mu, nu, last, "adam_flush")
+    check(lib.esr_adam_flush(_p(table), _p(mu), _p(nu), _p(last), table.shape[0], table.shape[1], int(step), float(lr),
+                             float(b1), float(b2), float(eps), _stream()), "esr_adam_flush")
+
+
 # ---------------------------------------------------------------------------------------------
 def score_all(emb, token):
     """scores[v, t] = emb[v] . emb[token[t]]  -> [V, T]."""

@@ -49,13 +49,25 @@ def generate_triplets(scene_product, num_neg, seed=0):
     return train, test
 
 
+def _lazy_adam(state):
+    from ..train_state import _Adam
+    return isinstance(state.tx, _Adam) and state.tx.lazy
+
+
+def _reads(state):
+    """The parameter tree a step reads: under lazy Adam the raw tables (the step brings the rows it reads up to date
+    itself, tx.prepare; state.params would bring EVERY row up to date each step), else state.params."""
+    return state.raw_params if _lazy_adam(state) else state.params
+
+
 def _tables(state):
-    p = state.params["params"] if "params" in state.params else state.params
+    tree = _reads(state)
+    p = tree["params"] if "params" in tree else tree
     return p, p["scene_tower"]["embedding"], p["product_tower"]["embedding"]
 
 
 def _wrap(state, inner):
-    return {"params": inner} if "params" in state.params else inner
+    return {"params": inner} if "params" in _reads(state) else inner
 
 
 import os as _os
@@ -213,9 +225,16 @@ def train_step(state, scene, pos_product, neg_product, regularization, batch_siz
     pid = ops.as_ids(pos_product, dev, check_range=pt.shape[0]).reshape(-1)
     B = sid.numel()
     sparse = not getattr(state.tx, "wants_dense", False)
-    prefix = ("params",) if "params" in state.params else ()
+    prefix = ("params",) if "params" in _reads(state) else ()
     paths = [prefix + ("scene_tower", "embedding"), prefix + ("product_tower", "embedding")]
     Vs, Vp = st.shape[0], pt.shape[0]
+    nid = ops.as_ids(neg_product, dev, check_range=pt.shape[0]).reshape(-1) if neg_product is not None else None
+    if _lazy_adam(state):
+        # lazy optax.adam: the rows this batch reads are brought up to the previous step here, nobody else's
+        if state.versions:
+            state.consolidate()
+        look = [(paths[0], sid, 0), (paths[1], pid, 0)] + ([(paths[1], nid, 0)] if nid is not None else [])
+        state.tx.prepare(state.raw_params, state.opt_state, look)
     if neg_product is None and _inbatch_one_call(state, st, pt, B, precision):
         # the whole step -- gather + split, pass Q, [merge<Q> + scene-tower Adagrad] beside [pass C, merge<C>, product-tower
         # Adagrad] -- as ONE library call (esr_inbatch_train_step_f16x2; round 5)
@@ -252,7 +271,6 @@ def train_step(state, scene, pos_product, neg_product, regularization, batch_siz
         g_scene = RowGrads([sid], gq, st.shape, fused)
         g_prod = RowGrads([pid], gc, pt.shape, fused)
     else:
-        nid = ops.as_ids(neg_product, dev, check_range=pt.shape[0]).reshape(-1)
         # (no side-stream pre-sort here: the fused triplet kernel is ~12 us, there is nothing to hide the sort
         # behind and the cross-stream event round trip costs more than it saves: 0.19 vs 0.14 ms/step)
         loss, _, _, gs, gp, gn = ops.triplet_fwd_bwd(st, pt, pt, sid, pid, nid, B, regularization, batch_size,

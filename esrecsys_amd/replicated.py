@@ -20,7 +20,7 @@ the device count).
 import torch
 import torch.distributed as dist
 
-from .sharded import _Collectives, _joined
+from .sharded import _Collectives, _check_lr, _joined
 
 
 class ReplicatedTables:
@@ -76,6 +76,7 @@ def replicated_inbatch_step(rep, scene_ids, pos_ids, regularization, global_batc
     """In-batch softmax on replicated towers (rep.tables = [scene, product]): negatives are the local batch, gradients
     are normalised by the GLOBAL batch size (the sum of the per-rank losses is the global mean loss) -- the same
     semantics as sharded.sharded_inbatch_step."""
+    _check_lr(lr, "replicated_inbatch_step")
     k = rep.k
     st, pt = rep.tables
     folded = getattr(k, "inbatch_towers_fwd_bwd", None)
@@ -92,6 +93,7 @@ def replicated_inbatch_step(rep, scene_ids, pos_ids, regularization, global_batc
 def replicated_triplet_step(rep, scene_ids, pos_ids, neg_ids, regularization, global_batch_size, lr):
     """The reference triplet loss (pinterest/train_shop_the_look.py:93-109) on replicated towers: G ranks x B triplets
     == one device with G * B triplets and batch_size = G * B."""
+    _check_lr(lr, "replicated_triplet_step")
     k = rep.k
     st, pt = rep.tables
     B = scene_ids.numel()
@@ -106,6 +108,7 @@ def replicated_glove_step(rep_emb, rep_bias, inputs, target, mode, lr):
     and its [V, 1] bias table (two single-table ReplicatedTables over the same group): the loss is over this rank's
     batch, as in sharded.sharded_glove_step; every rank's occurrence ids are gathered and sorted ONCE and both tables take
     their one global update from it."""
+    _check_lr(lr, "replicated_glove_step")
     k = rep_emb.k
     ids = inputs.reshape(-1)
     gathered = rep_emb.gather_ids([ids], [0])   # (before the loss kernel: the sort needs the ids only)

@@ -45,6 +45,16 @@ def _a2a(group, out, inp, out_splits=None, in_splits=None, lane=0):
     return dist.all_to_all_single(out, inp, out_splits, in_splits, group=pg)
 
 
+def _check_lr(lr, who):
+    """The row-sharded and replicated steps run the build's row-sparse Adagrad with a plain learning rate; an optimizer
+    object (optim.adam(lazy=True) among them) is refused rather than silently replaced by something else."""
+    import numbers
+    if not isinstance(lr, numbers.Real) and not (isinstance(lr, torch.Tensor) and lr.numel() == 1):
+        raise TypeError("%s: lr must be a number (the sharded / replicated modes step row-sparse Adagrad only; "
+                        "optim.adam(lazy=True) and other optimizer objects are not supported here), got %s"
+                        % (who, type(lr).__name__))
+
+
 class RowShardedTable:
     """This rank's shard of one table: rows rank, rank + G, rank + 2G, ... and their fp32 accumulator."""
 
@@ -734,6 +744,7 @@ def sharded_inbatch_step(towers, scene_ids, pos_ids, regularization, global_batc
     """Data-parallel in-batch-softmax step on row-sharded towers (group = [scene table, product table]).
     Negatives are the local batch; gradients are normalised by the GLOBAL batch size, so the sum of the
     per-rank losses is the global mean loss.  rows: lookup_bucketed(plan) when the caller has it already (overlap)."""
+    _check_lr(lr, "sharded_inbatch_step")
     k = towers.k
     B = scene_ids.numel()
     if _world1_tables_ok(towers) and towers.tables[0].local.shape[1] <= 128 and B % 128 == 0 and \
@@ -775,6 +786,7 @@ def sharded_triplet_step(towers, scene_ids, pos_ids, neg_ids, regularization, gl
     """Reference triplet loss (pinterest/train_shop_the_look.py:93-109) on row-sharded towers.  The loss is a
     sum over triplets, so G ranks x B triplets == one device with G*B triplets and batch_size = G*B.
     rows: lookup_bucketed(plan) when the caller has it already (overlap)."""
+    _check_lr(lr, "sharded_triplet_step")
     k = towers.k
     B = scene_ids.numel()
     if (_world1_tables_ok(towers) and (_is_f32(towers) or _is_bf16(towers)) and
@@ -827,6 +839,7 @@ def sharded_glove_step(emb_group, bias_group, inputs, target, mode, lr, plan=Non
     """GloVe step on row-sharded embedding + bias tables (two single-table groups sharing one routing plan:
     same ids, same sharding, different widths); the loss is over the local batch.  rows: (lookup_bucketed of the
     embedding group, of the bias group) when the caller has them already (overlap)."""
+    _check_lr(lr, "sharded_glove_step")
     k = emb_group.k
     B = inputs.shape[1]
     if _world1_tables_ok(emb_group) and _is_f32(emb_group) and _is_f32(bias_group) and emb_group.versions() is not None:
@@ -884,6 +897,7 @@ def sharded_train_steps(workload, groups, batches, *, regularization=0.0, global
     intersection of two owner-side lists, made with the plans a group ahead), and after the update they are served again
     in a second, small exchange (patch_rows) -- results equal the sequential loop's bit for bit.  Each step is then
     lookup-patch, loss kernel, esr_sharded_update on the main stream + the next esr_sharded_lookup beside them."""
+    _check_lr(lr, "sharded_train_steps")
     from .train_state import quiet_gc
     if workload not in ("inbatch", "triplet", "glove"):
         raise ValueError("workload must be 'inbatch', 'triplet' or 'glove', got %r" % (workload,))

@@ -192,14 +192,108 @@ class GradientTransformation:
 
 class _Adam(GradientTransformation):
     """optax.adam(learning_rate, b1=0.9, b2=0.999, eps=1e-8) [upstream optax 0.1.2] -- dense, every element
-    of every table moves every step (wikipedia/train_cooccurence.py:171)."""
+    of every table moves every step (wikipedia/train_cooccurence.py:171).
+
+    lazy=True: the same trajectory without a whole-table pass per step.  A row without a gradient still moves (mu *= b1,
+    nu *= b2, p -= lr mu_hat / (sqrt(nu_hat) + eps)), a function of (p, mu, nu, step) alone, so it is moved when it is next
+    READ.  ``opt_state['_lazy']['last']`` holds per table an int32 [V]: the step each row is current with
+    (``opt_state['count']`` stays the step counter: checkpoints keep optax's {count, mu, nu}).  A step is ``prepare`` (the
+    rows the forward pass will read brought up to the previous step), the forward / backward, then ``apply`` (the whole
+    Adam step on the touched rows, catching up any the caller did not prepare).  ``flush`` brings every row (p, mu and nu)
+    up to the current step; ``TrainState.params`` does it.  Rows whose gaps stay within ops.ADAM_EXACT_STEPS are
+    bit-identical to the dense optimizer; longer gaps are applied in closed form (include/esr_hip.h states the bound).
+    fp32 tables on the GPU only."""
     wants_dense = True
 
-    def __init__(self, learning_rate, b1=0.9, b2=0.999, eps=1e-8):
+    def __init__(self, learning_rate, b1=0.9, b2=0.999, eps=1e-8, lazy=False):
         self.lr, self.b1, self.b2, self.eps = learning_rate, b1, b2, eps
+        self.lazy = bool(lazy)
+        if self.lazy:
+            self.wants_dense = False  # row-sparse RowGrads, no to_dense
+        self.needs_flush = self.lazy
 
     def init(self, params):
+        if self.lazy:
+            for path, p in tree_leaves_with_path(params):
+                if p.dtype != torch.float32 or p.dim() != 2:
+                    raise TypeError("adam(lazy=True) steps fp32 [V, D] tables only (got %s %s at %s); use "
+                                    "adam(lazy=False) or sparse_adagrad for bf16 tables"
+                                    % (p.dtype, tuple(p.shape), "/".join(map(str, path))))
         return {"count": 0, "mu": tree_map(torch.zeros_like, params), "nu": tree_map(torch.zeros_like, params)}
+
+    def _hp(self):
+        return dict(b1=self.b1, b2=self.b2, eps=self.eps)
+
+    def _lazy_state(self, params, opt_state):
+        """The books of the lazy form, created on first use: every row current with the state's count (a fresh or
+        restored state)."""
+        lz = opt_state.get("_lazy")
+        if lz is None:
+            count = int(opt_state["count"])
+            lz = opt_state["_lazy"] = {"dirty": False, "last": {
+                path: torch.full((p.shape[0],), count, dtype=torch.int32, device=p.device)
+                for path, p in tree_leaves_with_path(params)}}
+        return lz
+
+    def _lazy_ok(self, params, grads):
+        return all(p.dim() == 2 and p.is_cuda and p.dtype == torch.float32 for _, p in tree_leaves_with_path(params)) and \
+            all(isinstance(tree_get(grads, path), RowGrads) or tree_get(grads, path) is None
+                for path, _ in tree_leaves_with_path(params))
+
+    def prepare(self, params, opt_state, lookups):
+        """Start of a lazy step: lookups = [(path, int32 ids, modulus)] -- the rows the step is about to read (row =
+        id % modulus when modulus > 0).  They are brought up to the previous step (two tables per launch)."""
+        if not self.lazy:
+            return
+        lz = self._lazy_state(params, opt_state)
+        step = int(opt_state["count"]) + 1
+        todo = []
+        for path, ids, modulus in lookups:
+            path = tuple(path)
+            if path in lz["last"]:
+                todo.append((tree_get(params, path), tree_get(opt_state["mu"], path), tree_get(opt_state["nu"], path),
+                             lz["last"][path], ids, modulus))
+        for i in range(0, len(todo), 2):
+            ops.adam_catchup_rows(todo[i:i + 2], step, self.lr, **self._hp())
+        if todo:
+            lz["dirty"] = True
+
+    def flush(self, params, opt_state):
+        lz = opt_state.get("_lazy") if isinstance(opt_state, dict) else None
+        if lz is None or not lz["dirty"]:
+            return
+        for path, last in lz["last"].items():
+            ops.adam_flush(tree_get(params, path), tree_get(opt_state["mu"], path), tree_get(opt_state["nu"], path), last,
+                           int(opt_state["count"]), self.lr, **self._hp())
+        lz["dirty"] = False
+
+    def _apply_lazy(self, params, grads, opt_state):
+        lz = self._lazy_state(params, opt_state)
+        count = int(opt_state["count"]) + 1
+        done = set()
+        for path, p in tree_leaves_with_path(params):
+            g = tree_get(grads, path)
+            if g is None:
+                continue
+            f = g.fused
+            if f is not None and tuple(path) in f.paths and len(f.paths) <= 2:
+                if id(f) in done:
+                    continue
+                done.add(id(f))  # the members of a fused scatter: one sort, one launch pair
+                f.consume()
+                sorted_vids, perm = f.index.sorted()
+                ops.sparse_adam_step_lazy([tree_get(params, q) for q in f.paths], [tree_get(opt_state["mu"], q) for q in f.paths],
+                                          [tree_get(opt_state["nu"], q) for q in f.paths], [lz["last"][q] for q in f.paths],
+                                          f.row_offsets, sorted_vids, perm, f.rows, self.lr, count, **self._hp())
+                continue
+            _consume(g, "RowGrads")
+            sorted_ids, perm = g.index.sorted()
+            D = p.shape[1]
+            ops.sparse_adam_step_lazy([p], [tree_get(opt_state["mu"], path)], [tree_get(opt_state["nu"], path)],
+                                      [lz["last"][tuple(path)]], [0, p.shape[0]], sorted_ids, perm, g.rows.reshape(-1, D),
+                                      self.lr, count, **self._hp())
+        lz["dirty"] = True
+        return {"count": count, "mu": opt_state["mu"], "nu": opt_state["nu"], "_lazy": lz}
 
     # optax.adam's state is (ScaleByAdamState(count, mu, nu), EmptyState()) -> {'0': {...}, '1': {}} on the wire
     def to_optax_state(self, opt_state):
@@ -210,6 +304,10 @@ class _Adam(GradientTransformation):
         return {"count": int(np.asarray(tree["0"]["count"])), "mu": tree["0"]["mu"], "nu": tree["0"]["nu"]}
 
     def apply(self, params, grads, opt_state, step):
+        if self.lazy:
+            if self._lazy_ok(params, grads):
+                return self._apply_lazy(params, grads, opt_state)
+            self.flush(params, opt_state)  # a dense step on lazily stepped tables: bring every row up to date first
         count = opt_state["count"] + 1
         for path, p in tree_leaves_with_path(params):
             g = tree_get(grads, path)
@@ -217,6 +315,10 @@ class _Adam(GradientTransformation):
                 g = g.to_dense()
             ops.dense_adam(p, tree_get(opt_state["mu"], path), tree_get(opt_state["nu"], path), g.reshape(p.shape),
                            self.lr, count, self.b1, self.b2, self.eps)
+        if self.lazy and isinstance(opt_state.get("_lazy"), dict):  # (everybody is current with the dense step)
+            for last in opt_state["_lazy"]["last"].values():
+                last.fill_(count)
+            return {"count": count, "mu": opt_state["mu"], "nu": opt_state["nu"], "_lazy": opt_state["_lazy"]}
         return {"count": count, "mu": opt_state["mu"], "nu": opt_state["nu"]}
 
 
@@ -395,8 +497,9 @@ class _SgdMomentum(GradientTransformation):
         return opt_state
 
 
-def adam(learning_rate, b1=0.9, b2=0.999, eps=1e-8):
-    return _Adam(learning_rate, b1, b2, eps)
+def adam(learning_rate, b1=0.9, b2=0.999, eps=1e-8, lazy=False):
+    """optax.adam.  lazy=True: the same trajectory, each row moved only when it is read (see _Adam)."""
+    return _Adam(learning_rate, b1, b2, eps, lazy=lazy)
 
 
 def sparse_adagrad(learning_rate, initial_accumulator_value=0.1, eps=1e-7):

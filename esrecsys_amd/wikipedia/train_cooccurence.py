@@ -50,13 +50,23 @@ def apply_model(state, inputs, target):
     ``{'_token_embedding': {'embedding': g}, '_bias': {'embedding': g}}``; the leaves are dense [V, D] /
     [V, 1] tensors when the optimizer is the reference's dense Adam, else row-sparse ``RowGrads``.
     ``loss`` is a 0-dim device tensor (float(loss) synchronises, like a JAX device scalar)."""
-    emb = state.params["_token_embedding"]["embedding"]
-    bias = state.params["_bias"]["embedding"]
+    from ..train_state import _Adam
+    lazy = isinstance(state.tx, _Adam) and state.tx.lazy
+    if lazy and state.versions:
+        state.consolidate()
+    # (lazy optax.adam: the raw tables -- state.params would bring EVERY row up to date each step -- and the rows this
+    # batch reads are brought up to the previous step below, nobody else's)
+    p = state.raw_params if lazy else state.params
+    emb = p["_token_embedding"]["embedding"]
+    bias = p["_bias"]["embedding"]
     model = _model_of(state)
     mode = _MODES[model.loss_mode if model is not None else "reference"]
     V = emb.shape[0]
     inputs = ops.as_ids(inputs, emb.device, check_range=V)
     target = ops.as_f32(target, emb.device)
+    if lazy:
+        ids = inputs.reshape(-1)
+        state.tx.prepare(p, state.opt_state, [(("_token_embedding", "embedding"), ids, 0), (("_bias", "embedding"), ids, 0)])
     index = SegmentIndex(inputs.reshape(-1), V)  # occurrence ids = [token1 ; token2]
     loss, grad_rows, grad_bias = ops.glove_fwd_bwd(emb, bias, inputs, target, mode)
     g_emb = RowGrads(index, grad_rows, emb.shape)

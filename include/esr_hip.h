@@ -411,6 +411,39 @@ int esr_segment_sum_rows(float* out, int64_t rows_out, int D, const int32_t* sor
 int esr_dense_adam(float* param, float* mu, float* nu, const float* grad, int64_t numel, float lr,
                    float b1, float b2, float eps, int64_t step, esr_stream_t stream);
 
+/* Lazy optax.adam: the dense trajectory without a whole-table pass per step.  A row that gets no gradient still moves
+ * (mu *= b1 ; nu *= b2 ; p -= lr (mu ibc1) / (sqrt(nu ibc2) + eps)) -- a function of (p, mu, nu, t) alone -- so it is
+ * moved when it is next read.  last[row] (int32 [V]) = the step the row is current with (0 for a fresh table: every
+ * row current with step 0).  A step t >= 1 is: esr_adam_catchup_rows2 on the ids the step will read (rows brought up to
+ * step t - 1 and stamped so), the forward / backward on current rows, then esr_sparse_adam_step_lazy (the touched rows
+ * caught up if they were not, one whole Adam step with the run-summed gradient, marked t).  esr_adam_flush brings EVERY
+ * row up to step t -- before a dense step, a checkpoint, or anybody reading the whole tables.
+ *
+ * Exactness contract, against esr_dense_adam stepped on the same gradients (the dense gradient of esr_rows_to_dense):
+ *   - a touched row, and a row whose gap is <= 8 steps (ESR_ADAM_EXACT_STEPS), is bit-identical in p, mu and nu: the
+ *     same per-element operations, the same fp32 bias corrections (computed on the host in fp64, as esr_dense_adam);
+ *   - a longer gap of n steps is applied in closed form in fp64: mu and nu within 1e-6 relative of an fp64 replay of
+ *     the n zero-gradient steps, p within 1e-6 |dp| + 2 ulp(p) of it (dp = that replay's displacement);
+ *   - a row with mu = nu = 0 never moves (bit-identical).
+ * fp32 tables only.  D <= 1024 (D % 4 == 0) or D <= 256; table / mu / nu 16-byte aligned, last / ids 4-byte aligned. */
+#define ESR_ADAM_EXACT_STEPS 8
+/* Rows ids0[i] % modulus0 (modulus 0: ids0[i]) of table 0 and ids1[i] % modulus1 of table 1 up to step - 1 (ids outside
+ * [0, V) are skipped).  Table 1 is optional (table1 = NULL); the two may differ in width and row count.  One launch. */
+int esr_adam_catchup_rows2(float* table0, float* mu0, float* nu0, int32_t* last0, int64_t V0, int D0, const int32_t* ids0,
+                           int64_t n0, int modulus0, float* table1, float* mu1, float* nu1, int32_t* last1, int64_t V1,
+                           int D1, const int32_t* ids1, int64_t n1, int modulus1, int step, float lr, float b1, float b2,
+                           float eps, esr_stream_t stream);
+/* Step `step` on the touched rows of one or two same-width tables addressed by virtual rows (row_offsets[0] = 0,
+ * row_offsets[t + 1] = row_offsets[t] + V_t; sorted_vids / perm from esr_segment_sort_ids, grad_rows [n, D]).  Duplicates
+ * are summed exactly as esr_rows_to_dense sums them.  May overwrite grad_rows (partials of long runs). */
+int esr_sparse_adam_step_lazy(float* const* tables, float* const* mus, float* const* nus, int32_t* const* lasts,
+                              const int64_t* row_offsets, int ntables, int D, const int32_t* sorted_vids, const int32_t* perm,
+                              int64_t n, float* grad_rows, float lr, float b1, float b2, float eps, int step,
+                              esr_stream_t stream);
+/* Every row with last < step up to `step`; last = step afterwards. */
+int esr_adam_flush(float* table, float* mu, float* nu, int32_t* last, int64_t V, int D, int step, float lr, float b1,
+                   float b2, float eps, esr_stream_t stream);
+
 /* ---- G6: Glove.score_all + find_knn -- wikipedia/models.py:50-55, train_cooccurence.py:91-97
  * scores[v, t] = E[v] . E[token[t]]  ([V, T] row-major, no bias);
  * indices = stable ascending argsort of every column ([V, T] int32). */
