@@ -131,6 +131,8 @@ SIGNATURES = {
                                        c_int, c_f32, c_f32, c_f32, c_f32, c_vp]),
     "esr_sparse_adam_step_lazy": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_i32p, c_i32p, c_i64, c_f32p,
                                           c_f32, c_f32, c_f32, c_f32, c_int, c_vp]),
+    "esr_adam_catchup_gather": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_i32p, c_i32p, c_i64, c_f32p,
+                                        c_int, c_f32, c_f32, c_f32, c_f32, c_vp]),
     "esr_adam_flush": (c_int, [c_f32p, c_f32p, c_f32p, c_i32p, c_i64, c_int, c_int, c_f32, c_f32, c_f32, c_f32, c_vp]),
     "esr_score_all": (c_int, [c_f32p, c_i64, c_int, c_i32p, c_int, c_f32p, c_vp]),
     "esr_argsort_columns_workspace_bytes": (c_size, [c_i64, c_int]),

@@ -1,5 +1,6 @@
-// Lazy optax.adam: the catch-up of the rows a step is about to read and the flush of every row (esr_adam.h has the
-// arithmetic and the exactness contract; the step itself is esr_optim.hip's kAdamStepLazy segment update).
+// Lazy optax.adam: the catch-up of the rows a step is about to read (alone, or fused with the owner-side gather of a
+// row-sharded lookup) and the flush of every row (esr_adam.h has the arithmetic and the exactness contract; the step
+// itself is esr_optim.hip's kAdamStepLazy segment update).
 #include "esr_adam.h"
 
 #include <algorithm>
@@ -76,6 +77,89 @@ __global__ __launch_bounds__(kBlock) void adam_flush_kernel(float* __restrict__ 
     row_store(a, mu + row * D, lig, G, nvec);
     row_store(b, nu + row * D, lig, G, nvec);
     if (lig == 0) last[row] = ax.now;
+  }
+}
+
+// The owner side of a row-sharded lookup under lazy Adam: the sorted rows asked of this rank (virtual local rows of up to
+// two same-width tables at offsets off[]), each brought up to step ax.now - 1 and served.  One row group per RUN of equal
+// rows (the group at the run's first position owns it; runs are distinct, so no atomics): a row with last < now - 1 is
+// caught up and stored back (p, mu, nu, last), then written to served[perm[j]] for the first G positions j of the run (their
+// perm entries loaded by the group at once).  A longer run's other positions -- a Zipf batch asks for its top rows thousands
+// of times, which one group would walk serially -- are served by adam_serve_tail_kernel, launched behind this kernel: a
+// copy of the caught-up row.  served == nullptr: catch up only (the replicated steps).  Rows outside [0, off[nt]) are
+// skipped.
+struct AdamServeTables {
+  float* table[2];
+  float* mu[2];
+  float* nu[2];
+  int32_t* last[2];
+  int64_t off[3];
+  int nt;
+};
+
+template <int VEC, int NCH>
+__global__ __launch_bounds__(kBlock) void adam_catchup_gather_kernel(AdamServeTables at, const int32_t* __restrict__ sorted,
+                                                                    const int32_t* __restrict__ perm, int64_t n,
+                                                                    float* __restrict__ served, int D, int G,
+                                                                    AdamLazyArgs ax) {
+  const int lig = threadIdx.x & (G - 1);
+  const int64_t gpb = kBlock / G;
+  const int nvec = D / VEC;
+  const int target = ax.now - 1;
+  const int64_t end = at.off[at.nt];
+  for (int64_t i = (int64_t)blockIdx.x * gpb + threadIdx.x / G; i < n; i += (int64_t)gridDim.x * gpb) {
+    const int64_t vid = sorted[i];
+    if (i > 0 && sorted[i - 1] == vid) continue;  // not the head of its run
+    if (vid < 0 || vid >= end) continue;
+    const int t = (at.nt > 1 && vid >= at.off[1]) ? 1 : 0;
+    float* __restrict__ table = t ? at.table[1] : at.table[0];
+    const int64_t row = vid - (t ? at.off[1] : at.off[0]);
+    RowRegs<VEC, NCH> w;
+    row_load(w, table + row * D, lig, G, nvec);
+    int32_t* __restrict__ last = t ? at.last[1] : at.last[0];
+    const int t0 = last[row];
+    if (t0 < target) {  // (the same row for every lane of the group: adam_catchup's group sums see every lane)
+      float* __restrict__ mu = t ? at.mu[1] : at.mu[0];
+      float* __restrict__ nu = t ? at.nu[1] : at.nu[0];
+      RowRegs<VEC, NCH> a, b;
+      row_load(a, mu + row * D, lig, G, nvec);
+      row_load(b, nu + row * D, lig, G, nvec);
+      adam_catchup(w, a, b, t0, target, ax, lig, G);
+      row_store(w, table + row * D, lig, G, nvec);
+      row_store(a, mu + row * D, lig, G, nvec);
+      row_store(b, nu + row * D, lig, G, nvec);
+      if (lig == 0) last[row] = target;
+    }
+    if (served == nullptr) continue;
+    const int64_t j = i + lig;
+    const int pj = (j < n && sorted[j] == vid) ? perm[j] : -1;  // (sorted: the run's positions come first)
+    const int base = (threadIdx.x & (kWave - 1)) & ~(G - 1);
+    for (int c = 0; c < G; ++c) {
+      const int pc = __shfl(pj, base + c, kWave);
+      if (pc < 0) break;
+      row_store(w, served + (int64_t)pc * D, lig, G, nvec);
+    }
+  }
+}
+
+// the positions of a run beyond its first G (i >= G with sorted[i - G] == sorted[i]): the row, caught up by
+// adam_catchup_gather_kernel, copied to served[perm[i]]
+template <int VEC, int NCH>
+__global__ __launch_bounds__(kBlock) void adam_serve_tail_kernel(AdamServeTables at, const int32_t* __restrict__ sorted,
+                                                                const int32_t* __restrict__ perm, int64_t n,
+                                                                float* __restrict__ served, int D, int G) {
+  const int lig = threadIdx.x & (G - 1);
+  const int64_t gpb = kBlock / G;
+  const int nvec = D / VEC;
+  const int64_t end = at.off[at.nt];
+  for (int64_t i = (int64_t)blockIdx.x * gpb + threadIdx.x / G + G; i < n; i += (int64_t)gridDim.x * gpb) {
+    const int64_t vid = sorted[i];
+    if (sorted[i - G] != vid || vid < 0 || vid >= end) continue;
+    const int t = (at.nt > 1 && vid >= at.off[1]) ? 1 : 0;
+    const float* __restrict__ table = t ? at.table[1] : at.table[0];
+    RowRegs<VEC, NCH> w;
+    row_load(w, table + (vid - (t ? at.off[1] : at.off[0])) * D, lig, G, nvec);
+    row_store(w, served + (int64_t)perm[i] * D, lig, G, nvec);
   }
 }
 
@@ -180,6 +264,50 @@ int esr_adam_catchup_rows2(float* table0, float* mu0, float* nu0, int32_t* last0
   geo[0] = wide(geo[0]);
   geo[1] = wide(geo[1]);
   return launch_catchup(ct, 0, 2, geo, ax, st);
+}
+
+int esr_adam_catchup_gather(float* const* tables, float* const* mus, float* const* nus, int32_t* const* lasts,
+                            const int64_t* row_offsets, int ntables, int D, const int32_t* sorted_rows, const int32_t* perm,
+                            int64_t n, float* served, int step, float lr, float b1, float b2, float eps,
+                            esr_stream_t stream) {
+  ESR_REQUIRE(ntables >= 1 && ntables <= 2 && D > 0 && n >= 0 && step >= 1,
+              "esr_adam_catchup_gather: ntables=%d not in [1, 2] or bad D=%d n=%lld step=%d", ntables, D, (long long)n,
+              step);
+  const RowGeom g = wide(row_geom(D));  // the geometry esr_adam_catchup_rows2 gives a table of this width (same sums)
+  ESR_REQUIRE(g.nch <= kMaxChunksPerLane, "esr_adam_catchup_gather: D=%d not supported", D);
+  ESR_REQUIRE(tables && mus && nus && lasts && row_offsets && (n == 0 || (sorted_rows && (served == nullptr || perm))),
+              "esr_adam_catchup_gather: null pointer");  // (an empty list may come with null ids: torch's empty tensors)
+  ESR_REQUIRE((((uintptr_t)sorted_rows | (uintptr_t)perm) & 3) == 0 && ((uintptr_t)served & (D % 4 ? 3 : 15)) == 0,
+              "esr_adam_catchup_gather: misaligned ids or served rows");
+  ESR_REQUIRE(row_offsets[0] == 0, "esr_adam_catchup_gather: row_offsets[0] must be 0");
+  AdamServeTables at{};
+  at.nt = ntables;
+  for (int i = 0; i < ntables; ++i) {
+    ESR_REQUIRE(tables[i] && mus[i] && nus[i] && lasts[i] && row_offsets[i + 1] > row_offsets[i],
+                "esr_adam_catchup_gather: bad table %d", i);
+    ESR_REQUIRE(adam_ptrs_ok(tables[i], mus[i], nus[i], lasts[i], sorted_rows),
+                "esr_adam_catchup_gather: table %d: table / mu / nu must be 16-byte aligned, last 4-byte aligned", i);
+    at.table[i] = tables[i];
+    at.mu[i] = mus[i];
+    at.nu[i] = nus[i];
+    at.last[i] = lasts[i];
+  }
+  for (int i = 0; i <= 2; ++i) at.off[i] = row_offsets[std::min(i, ntables)];
+  ESR_REQUIRE(row_offsets[ntables] < ((int64_t)1 << 31), "esr_adam_catchup_gather: %lld virtual rows >= 2^31",
+              (long long)row_offsets[ntables]);
+  if (n == 0) return ESR_OK;
+  AdamLazyArgs ax;
+  adam_lazy_args(ax, lr, b1, b2, eps, step);
+  const int grid = grid_for_groups(n, g.G);
+  hipStream_t st = as_stream(stream);
+  ESR_DISPATCH_ROW(g, ESR_KT("adam_catchup_gather_kernel", st,
+                             hipLaunchKernelGGL((adam_catchup_gather_kernel<VEC, NCH>), dim3(grid), dim3(kBlock), 0, st, at,
+                                                sorted_rows, perm, n, served, D, g.G, ax)));
+  if (served == nullptr || n <= g.G) return check_launch("esr_adam_catchup_gather");
+  ESR_DISPATCH_ROW(g, ESR_KT("adam_serve_tail_kernel", st,
+                             hipLaunchKernelGGL((adam_serve_tail_kernel<VEC, NCH>), dim3(grid_for_groups(n - g.G, g.G)),
+                                                dim3(kBlock), 0, st, at, sorted_rows, perm, n, served, D, g.G)));
+  return check_launch("esr_adam_catchup_gather");
 }
 
 int esr_adam_flush(float* table, float* mu, float* nu, int32_t* last, int64_t V, int D, int step, float lr, float b1, float b2,

@@ -893,6 +893,40 @@ def sparse_adam_step_lazy(tables, mus, nus, lasts, row_offsets, sorted_vids, per
           "esr_sparse_adam_step_lazy")
 
 
+def adam_catchup_gather(tables, mus, nus, lasts, row_offsets, sorted_rows, perm, step, lr, b1=0.9, b2=0.999, eps=1e-8,
+                        out=None, serve=True):
+    """Lazy optax.adam, owner side of a row-sharded lookup: the rows sorted_rows (virtual rows of one or two same-width
+    tables, sorted by segment_sort, perm its permutation) brought up to step - 1 and served: returns out [n, D] with
+    out[perm[j]] = the caught-up row sorted_rows[j] -- what adam_catchup_rows followed by gather_rows_multi gives, bit for
+    bit, in one pass.  serve=False: catch up only (returns None)."""
+    lib = _lib.load()
+    nt = len(tables)
+    if not 1 <= nt <= 2 or not (len(mus) == len(nus) == len(lasts) == nt) or len(row_offsets) != nt + 1:
+        raise ValueError("adam_catchup_gather takes one or two tables")
+    D = tables[0].shape[1]
+    for t, m, v, l in zip(tables, mus, nus, lasts):
+        _adam_table(t, m, v, l, "adam_catchup_gather")
+        if t.shape[1] != D:
+            raise ValueError("adam_catchup_gather: the tables of one launch must share D")
+    _req(sorted_rows, torch.int32, "sorted_rows")
+    n = sorted_rows.numel()
+    if serve:
+        _req(perm, torch.int32, "perm")
+        if perm.numel() != n:
+            raise ValueError("adam_catchup_gather: sorted_rows and perm differ in length")
+        if out is None:
+            out = torch.empty((n, D), dtype=torch.float32, device=tables[0].device)
+        _req(out, torch.float32, "out")
+        if tuple(out.shape) != (n, D):
+            raise ValueError("adam_catchup_gather: out must be [%d, %d], got %s" % (n, D, tuple(out.shape)))
+    ptrs = lambda ts: (ctypes.c_void_p * nt)(*[t.data_ptr() for t in ts])  # noqa: E731
+    offs = (ctypes.c_int64 * (nt + 1))(*[int(o) for o in row_offsets])
+    check(lib.esr_adam_catchup_gather(ptrs(tables), ptrs(mus), ptrs(nus), ptrs(lasts), offs, nt, D, _p(sorted_rows),
+                                      _p(perm) if serve else None, n, _p(out) if serve else None, int(step), float(lr),
+                                      float(b1), float(b2), float(eps), _stream()), "esr_adam_catchup_gather")
+    return out if serve else None
+
+
 def adam_flush(table, mu, nu, last, step, lr, b1=0.9, b2=0.999, eps=1e-8):
     """Lazy optax.adam: every row with last < step brought up to `step` (p, mu and nu); last = step afterwards."""
     lib = _lib.load()

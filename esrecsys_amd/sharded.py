@@ -46,21 +46,111 @@ def _a2a(group, out, inp, out_splits=None, in_splits=None, lane=0):
 
 
 def _check_lr(lr, who):
-    """The row-sharded and replicated steps run the build's row-sparse Adagrad with a plain learning rate; an optimizer
-    object (optim.adam(lazy=True) among them) is refused rather than silently replaced by something else."""
+    """What the row-sharded and replicated steps do with `lr`: a plain learning rate steps the build's row-sparse Adagrad
+    ("adagrad"), optim.adam(lr, lazy=True) steps lazy Adam ("adam").  Any other optimizer object (dense adam, sgd) is
+    refused rather than silently replaced by something else."""
     import numbers
-    if not isinstance(lr, numbers.Real) and not (isinstance(lr, torch.Tensor) and lr.numel() == 1):
-        raise TypeError("%s: lr must be a number (the sharded / replicated modes step row-sparse Adagrad only; "
-                        "optim.adam(lazy=True) and other optimizer objects are not supported here), got %s"
-                        % (who, type(lr).__name__))
+    if isinstance(lr, numbers.Real) or (isinstance(lr, torch.Tensor) and lr.numel() == 1):
+        return "adagrad"
+    from .train_state import _Adam
+    if isinstance(lr, _Adam) and lr.lazy:
+        return "adam"
+    raise TypeError("%s: lr must be a number (row-sparse Adagrad) or optim.adam(lr, lazy=True) (the sharded / replicated "
+                    "modes step nothing else: dense adam and sgd move rows no step reads), got %s"
+                    % (who, type(lr).__name__))
+
+
+class _LazyAdamBooks:
+    """Lazy Adam state of same-width tables stepped together (a ShardedTableGroup's local shards, or a ReplicatedTables'
+    full copies): optax's {count, mu, nu} plus every row's `last` step, one entry per table.  The tables are addressed as
+    virtual rows row_offsets[t] + row.  Created on a holder's first Adam step; the holder refuses Adagrad from then on."""
+
+    def __init__(self, opt, kernels, tables, row_offsets, who):
+        if not hasattr(kernels, "adam_catchup_gather"):
+            raise TypeError("%s: these kernels provide no lazy Adam" % who)
+        st = opt.init({str(i): t for i, t in enumerate(tables)})  # (refuses bf16 tables as the one-GPU path does)
+        self.opt, self.k = opt, kernels
+        self.tables, self.row_offsets = list(tables), list(row_offsets)
+        self.count = int(st["count"])
+        self.mu = [st["mu"][str(i)] for i in range(len(tables))]
+        self.nu = [st["nu"][str(i)] for i in range(len(tables))]
+        self.last = [torch.zeros((t.shape[0],), dtype=torch.int32, device=t.device) for t in tables]
+
+    def same(self, opt):
+        o = self.opt
+        return opt is o or (opt.lr, opt.b1, opt.b2, opt.eps) == (o.lr, o.b1, o.b2, o.eps)
+
+    def _hp(self):
+        o = self.opt
+        return dict(b1=o.b1, b2=o.b2, eps=o.eps)
+
+    def catch_up(self, sorted_rows, perm=None, out=None, serve=False):
+        """The rows sorted_rows (sorted virtual rows) brought up to the coming step; serve: also returned as out[perm[j]]."""
+        return self.k.adam_catchup_gather(self.tables, self.mu, self.nu, self.last, self.row_offsets, sorted_rows, perm,
+                                          self.count + 1, self.opt.lr, out=out, serve=serve, **self._hp())
+
+    def step(self, sorted_rows, perm, grad_rows):
+        """The coming step on the rows sorted_rows with their gradient rows (summed per run); the count advances."""
+        step = self.count + 1
+        if sorted_rows is not None and sorted_rows.numel():
+            self.k.sparse_adam_step_lazy(self.tables, self.mu, self.nu, self.last, self.row_offsets, sorted_rows, perm,
+                                         grad_rows.contiguous(), self.opt.lr, step, **self._hp())
+        self.count = step
+
+    def flush(self):
+        for t, m, v, l in zip(self.tables, self.mu, self.nu, self.last):
+            if t.shape[0]:
+                self.k.adam_flush(t, m, v, l, self.count, self.opt.lr, **self._hp())
+
+    def optax_state(self):
+        self.flush()
+        return {"count": self.count, "mu": list(self.mu), "nu": list(self.nu)}
+
+
+def _use_optimizer(holder, lr, who, tables, row_offsets, accums):
+    """Start of a step of `holder` (ShardedTableGroup or ReplicatedTables): "adagrad" or "adam", the lazy Adam books
+    created on the first Adam step.  One holder steps one optimizer: mixing a plain learning rate with Adam is refused."""
+    kind = _check_lr(lr, who)
+    books = holder.adam
+    if kind == "adagrad":
+        if books is not None:
+            raise ValueError("%s: these tables have stepped optim.adam(lazy=True); a plain learning rate (row-sparse "
+                             "Adagrad) cannot continue them" % who)
+        if any(a is None for a in accums):
+            raise ValueError("%s: row-sparse Adagrad needs the tables' accumulators (built with local_accum=None)" % who)
+        holder._stepped_adagrad = True
+        return kind
+    if holder._stepped_adagrad:
+        raise ValueError("%s: these tables have stepped row-sparse Adagrad; optim.adam(lazy=True) cannot continue them" % who)
+    if books is None:
+        holder.adam = _LazyAdamBooks(lr, holder.k, tables, row_offsets, who)
+    elif not books.same(lr):
+        raise ValueError("%s: these tables step optim.adam with other hyper-parameters" % who)
+    return kind
+
+
+def _begin_step(holders, lr, who, cls):
+    """Start of a step of the tables `holders` (ShardedTableGroup or ReplicatedTables, `cls`): "adagrad" or "adam".  Lazy
+    Adam keeps its state (mu, nu, last, the step count) with the tables, so under it anything but a `cls` is refused with a
+    TypeError before any work; every holder then starts the step (_use_optimizer)."""
+    kind = _check_lr(lr, who)
+    if kind == "adam":
+        for h in holders:
+            if not isinstance(h, cls):
+                raise TypeError("%s: optim.adam(lazy=True) keeps its state (mu, nu, last) with the tables it steps: it "
+                                "needs a %s, got %s" % (who, cls.__name__, type(h).__name__))
+    for h in holders:
+        h.use_optimizer(lr, who)
+    return kind
 
 
 class RowShardedTable:
-    """This rank's shard of one table: rows rank, rank + G, rank + 2G, ... and their fp32 accumulator."""
+    """This rank's shard of one table: rows rank, rank + G, rank + 2G, ... and their fp32 Adagrad accumulator (None for a
+    table stepped only by lazy Adam, whose state its ShardedTableGroup keeps)."""
 
     def __init__(self, local_table, local_accum, num_rows):
         self.local = local_table      # [ceil((V - rank) / G), D]
-        self.accum = local_accum      # fp32, same shape
+        self.accum = local_accum      # fp32, same shape, or None
         self.num_rows = int(num_rows)
 
     @staticmethod
@@ -469,6 +559,32 @@ class ShardedTableGroup:
             raise ValueError("grad_dtype must be 'f32' or 'bf16', got %r" % (self.grad_dtype,))
         self._c_tables = None
         self._c_group_cache = None
+        # lazy Adam (optim.adam(lr, lazy=True) as a step's lr): the books of the local shards, created on the first Adam
+        # step -- opt_state = this rank's {count, mu, nu, last}.  The owner catches a row up when it serves it
+        # (esr_adam_catchup_gather) and steps it when its gradient rows come back; op by op, never the one-call steps.
+        self.adam = None
+        self._stepped_adagrad = False
+
+    @property
+    def opt_state(self):
+        """Lazy Adam: {count, mu, nu, last} of this rank's shards (one entry per table); None under Adagrad."""
+        a = self.adam
+        return None if a is None else {"count": a.count, "mu": a.mu, "nu": a.nu, "last": a.last}
+
+    def use_optimizer(self, lr, who):
+        """Start of a step with learning rate / optimizer `lr`: "adagrad" or "adam" (see _use_optimizer)."""
+        return _use_optimizer(self, lr, who, [t.local for t in self.tables], self.loff, [t.accum for t in self.tables])
+
+    def flush(self):
+        """Lazy Adam: every local row brought up to the group's step count (esr_adam_flush) -- table.local, mu and nu are
+        then this rank's shard of what dense optax.adam would hold.  No-op under Adagrad."""
+        if self.adam is not None:
+            self.adam.flush()
+
+    def adam_state(self):
+        """This rank's shard of optax.adam's {count, mu, nu} (mu / nu: one local [rows, D] tensor per table, rows rank,
+        rank + G, ...), flushed first: with table.local it assembles full tables or a checkpoint.  None under Adagrad."""
+        return None if self.adam is None else self.adam.optax_state()
 
     @property
     def unique(self):
@@ -492,9 +608,9 @@ class ShardedTableGroup:
         (esr_sharded_lookup / esr_sharded_update): CUDA shards and either a world of one rank or the direct RCCL exchange.
         None: op by op through `kernels` and torch.distributed (the CPU doubles of the gloo tests, ESR_SHARDED_FUSED=0)."""
         k = self.k
-        if not hasattr(k, "sharded_lookup") or os.environ.get("ESR_SHARDED_FUSED", "1") != "1" or \
-                not all(t.local.is_cuda for t in self.tables):
-            return None
+        if self.adam is not None or not hasattr(k, "sharded_lookup") or \
+                os.environ.get("ESR_SHARDED_FUSED", "1") != "1" or not all(t.local.is_cuda for t in self.tables):
+            return None  # (the one-call steps are Adagrad's: a lazy Adam group goes op by op)
         comm = None
         if self.world > 1:
             x = self.exchange(lane)
@@ -599,6 +715,14 @@ class ShardedTableGroup:
         self.consolidate()  # rows a world-1 one-pass step left in the second buffers (no-op when nothing is displaced)
         recv = plan.exchange_ids()
         back, served = buffers if buffers is not None else self.lookup_buffers(plan)
+        if self.adam is not None:  # lazy Adam: the asked rows caught up and served in one pass, then the rows exchange
+            if recv.numel():
+                srt, prm = plan.owner_sorted
+                served = self.adam.catch_up(srt, prm, out=served, serve=True)
+            elif served is None:
+                served = torch.empty((0, self.dim), dtype=back.dtype, device=back.device)
+            _a2a(self, back, served, plan.send_counts, plan.recv_counts, lane=lane)
+            return back
         fused = self._fused(lane)
         if fused is not None:  # gather + rows exchange as one library call
             comm, tc, _, lc, code = fused
@@ -649,6 +773,15 @@ class ShardedTableGroup:
                            device=grad_rows.device)
         _a2a(self, recv, grad_rows, plan.recv_counts, plan.send_counts)
         return recv
+
+    def apply_update(self, plan, grad_rows, lr, bucketed=False):
+        """The update of a step: row-sparse Adagrad (apply_sparse_adagrad) for a plain learning rate; under lazy Adam the
+        gradient rows routed to their owners and ONE lazy Adam step on the owner's sorted rows (the count advances)."""
+        if self.adam is None:
+            return self.apply_sparse_adagrad(plan, grad_rows, lr, bucketed=bucketed)
+        rows = self.route_grads(plan, grad_rows, bucketed=bucketed)
+        srt, prm = plan.owner_sorted if rows.shape[0] else (None, None)
+        self.adam.step(srt, prm, rows)
 
     def apply_sparse_adagrad(self, plan, grad_rows, lr, eps=1e-7, bucketed=False):
         """Route the gradients to their owners and update the local shards: one fused segment-reduce + RMW."""
@@ -737,14 +870,14 @@ def _joined(first, *rest):
 
 
 def _world1_tables_ok(group):
-    return group.world1_direct and all(t.local.is_cuda for t in group.tables)
+    return group.world1_direct and group.adam is None and all(t.local.is_cuda for t in group.tables)
 
 
 def sharded_inbatch_step(towers, scene_ids, pos_ids, regularization, global_batch_size, scale, lr, plan=None, rows=None):
     """Data-parallel in-batch-softmax step on row-sharded towers (group = [scene table, product table]).
     Negatives are the local batch; gradients are normalised by the GLOBAL batch size, so the sum of the
     per-rank losses is the global mean loss.  rows: lookup_bucketed(plan) when the caller has it already (overlap)."""
-    _check_lr(lr, "sharded_inbatch_step")
+    _begin_step((towers,), lr, "sharded_inbatch_step", ShardedTableGroup)
     k = towers.k
     B = scene_ids.numel()
     if _world1_tables_ok(towers) and towers.tables[0].local.shape[1] <= 128 and B % 128 == 0 and \
@@ -770,15 +903,15 @@ def sharded_inbatch_step(towers, scene_ids, pos_ids, regularization, global_batc
         iq, ic = plan.index[:B], plan.index[B:]
         if plan.unique:  # several occurrences may read one row: per-occurrence gradient rows, summed per distinct row
             loss, _, gq, gc = folded(back, back, iq, ic, scale, regularization, global_batch_size)
-            towers.apply_sparse_adagrad(plan, _joined(gq, gc), lr)
+            towers.apply_update(plan, _joined(gq, gc), lr)
             return loss
         loss, _, gbuf, _ = folded(back, back, iq, ic, scale, regularization, global_batch_size,
                                   grad_positions=(iq, ic))
-        towers.apply_sparse_adagrad(plan, gbuf, lr, bucketed=True)
+        towers.apply_update(plan, gbuf, lr, bucketed=True)
         return loss
     rows = towers.lookup(plan, back=rows)          # [q ; c]
     loss, _, gq, gc = k.inbatch_softmax_fwd_bwd(rows[:B], rows[B:], scale, regularization, global_batch_size)
-    towers.apply_sparse_adagrad(plan, _joined(gq, gc), lr)
+    towers.apply_update(plan, _joined(gq, gc), lr)
     return loss
 
 
@@ -786,7 +919,7 @@ def sharded_triplet_step(towers, scene_ids, pos_ids, neg_ids, regularization, gl
     """Reference triplet loss (pinterest/train_shop_the_look.py:93-109) on row-sharded towers.  The loss is a
     sum over triplets, so G ranks x B triplets == one device with G*B triplets and batch_size = G*B.
     rows: lookup_bucketed(plan) when the caller has it already (overlap)."""
-    _check_lr(lr, "sharded_triplet_step")
+    _begin_step((towers,), lr, "sharded_triplet_step", ShardedTableGroup)
     k = towers.k
     B = scene_ids.numel()
     if (_world1_tables_ok(towers) and (_is_f32(towers) or _is_bf16(towers)) and
@@ -820,18 +953,18 @@ def sharded_triplet_step(towers, scene_ids, pos_ids, neg_ids, regularization, gl
             loss, _, _, gs, gp, gn = k.triplet_fwd_bwd(back, back, back, inv[:B], inv[B:2 * B], inv[2 * B:], B,
                                                        regularization, global_batch_size, with_reg=True,
                                                        want_grads=True, want_scores=False)
-            towers.apply_sparse_adagrad(plan, _joined(gs, gp, gn), lr)
+            towers.apply_update(plan, _joined(gs, gp, gn), lr)
             return loss
         loss, _, _, gbuf, _, _ = k.triplet_fwd_bwd(back, back, back, inv[:B], inv[B:2 * B], inv[2 * B:], B,
                                                    regularization, global_batch_size, with_reg=True, want_grads=True,
                                                    want_scores=False, grads_at_ids=True)
-        towers.apply_sparse_adagrad(plan, gbuf, lr, bucketed=True)
+        towers.apply_update(plan, gbuf, lr, bucketed=True)
         return loss
     rows = towers.lookup(plan, back=rows)          # [scene ; pos ; neg]
     loss, _, _, gs, gp, gn = k.triplet_fwd_bwd(rows[:B], rows[B:2 * B], rows[2 * B:], None, None, None, B,
                                                regularization, global_batch_size, with_reg=True, want_grads=True,
                                                want_scores=False)
-    towers.apply_sparse_adagrad(plan, _joined(gs, gp, gn), lr)
+    towers.apply_update(plan, _joined(gs, gp, gn), lr)
     return loss
 
 
@@ -839,7 +972,7 @@ def sharded_glove_step(emb_group, bias_group, inputs, target, mode, lr, plan=Non
     """GloVe step on row-sharded embedding + bias tables (two single-table groups sharing one routing plan:
     same ids, same sharding, different widths); the loss is over the local batch.  rows: (lookup_bucketed of the
     embedding group, of the bias group) when the caller has them already (overlap)."""
-    _check_lr(lr, "sharded_glove_step")
+    _begin_step((emb_group, bias_group), lr, "sharded_glove_step", ShardedTableGroup)
     k = emb_group.k
     B = inputs.shape[1]
     if _world1_tables_ok(emb_group) and _is_f32(emb_group) and _is_f32(bias_group) and emb_group.versions() is not None:
@@ -863,16 +996,16 @@ def sharded_glove_step(emb_group, bias_group, inputs, target, mode, lr, plan=Non
         brow = brow if brow is not None else bias_group.lookup_bucketed(plan)  # [.., 1]
         loss, grad_rows, grad_bias = k.glove_fwd_bwd(rows, brow, plan.index.reshape(2, B), target, mode,
                                                      grads_at_ids=not plan.unique)
-        emb_group.apply_sparse_adagrad(plan, grad_rows, lr, bucketed=not plan.unique)
-        bias_group.apply_sparse_adagrad(plan, grad_bias.reshape(-1, 1), lr, bucketed=not plan.unique)
+        emb_group.apply_update(plan, grad_rows, lr, bucketed=not plan.unique)
+        bias_group.apply_update(plan, grad_bias.reshape(-1, 1), lr, bucketed=not plan.unique)
         return loss
     erow, brow = rows if rows is not None else (None, None)
     rows = emb_group.lookup(plan, back=erow)    # [2B, D]: E[t1] ; E[t2]
     brow = bias_group.lookup(plan, back=brow)   # [2B, 1]
     local_inputs = torch.arange(2 * B, dtype=torch.int32, device=rows.device).reshape(2, B)
     loss, grad_rows, grad_bias = k.glove_fwd_bwd(rows, brow, local_inputs, target, mode)
-    emb_group.apply_sparse_adagrad(plan, grad_rows, lr)
-    bias_group.apply_sparse_adagrad(plan, grad_bias.reshape(-1, 1), lr)
+    emb_group.apply_update(plan, grad_rows, lr)
+    bias_group.apply_update(plan, grad_bias.reshape(-1, 1), lr)
     return loss
 
 
@@ -897,7 +1030,12 @@ def sharded_train_steps(workload, groups, batches, *, regularization=0.0, global
     intersection of two owner-side lists, made with the plans a group ahead), and after the update they are served again
     in a second, small exchange (patch_rows) -- results equal the sequential loop's bit for bit.  Each step is then
     lookup-patch, loss kernel, esr_sharded_update on the main stream + the next esr_sharded_lookup beside them."""
-    _check_lr(lr, "sharded_train_steps")
+    adam = _check_lr(lr, "sharded_train_steps") == "adam"
+    if adam:  # (the steps start the groups; refuse what cannot hold lazy Adam's state before any batch is planned)
+        for g in groups:
+            if not isinstance(g, ShardedTableGroup):
+                raise TypeError("sharded_train_steps: optim.adam(lazy=True) keeps its state (mu, nu, last) with the tables "
+                                "it steps: it needs ShardedTableGroups, got %s" % type(g).__name__)
     from .train_state import quiet_gc
     if workload not in ("inbatch", "triplet", "glove"):
         raise ValueError("workload must be 'inbatch', 'triplet' or 'glove', got %r" % (workload,))
@@ -922,13 +1060,16 @@ def sharded_train_steps(workload, groups, batches, *, regularization=0.0, global
             return sharded_inbatch_step(g0, b[0], b[1], regularization, gbs, scale, lr, plan=plan, rows=rows)
         return sharded_triplet_step(g0, b[0], b[1], b[2], regularization, gbs, lr, plan=plan, rows=rows)
 
+    if overlap is None:
+        overlap = os.environ.get("ESR_SHARDED_OVERLAP", "0") == "1"
+    if overlap and adam:
+        raise ValueError("sharded_train_steps: overlap does not work with optim.adam(lazy=True): the early lookup of batch "
+                         "k + 1 would catch up rows that batch k is about to step")
     losses = []
     if not batches:
         return losses
-    if overlap is None:
-        overlap = os.environ.get("ESR_SHARDED_OVERLAP", "0") == "1"
     with quiet_gc():  # a full cyclic collection inside the loop is a 40 ms hole in the launch stream
-        if g0.world1_direct:  # a world of one rank takes the single-GPU steps: nothing is routed
+        if g0.world1_direct and not adam:  # a world of one rank takes the single-GPU steps: nothing is routed
             for b in batches:
                 losses.append(step(b, None))
             return losses

@@ -440,6 +440,19 @@ int esr_sparse_adam_step_lazy(float* const* tables, float* const* mus, float* co
                               const int64_t* row_offsets, int ntables, int D, const int32_t* sorted_vids, const int32_t* perm,
                               int64_t n, float* grad_rows, float lr, float b1, float b2, float eps, int step,
                               esr_stream_t stream);
+/* The owner side of a row-sharded lookup under lazy Adam, in one pass: catch up and serve.  sorted_rows / perm =
+ * esr_segment_sort_ids of the n virtual rows asked of this rank (row_offsets as esr_sparse_adam_step_lazy, one or two
+ * same-width tables).  Every distinct row is brought up to step - 1 if last < step - 1 (p, mu, nu stored back, last =
+ * step - 1) and written to served[perm[j]] ([n, D] fp32) for every j of its run; duplicate requests get the same bytes.
+ * One launch; a second, copy-only one serves the positions of runs longer than the row group (Zipf batches).
+ * served = NULL: catch up only (perm may then be NULL).  Rows outside [0, row_offsets[ntables]) are skipped.
+ * Exactness: served rows, p, mu, nu and last are bit-identical to esr_adam_catchup_rows2 on each table's rows followed
+ * by esr_gather_rows_multi on sorted_rows, for short and long gaps alike (the same per-row geometry and arithmetic).
+ * served 16-byte aligned (4-byte when D % 4 != 0), sorted_rows / perm 4-byte aligned; tables as above. */
+int esr_adam_catchup_gather(float* const* tables, float* const* mus, float* const* nus, int32_t* const* lasts,
+                            const int64_t* row_offsets, int ntables, int D, const int32_t* sorted_rows, const int32_t* perm,
+                            int64_t n, float* served, int step, float lr, float b1, float b2, float eps,
+                            esr_stream_t stream);
 /* Every row with last < step up to `step`; last = step afterwards. */
 int esr_adam_flush(float* table, float* mu, float* nu, int32_t* last, int64_t V, int D, int step, float lr, float b1,
                    float b2, float eps, esr_stream_t stream);
