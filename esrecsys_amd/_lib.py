@@ -164,6 +164,9 @@ SIGNATURES = {
                                     c_f32p, c_i32p, c_f32p, c_f32p, c_vp, c_size, c_vp]),
     "esr_spotify_affinity_all": (c_int, [c_f32p, c_i64, c_f32p, c_i64, c_int, c_i32p, c_i32p, c_int, c_i32p, c_i32p,
                                          c_i64, c_f32p, c_vp]),
+    "esr_spotify_topk_batch_workspace_bytes": (c_size, [c_i64, c_int, c_i64, c_int, c_int]),
+    "esr_spotify_topk_batch": (c_int, [c_f32p, c_i64, c_f32p, c_i64, c_int, c_i32p, c_i32p, c_i64, c_int, c_i32p, c_i32p,
+                                       c_i64, c_int, c_f32p, c_i32p, c_vp, c_size, c_vp]),
     "esr_dense_momentum_decay": (c_int, [c_f32p, c_f32p, c_i64, c_f32, c_f32, c_vp]),
     "esr_sparse_momentum_scatter": (c_int, [c_f32p, c_f32p, c_i64, c_int, c_i32p, c_i32p, c_i64, c_f32p, c_f32,
                                             c_vp]),

@@ -822,6 +822,40 @@ def spotify_affinity_all(album_table, artist_table, ctx_album, ctx_artist, all_a
     return out
 
 
+def spotify_topk_batch(album_table, artist_table, ctx_album, ctx_artist, all_albums, all_artists, k):
+    """top_k(affinity, k) over every track for P playlists at once (train_spotify.py:113-120 over the eval loop of
+    :270-281): ctx_album / ctx_artist [P, n] -> (scores [P, k] f32, indices [P, k] int32), best first, ties to the
+    lower track index.  Row p equals what spotify_affinity_all + a top-k give playlist p, bit for bit."""
+    lib = _lib.load()
+    _req(album_table, torch.float32, "album_table"), _req(artist_table, torch.float32, "artist_table")
+    for t, name in ((ctx_album, "ctx_album"), (ctx_artist, "ctx_artist"), (all_albums, "all_albums"),
+                    (all_artists, "all_artists")):
+        _req(t, torch.int32, name)
+    if album_table.dim() != 2 or artist_table.dim() != 2 or album_table.shape[1] != artist_table.shape[1]:
+        raise ValueError("album_table / artist_table must be [rows, F] of one width F")
+    if ctx_album.dim() != 2 or ctx_album.shape != ctx_artist.shape:
+        raise ValueError("ctx_album / ctx_artist must both be [P, n], got %s and %s"
+                         % (tuple(ctx_album.shape), tuple(ctx_artist.shape)))
+    P, n = ctx_album.shape
+    T = all_albums.numel()
+    if all_artists.numel() != T:
+        raise ValueError("all_albums and all_artists differ in length (%d vs %d)" % (T, all_artists.numel()))
+    F = album_table.shape[1]
+    if not (P >= 1 and 1 <= n <= 32 and 1 <= F and 2 * F <= 256 and 1 <= k <= min(T, 1024)):
+        raise ValueError("spotify_topk_batch: P=%d n=%d F=%d T=%d k=%d (P >= 1, 1 <= n <= 32, 2F <= 256, "
+                         "1 <= k <= min(T, 1024))" % (P, n, F, T, k))
+    dev = album_table.device
+    scores = torch.empty((P, k), dtype=torch.float32, device=dev)
+    indices = torch.empty((P, k), dtype=torch.int32, device=dev)
+    # (not through _ws_bytes' cache: the chunk plan reads ESR_SPOTIFY_EVAL_CHUNK at every call)
+    ws = _ws(lib.esr_spotify_topk_batch_workspace_bytes(P, n, T, F, k), dev)
+    check(lib.esr_spotify_topk_batch(_p(album_table), album_table.shape[0], _p(artist_table), artist_table.shape[0], F,
+                                     _p(ctx_album), _p(ctx_artist), P, n, _p(all_albums), _p(all_artists), T, int(k),
+                                     _p(scores), _p(indices), _p(ws), ws.numel(), _stream()),
+          "esr_spotify_topk_batch")
+    return scores, indices
+
+
 def rows_to_dense(V, D, sorted_ids, perm, grad_rows, out=None):
     """The dense [V, D] gradient (zero-filled, segment sums scattered) the reference's autodiff yields."""
     lib = _lib.load()

@@ -2,6 +2,7 @@
 
 ``train_step(state, x, regularization) -> (new_state, loss)`` and ``eval_step(state, y, all_tracks, all_albums,
 all_artists) -> metrics[2]`` keep the reference's signatures; ``x`` / ``y`` are the reference's feature dicts.
+``eval_batch`` / ``eval_steps`` score many playlists per library call and return what the per-playlist loop returns.
 The optimizer of the reference is ``optax.sgd(learning_rate, momentum)`` = ``esrecsys_amd.optim.sgd(lr, momentum)``.
 """
 import numpy as np
@@ -87,6 +88,98 @@ def eval_step(state, y, all_tracks, all_albums, all_artists):
     tracks_recall = torch.isin(tracks, nt).sum().float() / nt.numel()
     artists_recall = torch.isin(artists, na).sum().float() / na.numel()
     return torch.stack([tracks_recall, artists_recall])
+
+
+def _context_length(ys):
+    """The common context length of a batch of playlists (ValueError for an empty batch or mixed lengths)."""
+    if len(ys) == 0:
+        raise ValueError("an empty batch of playlists")
+    size = lambda v: v.numel() if isinstance(v, torch.Tensor) else int(np.size(v))  # noqa: E731
+    lens = {size(y["album_context"]) for y in ys} | {size(y["artist_context"]) for y in ys}
+    if len(lens) != 1:
+        raise ValueError("the playlists of one batch must have one context length, got %s" % sorted(lens))
+    return lens.pop()
+
+
+def _stack_ids(values, dev):
+    """[P, n] int32 on `dev` from P id lists: one upload when they are host arrays."""
+    if any(isinstance(v, torch.Tensor) for v in values):
+        return torch.stack([ops.as_ids(v, dev).reshape(-1) for v in values])
+    return ops.as_ids(np.stack([np.asarray(v).reshape(-1) for v in values]), dev)
+
+
+def all_track_top_k_batch(state, ys, all_albums, all_artists, k=TOP_K):
+    """all_track_top_k for a batch of playlists (the reference's feature dicts, one context length): (scores [P, k],
+    indices [P, k]), row p bit-identical to all_track_top_k(state, ys[p], ...).  One library call scores the corpus
+    for all of them (esr_spotify_topk_batch); the tables are read through state.params once."""
+    _context_length(ys)
+    p = state.params["params"]
+    at, rt = p["album_embed"]["embedding"], p["artist_embed"]["embedding"]
+    dev = at.device
+    ca, cr = _stack_ids([y["album_context"] for y in ys], dev), _stack_ids([y["artist_context"] for y in ys], dev)
+    aa, rr = ops.as_ids(all_albums, dev).reshape(-1), ops.as_ids(all_artists, dev).reshape(-1)
+    return ops.spotify_topk_batch(at, rt, ca, cr, aa, rr, min(k, aa.numel()))
+
+
+_NO_ID = 1 << 40  # pads the ragged next lists: above every int32 id
+
+
+def _recall(top_ids, nexts, dev):
+    """Per row: how many of top_ids [P, k] are in that row's next list, over the list's length (eval_step's
+    isin(...).sum().float() / numel, row by row)."""
+    if any(isinstance(v, torch.Tensor) for v in nexts):
+        rows = [ops.as_ids(v, dev).reshape(-1) for v in nexts]
+        lens = [r.numel() for r in rows]
+        L = max(lens)
+        # one scatter of all the lists (a copy per row was a launch per playlist)
+        at_row = np.repeat(np.arange(len(rows)), lens)
+        at_col = np.arange(at_row.size) - np.repeat(np.cumsum(lens) - lens, lens)
+        pad = torch.full((len(rows), L), _NO_ID, dtype=torch.int64, device=dev)
+        pad[torch.from_numpy(at_row).to(dev), torch.from_numpy(at_col).to(dev)] = torch.cat(rows).long()
+    else:
+        rows = [np.asarray(v).reshape(-1) for v in nexts]
+        L = max(r.size for r in rows)
+        pad = np.full((len(rows), L), _NO_ID, dtype=np.int64)
+        for i, r in enumerate(rows):
+            pad[i, :r.size] = r
+        pad = torch.from_numpy(pad).to(dev)
+        lens = [r.size for r in rows]
+    pad = pad.sort(dim=1).values
+    ids = top_ids.long()
+    pos = torch.searchsorted(pad, ids).clamp_(max=L - 1)
+    hits = (pad.gather(1, pos) == ids).sum(dim=1)
+    # eval_step's `count.float() / numel` divides a device tensor by a host scalar, which torch computes as
+    # count * (1 / numel) with the reciprocal rounded to float32 on the host: the same here, row by row
+    inv = torch.from_numpy(np.float32(1.0) / np.asarray(lens, dtype=np.float32)).to(dev)
+    return hits.float() * inv
+
+
+def eval_batch(state, ys, all_tracks, all_albums, all_artists):
+    """eval_step for a batch of playlists: metrics [P, 2], row p bit-identical to eval_step(state, ys[p], ...)."""
+    _, top = all_track_top_k_batch(state, ys, all_albums, all_artists)
+    dev = top.device
+    top = top.long()
+    tracks = ops.as_ids(all_tracks, dev).reshape(-1)[top]
+    artists = ops.as_ids(all_artists, dev).reshape(-1)[top]
+    return torch.stack([_recall(tracks, [y["next_track"] for y in ys], dev),
+                        _recall(artists, [y["next_artist"] for y in ys], dev)], dim=1)
+
+
+def eval_steps(state, test_it, eval_steps, all_tracks, all_albums, all_artists, batch=256):
+    """The eval of train_spotify.py:270-276: `eval_steps` playlists drawn from `test_it`, their eval_step metrics summed
+    in float32 in playlist order and divided by eval_steps -- bit for bit the reference's loop -- scored `batch`
+    playlists per call.  Returns the average metrics [2] (float32, on the tables' device)."""
+    if eval_steps < 1 or batch < 1:
+        raise ValueError("eval_steps and batch must be >= 1, got %d and %d" % (eval_steps, batch))
+    s = np.zeros(2, np.float32)
+    left = eval_steps
+    while left:
+        ys = [next(test_it) for _ in range(min(batch, left))]
+        left -= len(ys)
+        for m in eval_batch(state, ys, all_tracks, all_albums, all_artists).cpu().numpy():
+            s = s + m                      # sequential, as the loop's sum_metrics = sum_metrics + eval_metrics
+    dev = state.params["params"]["album_embed"]["embedding"].device
+    return torch.from_numpy(s).to(dev) / eval_steps   # (the loop's division, by the same torch kernel)
 
 
 def sample_negative(x, rng, num_negatives, all_tracks, all_albums, all_artists):

@@ -590,6 +590,18 @@ int esr_spotify_affinity_all(const float* album_table, int64_t n_album_rows, con
                              int64_t n_artists, int F, const int32_t* ctx_album, const int32_t* ctx_artist,
                              int n, const int32_t* all_albums, const int32_t* all_artists, int64_t T,
                              float* affinity, esr_stream_t stream);
+/* eval_step's top_k over every track (train_spotify.py:113-131) for P playlists at once (the eval loop of :270-281):
+ * ctx_album / ctx_artist [P * n] raw ids (n context tracks per playlist), out_scores / out_indices [P * k], best first,
+ * ties to the lower track index.  Every score has the bits esr_spotify_affinity_all gives that playlist, so the result
+ * equals its top-k.  1 <= n <= 32, 2F <= 256, P >= 1, 1 <= k <= min(T, 1024).  The workspace holds no [P, T] scores:
+ * the first chunk of tracks is scored densely, later chunks append only what reaches each playlist's running
+ * k-th best (lists of ~1 GiB in all; ESR_SPOTIFY_EVAL_CHUNK sets the tracks per chunk). */
+size_t esr_spotify_topk_batch_workspace_bytes(int64_t P, int n, int64_t T, int F, int k);
+int esr_spotify_topk_batch(const float* album_table, int64_t n_album_rows, const float* artist_table,
+                           int64_t n_artists, int F, const int32_t* ctx_album, const int32_t* ctx_artist, int64_t P,
+                           int n, const int32_t* all_albums, const int32_t* all_artists, int64_t T, int k,
+                           float* out_scores, int32_t* out_indices, void* workspace, size_t workspace_bytes,
+                           esr_stream_t stream);
 /* optax.sgd(lr, momentum) [upstream] in two halves: the decay over the whole table (trace *= momentum;
  * p -= lr * trace) and the row-sparse gradient (trace[row] += g; p[row] -= lr * g, duplicates summed in
  * occurrence order first).  Together: trace' = g + momentum * trace, p' = p - lr * trace'. */
