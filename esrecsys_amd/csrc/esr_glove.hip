@@ -1605,7 +1605,10 @@ int esr_rows_consolidate(void* primary, const void* shadow, uint8_t* loc, int64_
   ESR_REQUIRE(dtype == ESR_F32 || dtype == ESR_BF16, "esr_rows_consolidate: bad dtype %d", dtype);
   if (V == 0) return ESR_OK;
   ESR_REQUIRE(primary && shadow && loc, "esr_rows_consolidate: null pointer");
-  const bool vec = D % 4 == 0;  // four elements per lane: 16 bytes of an f32 row, 8 of a bf16 row
+  // four elements per lane: 16 bytes of an f32 row, 8 of a bf16 row -- where both buffers are aligned for such
+  // accesses (a sliced view need not be: the train steps refuse it, a plain copy takes the element-wise kernel)
+  const uintptr_t lane_bytes = dtype == ESR_BF16 ? 8 : 16;
+  const bool vec = D % 4 == 0 && (((uintptr_t)primary | (uintptr_t)shadow) & (lane_bytes - 1)) == 0;
   const int nchunk = vec ? D / 4 : D;
   int G = 1;
   while (G < nchunk && G < kWave) G <<= 1;

@@ -92,6 +92,15 @@ struct FusedTables {
   int n;
 };
 
+// one element of optax.sgd(lr, momentum)'s step: trace = g + m * trace ; p = p - lr * trace, four roundings.  Contraction
+// is switched off for these two lines: left to -ffp-contract=fast they became two FMAs, an ulp away from the float32
+// restatement in some elements of every row (tests/test_gpu_segment_update.py holds the step to it bit for bit).
+__device__ __forceinline__ void momentum_step_elem(float& p, float& t, float g, float lr, float m) {
+#pragma clang fp contract(off)
+  t = g + m * t;
+  p = p - lr * t;
+}
+
 // the read-modify-write of one table row with the summed gradient g of its occurrences
 template <int VEC, int NCH, int OP>
 __device__ __forceinline__ void seg_apply(const FusedTables& ft, int dtype, int32_t vid, const RowRegs<VEC, NCH>& g,
@@ -161,17 +170,15 @@ __device__ __forceinline__ void seg_apply(const FusedTables& ft, int dtype, int3
   } else if (OP == kMomentumStep) {
     // one WHOLE step of optax.sgd(lr, momentum) on a touched row (lazy mode: no dense decay pass runs; the row was
     // brought up to the previous step by momentum_catchup_kernel): trace = g + momentum * trace ; p -= lr * trace, in
-    // optax's own order and with explicit roundings.  `eps` carries the momentum.
+    // optax's own order and with every operation rounded on its own: the float32 oracle's bits (momentum_step_elem;
+    // __fmul_rn / __fadd_rn alone do not say so to hipcc, see esr_common.h).  `eps` carries the momentum.
     RowRegs<VEC, NCH> w, a;
     param_load(w, table, dtype, id, D, lig, G, nvec);
     row_load(a, accum + id * D, lig, G, nvec);
 #pragma unroll
     for (int k = 0; k < NCH; ++k)
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        a.v[k][e] = __fadd_rn(g.v[k][e], __fmul_rn(eps, a.v[k][e]));
-        w.v[k][e] = __fsub_rn(w.v[k][e], __fmul_rn(lr, a.v[k][e]));
-      }
+      for (int e = 0; e < VEC; ++e) momentum_step_elem(w.v[k][e], a.v[k][e], g.v[k][e], lr, eps);
     row_store(a, accum + id * D, lig, G, nvec);
     param_store(w, table, dtype, id, D, lig, G, nvec);
   } else if (OP == kMomentumStepLazy) {
@@ -193,8 +200,7 @@ __device__ __forceinline__ void seg_apply(const FusedTables& ft, int dtype, int3
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
         if (steps > 0) decay_apply(w.v[k][e], a.v[k][e], dk, lr, eps);
-        a.v[k][e] = __fadd_rn(g.v[k][e], __fmul_rn(eps, a.v[k][e]));
-        w.v[k][e] = __fsub_rn(w.v[k][e], __fmul_rn(lr, a.v[k][e]));
+        momentum_step_elem(w.v[k][e], a.v[k][e], g.v[k][e], lr, eps);
       }
     row_store(a, accum + id * D, lig, G, nvec);
     param_store(w, table, dtype, id, D, lig, G, nvec);

@@ -538,6 +538,12 @@ def inbatch_softmax_fwd_bwd(Q, C, scale, regularization, batch_size, precision="
     if C.shape != Q.shape:
         raise ValueError("Q and C must have the same shape")
     path = inbatch_split_path(precision, B, D)
+    if pass_c_forms is not None:  # checked before anything is launched: the library copies 8 int32 into it
+        if path != "f16x2":
+            raise ValueError("pass_c_forms: only the f16x2 path has them (this call took %r)" % path)
+        _req(pass_c_forms, torch.int32, "pass_c_forms")
+        if pass_c_forms.numel() < 8:
+            raise ValueError("pass_c_forms must hold at least 8 int32, got %d" % pass_c_forms.numel())
     dev = Q.device
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     lse = torch.empty(B, dtype=torch.float32, device=dev)
@@ -555,9 +561,6 @@ def inbatch_softmax_fwd_bwd(Q, C, scale, regularization, batch_size, precision="
     check(fn(_p(Q), _p(C), B, D, float(scale), float(regularization), float(batch_size), _p(loss), _p(lse), _p(gQ),
              _p(gC), _p(ws), ws.numel(), _stream()), name)
     if pass_c_forms is not None:  # diagnostics: which form pass C took per pass-Q split (include/esr_hip.h)
-        if path != "f16x2":
-            raise ValueError("pass_c_forms: only the f16x2 path has them (this call took %r)" % path)
-        _req(pass_c_forms, torch.int32, "pass_c_forms")
         check(lib.esr_inbatch2h_pass_c_forms(_p(ws), ws.numel(), B, _p(pass_c_forms), _stream()),
               "esr_inbatch2h_pass_c_forms")
     return loss, lse, gQ, gC
@@ -727,6 +730,24 @@ def sparse_momentum_step(table, trace, sorted_ids, perm, grad_rows, lr, momentum
     V, D = table.shape
     check(lib.esr_sparse_momentum_step(_p(table), _p(trace), V, D, _p(sorted_ids), _p(perm), sorted_ids.numel(),
                                        _p(grad_rows), float(lr), float(momentum), _stream()), "esr_sparse_momentum_step")
+
+
+def sparse_momentum_step_multi(tables, traces, row_offsets, sorted_vids, perm, grad_rows, lr, momentum):
+    """sparse_momentum_step over several same-width f32 tables addressed by virtual rows (one sort, one launch pair)."""
+    lib = _lib.load()
+    n_t = len(tables)
+    D = tables[0].shape[1] if tables[0].dim() > 1 else 1
+    for t, a in zip(tables, traces):
+        _req(t, torch.float32, "table"), _req(a, torch.float32, "trace")
+        if (t.shape[1] if t.dim() > 1 else 1) != D or a.numel() != t.numel():
+            raise ValueError("fused tables must share D and have matching traces")
+    _req(grad_rows, torch.float32, "grad_rows")
+    n = sorted_vids.numel()
+    tp = (ctypes.c_void_p * n_t)(*[t.data_ptr() for t in tables])
+    ap = (ctypes.c_void_p * n_t)(*[a.data_ptr() for a in traces])
+    ro = (ctypes.c_int64 * (n_t + 1))(*[int(o) for o in row_offsets])
+    check(lib.esr_sparse_momentum_step_multi(tp, ap, ro, n_t, D, _p(sorted_vids), _p(perm), n, _p(grad_rows), float(lr),
+                                             float(momentum), _stream()), "esr_sparse_momentum_step_multi")
 
 
 def momentum_flush(table, trace, last, step, lr, momentum):

@@ -1031,37 +1031,12 @@ def test_segment_sum_order_is_fixed(dev):
     dense = N(ops.rows_to_dense(V, D, sid, perm, T(rows, dev)))
     again = N(ops.rows_to_dense(V, D, sid, perm, T(rows, dev)))
     assert np.array_equal(dense, again)
-    order = np.argsort(ids, kind="stable")
-    sids = ids[order]
+    # the order, restated in numpy (tests/_segment_sum_ref.py); D = 32 -> 8 lanes per row group -> 32 groups per workgroup
+    from _segment_sum_ref import expected_run_sums, geom
+    assert geom(D).NG == 256 // 8
+    uniq, sums = expected_run_sums(ids, rows, D)
     exp = np.zeros((V, D), np.float32)
-    NG = 256 // 8                 # D = 32 -> 8 lanes per row group -> 32 groups per workgroup
-    p = 0
-    while p < n:
-        q = p
-        while q < n and sids[q] == sids[p]:
-            q += 1
-        parts, c = [], p          # chunk partials: head chunk, then aligned chunks of 32
-        while c < q:
-            e = min(((c + 63) // 32) * 32 if c == p else c + 32, q)
-            acc = rows[order[c]].copy()
-            for k in range(c + 1, e):
-                acc = acc + rows[order[k]]
-            parts.append(acc)
-            c = e
-        if len(parts) == 1:
-            total = parts[0]
-        else:
-            sums = []
-            for g in range(min(NG, len(parts))):
-                acc = np.zeros(D, np.float32)
-                for i in range(g, len(parts), NG):
-                    acc = acc + parts[i]
-                sums.append(acc)
-            total = sums[0]
-            for g in range(1, len(sums)):
-                total = total + sums[g]
-        exp[sids[p]] = total
-        p = q
+    exp[uniq] = sums
     assert np.array_equal(dense, exp)
     seq = np.zeros((V, D), np.float64)
     np.add.at(seq, ids, rows.astype(np.float64))
