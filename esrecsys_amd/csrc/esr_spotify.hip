@@ -628,7 +628,8 @@ static int sp_launch_affinity(const SpWs& w, SpShape sh, const int32_t* album_id
 
 static int sp_check(const char* who, int n, int m, int o, int F, int64_t A, int64_t n_artists) {
   if (!(n > 0 && m > 0 && o > 0 && F > 0 && A > 0 && n_artists > 0 && n <= kSpMaxCtx && 2 * F <= kSpMaxDim)) {
-    set_error("%s: bad sizes n=%d m=%d o=%d F=%d (n <= %d, 2F <= %d)", who, n, m, o, F, kSpMaxCtx, kSpMaxDim);
+    set_error("%s: bad sizes n=%d m=%d o=%d F=%d rows=%lld/%lld (1 <= n <= %d, m >= 1, o >= 1, 1 <= F, 2F <= %d, rows >= 1)",
+              who, n, m, o, F, (long long)A, (long long)n_artists, kSpMaxCtx, kSpMaxDim);
     return ESR_EINVAL;
   }
   return ESR_OK;

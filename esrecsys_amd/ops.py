@@ -773,8 +773,18 @@ def spotify_get_embeddings(album_table, artist_table, album_ids, artist_ids):
     return out
 
 
+def _sp_occurrences(who, album_ids, artist_ids, n, m, o):
+    """The kernels read n + m + o ids from both tensors: a shorter one would be read past its end on the device."""
+    R = int(n) + int(m) + int(o)
+    for t, name in ((album_ids, "album_ids"), (artist_ids, "artist_ids")):
+        if isinstance(t, torch.Tensor) and t.numel() != R:
+            raise ValueError("%s: %s holds %d entries, n + m + o = %d + %d + %d = %d are required"
+                             % (who, name, t.numel(), n, m, o, R))
+
+
 def spotify_forward(album_table, artist_table, album_ids, artist_ids, n, m, o):
     """SpotifyModel.__call__ (spotify/models.py:53-90) on occurrence ids ordered context, next, neg."""
+    _sp_occurrences("spotify_forward", album_ids, artist_ids, n, m, o)
     lib = _lib.load()
     _req(album_table, torch.float32, "album_table"), _req(artist_table, torch.float32, "artist_table")
     album_ids, artist_ids = _req(album_ids, torch.int32, "album_ids"), _req(artist_ids, torch.int32, "artist_ids")
@@ -791,6 +801,7 @@ def spotify_forward(album_table, artist_table, album_ids, artist_ids, n, m, o):
 def spotify_fwd_bwd(album_table, artist_table, album_ids, artist_ids, n, m, o, regularization):
     """loss and per-occurrence gradient rows of train_spotify.py:78-109.
     Returns (loss[1], album_rows[R] (hashed ids), g_album_rows[R, F], g_artist_rows[R, F])."""
+    _sp_occurrences("spotify_fwd_bwd", album_ids, artist_ids, n, m, o)
     lib = _lib.load()
     _req(album_table, torch.float32, "album_table"), _req(artist_table, torch.float32, "artist_table")
     album_ids, artist_ids = _req(album_ids, torch.int32, "album_ids"), _req(artist_ids, torch.int32, "artist_ids")
@@ -811,6 +822,7 @@ def spotify_train_step(album_table, album_trace, album_last, artist_table, artis
     """One whole Spotify train step under lazy optax.sgd(lr, momentum) by ONE library call (esr_spotify_train_step): catch
     the playlist's rows up, loss + gradient rows, one sort, the momentum step on the touched rows of both tables.
     Returns loss[1]."""
+    _sp_occurrences("spotify_train_step", album_ids, artist_ids, n, m, o)
     lib = _lib.load()
     for t, name in ((album_table, "album_table"), (album_trace, "album_trace"), (artist_table, "artist_table"),
                     (artist_trace, "artist_trace")):

@@ -20,8 +20,17 @@ def get_embeddings(album_table, artist_table, album, artist, dtype=np.float64):
     return np.concatenate([a, r], axis=-1)
 
 
-def _affinity(emb, ctx, album, artist, album_ctx, artist_ctx):
-    raw = emb @ ctx.T
+def _dot_rows(emb, ctx):
+    """emb @ ctx.T in which identical rows give identical products, bit for bit: the tie rule compares with ==, and a
+    BLAS may block two equal rows differently (seen at 2F = 66: one of two duplicated context rows off by an ulp, the
+    cotangent of the row max then not split).  Every distinct row is multiplied once."""
+    ue, ie = np.unique(emb, axis=0, return_inverse=True)
+    uc, ic = np.unique(ctx, axis=0, return_inverse=True)
+    return (ue @ uc.T)[np.ravel(ie)][:, np.ravel(ic)]
+
+
+def _affinity(emb, ctx, album, artist, album_ctx, artist_ctx, exact_ties=False):
+    raw = _dot_rows(emb, ctx) if exact_ties else emb @ ctx.T
     aff = raw.max(axis=-1)
     aff = aff + BOOST * np.isin(album, album_ctx) + BOOST * np.isin(artist, artist_ctx)
     return raw, aff
@@ -49,8 +58,8 @@ def loss_and_row_grads(album_table, artist_table, x, regularization, dtype=np.fl
     X = get_embeddings(album_table, artist_table, x["next_album"], x["next_artist"], dtype)
     Y = get_embeddings(album_table, artist_table, x["neg_album"], x["neg_artist"], dtype)
     n, m, o = len(C), len(X), len(Y)
-    P, pos = _affinity(X, C, x["next_album"], x["next_artist"], x["album_context"], x["artist_context"])
-    Q, neg = _affinity(Y, C, x["neg_album"], x["neg_artist"], x["album_context"], x["artist_context"])
+    P, pos = _affinity(X, C, x["next_album"], x["next_artist"], x["album_context"], x["artist_context"], True)
+    Q, neg = _affinity(Y, C, x["neg_album"], x["neg_artist"], x["album_context"], x["artist_context"], True)
     mt_arg = 1.0 + neg.mean() - pos.mean()
     et_arg = 1.0 + neg.max() - pos.min()
     sa_c, sa_x, sa_y = C[::-1] @ C.T, X[::-1] @ X.T, Y[::-1] @ Y.T

@@ -161,8 +161,9 @@ def test_lazy_momentum_equals_flushing_every_step_and_the_dense_oracle(dev):
 
 
 def test_lazy_momentum_long_gaps_take_the_closed_form(dev):
-    """A row that nobody reads for more than 2048 steps is caught up by the closed form of the geometric decay
-    (esr_optim.hip decay_steps): against the fp64 statement of n dense steps."""
+    """A row that nobody reads for more than 64 steps (kLazyExact, esr_common.h) is caught up by the closed form of the
+    geometric decay (decay_steps); shorter gaps are applied one step at a time: against the fp64 statement of n dense
+    steps."""
     from esrecsys_amd import ops
     V, D, lr, mom = 1000, 32, 0.01, 0.98
     g = torch.Generator(device=dev).manual_seed(2)
