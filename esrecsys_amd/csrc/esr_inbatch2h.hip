@@ -25,6 +25,7 @@
 // Pass C always reads the probabilities pass Q stored (inbatch2h_pc8_kernel): B <= 16384; larger batches and bf16
 // tables take the bf16 x 3 path (bf16 tables are one-plane there already).
 #include "esr_inbatch_mfma.h"
+#include "esr_segment.h"
 #include <atomic>
 #include <type_traits>
 #include <time.h>
@@ -2019,14 +2020,6 @@ struct InbatchUpdate {
   float lr, eps;
   bool skip_long;
 };
-
-// in esr_optim.hip
-int inbatch_merge_update(void* const* tables, float* const* accums, const int64_t* row_offsets, int dtype,
-                         const int32_t* sorted_vids, const int32_t* perm, const InbatchMergeArgs& a, float lr, float eps,
-                         hipStream_t st);
-int sparse_adagrad_range(void* const* tables, float* const* accums, const int64_t* row_offsets, int ntables, int dtype,
-                         int D, const int32_t* sorted_vids, const int32_t* perm, int64_t n, float* grad_rows, float lr,
-                         float eps, bool skip_long, hipStream_t st);
 
 // fork / join events of the overlapped form: one pair per host thread and device, made on first use (an event may be
 // recorded again while an earlier wait on it is still queued: a wait binds to the record that preceded it)

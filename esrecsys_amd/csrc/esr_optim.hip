@@ -17,15 +17,27 @@
 #include "esr_common.h"
 #include "esr_adam.h"
 #include "esr_inbatch_mfma.h"
+#include "esr_segment.h"
 
 #include <algorithm>
 
 namespace esr {
 
 enum SegOp { kAdagrad = 0, kSgd = 1, kToDense = 2, kMomentum = 3, kMomentumStep = 4, kMomentumStepLazy = 5, kAdamStepLazy = 6 };
-// what an op needs beyond (lr, eps): nothing, except lazy Adam (its nu / last arrays, betas, bias corrections, step)
+// what an op needs beyond (lr, eps): nothing, except the whole momentum step (its momentum; lazy: the tables' last arrays
+// and the step) and lazy Adam (its nu / last arrays, betas, bias corrections, step)
 struct NoSegExtra {};
+struct MomentumArgs {
+  float momentum;
+};
+struct MomentumLazyArgs {
+  float momentum;
+  int32_t* last[2];
+  int now;
+};
 template <int OP> struct SegExtraT { using type = NoSegExtra; };
+template <> struct SegExtraT<kMomentumStep> { using type = MomentumArgs; };
+template <> struct SegExtraT<kMomentumStepLazy> { using type = MomentumLazyArgs; };
 template <> struct SegExtraT<kAdamStepLazy> { using type = AdamLazyArgs; };
 
 template <int VEC, int NCH>
@@ -80,18 +92,6 @@ __device__ __forceinline__ void param_store(const RowRegs<VEC, NCH>& r, void* ta
   }
 }
 
-// Several tables may be updated by ONE sorted occurrence list: occurrence ids are then "virtual rows"
-// vid = row_offset[t] + id of a concatenation of up to kMaxFusedTables tables with the same D (the two towers of one
-// step), so a step needs one sort and one update instead of one per table -- at the reference's batch sizes the step
-// is bound by the number of dependent launches, not by bytes.  A single table is the n = 1 case.
-constexpr int kMaxFusedTables = 4;
-struct FusedTables {
-  void* table[kMaxFusedTables];
-  float* accum[kMaxFusedTables];
-  int64_t row_offset[kMaxFusedTables + 1];
-  int n;
-};
-
 // one element of optax.sgd(lr, momentum)'s step: trace = g + m * trace ; p = p - lr * trace, four roundings.  Contraction
 // is switched off for these two lines: left to -ffp-contract=fast they became two FMAs, an ulp away from the float32
 // restatement in some elements of every row (tests/test_gpu_segment_update.py holds the step to it bit for bit).
@@ -118,21 +118,22 @@ __device__ __forceinline__ void seg_apply(const FusedTables& ft, int dtype, int3
       base = ft.row_offset[k];
     }
   const int64_t id = (int64_t)vid - base;
-  if constexpr (OP == kAdamStepLazy) {
-    // one WHOLE optax.adam step on a touched row of a lazily stepped table (at most two tables; their nu / last arrays in
-    // `ex`): the row is first brought up from last[row] to step now - 1 (adam_catchup: the zero-gradient steps it missed),
-    // then stepped with its summed gradient -- the run sum kToDense stores, through adam_elem, the dense kernel's
-    // arithmetic -- and marked current with step now
-    const int ti = (1 < ft.n && (int64_t)vid >= ft.row_offset[1]) ? 1 : 0;
-    float* nu = ti ? ex.nu[1] : ex.nu[0];
-    int32_t* last = ti ? ex.last[1] : ex.last[0];
+  const bool second = 1 < ft.n && (int64_t)vid >= ft.row_offset[1];  // the lazy ops (at most two tables): which one's `last`
+  if constexpr (OP == kToDense) {
+    row_store(g, (float*)table + id * D, lig, G, nvec);
+  } else if constexpr (OP == kAdamStepLazy) {
+    // one WHOLE optax.adam step on a touched row of a lazily stepped table: the row is first brought up from last[row] to
+    // step now - 1 (adam_catchup: the zero-gradient steps it missed), then stepped with its summed gradient -- the run sum
+    // kToDense stores, through adam_elem, the dense kernel's arithmetic -- and marked current with step now
+    float* nu = second ? ex.nu[1] : ex.nu[0];
+    int32_t* last = second ? ex.last[1] : ex.last[0];
     RowRegs<VEC, NCH> w, a, b;
     row_load(w, (const float*)table + id * D, lig, G, nvec);
     row_load(a, accum + id * D, lig, G, nvec);
     row_load(b, nu + id * D, lig, G, nvec);
     adam_catchup(w, a, b, last[id], ex.now - 1, ex, lig, G);
     const float omb1 = 1.0f - ex.b1, omb2 = 1.0f - ex.b2;
-    const int64_t V = (ti ? ft.row_offset[2] : ft.row_offset[1]) - (ti ? ft.row_offset[1] : ft.row_offset[0]);
+    const int64_t V = (second ? ft.row_offset[2] : ft.row_offset[1]) - base;
 #pragma unroll
     for (int k = 0; k < NCH; ++k)
 #pragma unroll
@@ -149,81 +150,53 @@ __device__ __forceinline__ void seg_apply(const FusedTables& ft, int dtype, int3
     row_store(a, accum + id * D, lig, G, nvec);
     row_store(b, nu + id * D, lig, G, nvec);
     if (lig == 0) last[id] = ex.now;
-    return;
-  }
-  if (OP == kToDense) {
-    row_store(g, (float*)table + id * D, lig, G, nvec);
-  } else if (OP == kMomentum) {
-    // the gradient half of optax.sgd(lr, momentum): trace += g ; p -= lr * g  (the decay half is dense)
-    RowRegs<VEC, NCH> w, a;
-    param_load(w, table, dtype, id, D, lig, G, nvec);
-    row_load(a, accum + id * D, lig, G, nvec);
-#pragma unroll
-    for (int k = 0; k < NCH; ++k)
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        a.v[k][e] += g.v[k][e];
-        w.v[k][e] -= lr * g.v[k][e];
-      }
-    row_store(a, accum + id * D, lig, G, nvec);
-    param_store(w, table, dtype, id, D, lig, G, nvec);
-  } else if (OP == kMomentumStep) {
-    // one WHOLE step of optax.sgd(lr, momentum) on a touched row (lazy mode: no dense decay pass runs; the row was
-    // brought up to the previous step by momentum_catchup_kernel): trace = g + momentum * trace ; p -= lr * trace, in
-    // optax's own order and with every operation rounded on its own: the float32 oracle's bits (momentum_step_elem;
-    // __fmul_rn / __fadd_rn alone do not say so to hipcc, see esr_common.h).  `eps` carries the momentum.
-    RowRegs<VEC, NCH> w, a;
-    param_load(w, table, dtype, id, D, lig, G, nvec);
-    row_load(a, accum + id * D, lig, G, nvec);
-#pragma unroll
-    for (int k = 0; k < NCH; ++k)
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) momentum_step_elem(w.v[k][e], a.v[k][e], g.v[k][e], lr, eps);
-    row_store(a, accum + id * D, lig, G, nvec);
-    param_store(w, table, dtype, id, D, lig, G, nvec);
-  } else if (OP == kMomentumStepLazy) {
-    // kMomentumStep on a row that is still `now - 1 - last[row]` steps behind (lazy optax.sgd(lr, momentum), see decay_steps
-    // in esr_common.h): the catch-up first -- the very operations momentum_catchup_kernel applies -- then the step, and the
-    // row is marked current.  Saves the catch-up launch in front of the Spotify step (three dependent memory round trips: 12
-    // of its 60 us).  At most two tables; their `last` arrays ride in the unused table slots 2 and 3, `now` in the unused
-    // last row offset (sparse_momentum_step_lazy2 below).
-    int32_t* last = (int32_t*)ft.table[2];
-    if (1 < ft.n && (int64_t)vid >= ft.row_offset[1]) last = (int32_t*)ft.table[3];
-    const int now = (int)ft.row_offset[kMaxFusedTables];
-    const int steps = now - 1 - last[id];
-    RowRegs<VEC, NCH> w, a;
-    param_load(w, table, dtype, id, D, lig, G, nvec);
-    row_load(a, accum + id * D, lig, G, nvec);
-    const DecayCoef dk = decay_coef(steps, eps);
-#pragma unroll
-    for (int k = 0; k < NCH; ++k)
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        if (steps > 0) decay_apply(w.v[k][e], a.v[k][e], dk, lr, eps);
-        momentum_step_elem(w.v[k][e], a.v[k][e], g.v[k][e], lr, eps);
-      }
-    row_store(a, accum + id * D, lig, G, nvec);
-    param_store(w, table, dtype, id, D, lig, G, nvec);
-    if (lig == 0) last[id] = now;
-  } else if (OP == kSgd) {
-    RowRegs<VEC, NCH> w;
-    param_load(w, table, dtype, id, D, lig, G, nvec);
-#pragma unroll
-    for (int k = 0; k < NCH; ++k)
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) w.v[k][e] -= lr * g.v[k][e];
-    param_store(w, table, dtype, id, D, lig, G, nvec);
   } else {
-    // optax.adagrad [upstream]: acc += g^2 ; p -= lr * g * rsqrt(acc + eps)  (0 where acc == 0)
+    // every other op: load the parameter row and its state row (plain SGD has none), one function per element, store both
+    constexpr bool kLazy = OP == kMomentumStepLazy, kState = OP != kSgd;
+    // kMomentumStepLazy is kMomentumStep on a row that is still `now - 1 - last[row]` steps behind (lazy optax.sgd(lr,
+    // momentum), see decay_steps in esr_common.h): the catch-up first -- the very operations momentum_catchup_kernel applies
+    // -- then the step, and the row is marked current.  Saves the catch-up launch in front of the Spotify step (three
+    // dependent memory round trips: 12 of its 60 us).
+    int32_t* last = nullptr;
+    int steps = 0;
+    if constexpr (kLazy) {
+      last = second ? ex.last[1] : ex.last[0];
+      steps = ex.now - 1 - last[id];
+    }
     RowRegs<VEC, NCH> w, a;
     param_load(w, table, dtype, id, D, lig, G, nvec);
-    row_load(a, accum + id * D, lig, G, nvec);
+    if constexpr (kState) row_load(a, accum + id * D, lig, G, nvec);
+    DecayCoef dk{};
+    if constexpr (kLazy) dk = decay_coef(steps, ex.momentum);
 #pragma unroll
     for (int k = 0; k < NCH; ++k)
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) adagrad_elem(w.v[k][e], a.v[k][e], g.v[k][e], lr, eps);
-    row_store(a, accum + id * D, lig, G, nvec);
+      for (int e = 0; e < VEC; ++e) {
+        float& p = w.v[k][e];
+        const float gv = g.v[k][e];
+        if constexpr (OP == kSgd) {
+          p -= lr * gv;
+        } else if constexpr (OP == kMomentum) {
+          // the gradient half of optax.sgd(lr, momentum): trace += g ; p -= lr * g  (the decay half is dense)
+          a.v[k][e] += gv;
+          p -= lr * gv;
+        } else if constexpr (OP == kAdagrad) {
+          // optax.adagrad [upstream]: acc += g^2 ; p -= lr * g * rsqrt(acc + eps)  (0 where acc == 0)
+          adagrad_elem(p, a.v[k][e], gv, lr, eps);
+        } else {
+          // one WHOLE step of optax.sgd(lr, momentum) on a touched row (no dense decay pass runs; the row is at the previous
+          // step: momentum_catchup_kernel, or the catch-up here): trace = g + momentum * trace ; p -= lr * trace, in optax's
+          // own order and with every operation rounded on its own: the float32 oracle's bits (momentum_step_elem;
+          // __fmul_rn / __fadd_rn alone do not say so to hipcc, see esr_common.h)
+          if constexpr (kLazy)
+            if (steps > 0) decay_apply(p, a.v[k][e], dk, lr, ex.momentum);
+          momentum_step_elem(p, a.v[k][e], gv, lr, ex.momentum);
+        }
+      }
+    if constexpr (kState) row_store(a, accum + id * D, lig, G, nvec);
     param_store(w, table, dtype, id, D, lig, G, nvec);
+    if constexpr (kLazy)
+      if (lig == 0) last[id] = ex.now;
   }
 }
 
@@ -235,7 +208,6 @@ __device__ __forceinline__ void seg_apply(const FusedTables& ft, int dtype, int3
 // popular of 10^6 rows draws ~1 200 of 16 384 ids -- leaves one partial sum per chunk in the gradient buffer itself
 // (in the row of the chunk's first occurrence, which nobody else reads) for kernel 2.  One group walking such a run
 // alone took 0.23 - 5.8 ms per step.
-constexpr int kSegChunk = 32;
 template <int VEC, int NCH, int OP>
 __global__ __launch_bounds__(kBlock) void segment_update_kernel(FusedTables ft, int dtype, int D, int G,
                                                                const int32_t* __restrict__ sorted_ids,
@@ -468,20 +440,40 @@ static int launch_segment_tables(const char* who, const FusedTables& ft, int dty
   return check_launch(who);
 }
 
+// The one place a FusedTables is filled, and its structure checked: 1 .. max_tables tables, no null member (states: the
+// tables' state plane, null for an op without one), row offsets that do not fall (strict: that rise -- no empty table),
+// fewer than 2^31 virtual rows.  Errors are reported under the caller's name `who`.
+template <class T>
+static int fused_tables(const char* who, FusedTables& ft, T* const* tables, float* const* states,
+                        const int64_t* row_offsets, int ntables, bool strict = false, int max_tables = kMaxFusedTables) {
+  ESR_REQUIRE(ntables >= 1 && ntables <= max_tables, "%s: ntables=%d not in [1, %d]", who, ntables, max_tables);
+  ESR_REQUIRE(tables && row_offsets, "%s: null pointer", who);
+  ft.n = ntables;
+  for (int i = 0; i < kMaxFusedTables; ++i) {
+    ft.table[i] = i < ntables ? const_cast<void*>((const void*)tables[i]) : nullptr;
+    ft.accum[i] = i < ntables && states ? states[i] : nullptr;
+    ft.row_offset[i] = row_offsets[std::min(i, ntables)];
+    if (i < ntables) {
+      ESR_REQUIRE(tables[i] || states, "%s: null table %d", who, i);
+      ESR_REQUIRE(tables[i] && (!states || states[i]) && row_offsets[i + 1] >= row_offsets[i] + (strict ? 1 : 0),
+                  "%s: bad table %d", who, i);
+    }
+  }
+  ft.row_offset[kMaxFusedTables] = row_offsets[ntables];
+  ESR_REQUIRE(row_offsets[ntables] < ((int64_t)1 << 31), "%s: %lld virtual rows >= 2^31", who, (long long)row_offsets[ntables]);
+  return ESR_OK;
+}
+
+// one table: rows are their own virtual rows (nothing selects by the offsets)
 template <int OP>
 static int launch_segment_update(const char* who, void* table, int dtype, float* accum, int D,
                                  const int32_t* sorted_ids, const int32_t* perm, int64_t n, float* grad_rows,
-                                 float lr, float eps, hipStream_t st) {
+                                 float lr, float eps, hipStream_t st, typename SegExtraT<OP>::type ex = {}) {
+  const int64_t row_offsets[2] = {0, 0};
   FusedTables ft;
-  ft.n = 1;
-  for (int i = 0; i < kMaxFusedTables; ++i) {
-    ft.table[i] = i == 0 ? table : nullptr;
-    ft.accum[i] = i == 0 ? accum : nullptr;
-    ft.row_offset[i] = 0;
-  }
-  ft.row_offset[kMaxFusedTables] = 0;
+  if (const int rc = fused_tables(who, ft, &table, accum ? &accum : nullptr, row_offsets, 1)) return rc;
   // the gradient rows double as scratch for the partial sums of long runs (see segment_update_kernel)
-  return launch_segment_tables<OP>(who, ft, dtype, D, sorted_ids, perm, n, grad_rows, lr, eps, st);
+  return launch_segment_tables<OP>(who, ft, dtype, D, sorted_ids, perm, n, grad_rows, lr, eps, st, false, ex);
 }
 
 // optax.adam, elementwise over the whole table.
@@ -659,21 +651,10 @@ int esr_sparse_momentum_step_multi(float* const* tables, float* const* traces, c
   ESR_REQUIRE(tables && traces && row_offsets && sorted_vids && perm && grad_rows,
               "esr_sparse_momentum_step_multi: null pointer");
   FusedTables ft;
-  ft.n = ntables;
-  for (int i = 0; i < kMaxFusedTables; ++i) {
-    ft.table[i] = i < ntables ? tables[i] : nullptr;
-    ft.accum[i] = i < ntables ? traces[i] : nullptr;
-    ft.row_offset[i] = i <= ntables ? row_offsets[i] : row_offsets[ntables];
-    if (i < ntables) {
-      ESR_REQUIRE(tables[i] && traces[i] && row_offsets[i + 1] >= row_offsets[i],
-                  "esr_sparse_momentum_step_multi: bad table %d", i);
-    }
-  }
-  ft.row_offset[kMaxFusedTables] = row_offsets[ntables];
-  ESR_REQUIRE(row_offsets[ntables] < ((int64_t)1 << 31), "esr_sparse_momentum_step_multi: %lld virtual rows >= 2^31",
-              (long long)row_offsets[ntables]);
+  if (const int rc = fused_tables("esr_sparse_momentum_step_multi", ft, tables, traces, row_offsets, ntables))
+    return rc;
   return launch_segment_tables<kMomentumStep>("esr_sparse_momentum_step_multi", ft, ESR_F32, D, sorted_vids, perm, n,
-                                              grad_rows, lr, momentum, as_stream(stream));
+                                              grad_rows, lr, 0.f, as_stream(stream), false, {momentum});
 }
 
 }  // extern "C"
@@ -693,13 +674,7 @@ int sparse_adagrad_range(void* const* tables, float* const* accums, const int64_
   }
   if (n == 0) return ESR_OK;
   FusedTables ft;
-  ft.n = ntables;
-  for (int i = 0; i < kMaxFusedTables; ++i) {
-    ft.table[i] = i < ntables ? tables[i] : nullptr;
-    ft.accum[i] = i < ntables ? accums[i] : nullptr;
-    ft.row_offset[i] = i <= ntables ? row_offsets[i] : row_offsets[ntables];
-  }
-  ft.row_offset[kMaxFusedTables] = row_offsets[ntables];
+  if (const int rc = fused_tables("sparse_adagrad_range", ft, tables, accums, row_offsets, ntables)) return rc;
   return launch_segment_tables<kAdagrad>("sparse_adagrad_range", ft, dtype, D, sorted_vids, perm, n, grad_rows, lr, eps, st,
                                          skip_long);
 }
@@ -811,13 +786,7 @@ int inbatch_merge_update(void* const* tables, float* const* accums, const int64_
                          const int32_t* sorted_vids, const int32_t* perm, const InbatchMergeArgs& a, float lr, float eps,
                          hipStream_t st) {
   FusedTables ft;
-  ft.n = 2;
-  for (int i = 0; i < kMaxFusedTables; ++i) {
-    ft.table[i] = i < 2 ? tables[i] : nullptr;
-    ft.accum[i] = i < 2 ? accums[i] : nullptr;
-    ft.row_offset[i] = i <= 2 ? row_offsets[i] : row_offsets[2];
-  }
-  ft.row_offset[kMaxFusedTables] = row_offsets[2];
+  if (const int rc = fused_tables("inbatch_merge_update", ft, tables, accums, row_offsets, 2)) return rc;
   const int64_t n = 2 * a.B;
   // two positions per row group on long lists (the second one's id words arrive under the first one's rows): -0.2 .. -1.8 us
   // of 26 at B = 8192 in four same-box pairs; four per group: no better than one.  The slices only divide the work:
@@ -840,17 +809,11 @@ int sparse_momentum_step_lazy2(float* const* tables, float* const* traces, int32
   }
   if (n == 0) return ESR_OK;
   FusedTables ft;
-  ft.n = ntables;
-  for (int i = 0; i < kMaxFusedTables; ++i) {
-    ft.table[i] = i < ntables ? (void*)tables[i] : nullptr;
-    ft.accum[i] = i < ntables ? traces[i] : nullptr;
-    ft.row_offset[i] = i <= ntables ? row_offsets[i] : row_offsets[ntables];
-  }
-  ft.table[2] = lasts[0];
-  ft.table[3] = ntables > 1 ? lasts[1] : nullptr;
-  ft.row_offset[kMaxFusedTables] = now;
+  if (const int rc = fused_tables("sparse_momentum_step_lazy2", ft, tables, traces, row_offsets, ntables, false, 2))
+    return rc;
+  const MomentumLazyArgs ex{momentum, {lasts[0], ntables > 1 ? lasts[1] : nullptr}, now};
   return launch_segment_tables<kMomentumStepLazy>("sparse_momentum_step_lazy2", ft, ESR_F32, D, sorted_vids, perm, n,
-                                                  grad_rows, lr, momentum, st);
+                                                  grad_rows, lr, 0.f, st, false, ex);
 }
 }  // namespace esr
 
@@ -876,7 +839,7 @@ int esr_sparse_momentum_step(float* table, float* trace, int64_t V, int D, const
   if (n == 0) return ESR_OK;
   ESR_REQUIRE(table && trace && sorted_ids && perm && grad_rows, "esr_sparse_momentum_step: null pointer");
   return launch_segment_update<kMomentumStep>("esr_sparse_momentum_step", table, ESR_F32, trace, D, sorted_ids, perm, n,
-                                              grad_rows, lr, momentum, as_stream(stream));
+                                              grad_rows, lr, 0.f, as_stream(stream), {momentum});
 }
 
 int esr_dense_momentum_decay(float* param, float* trace, int64_t count, float lr, float momentum,
@@ -984,14 +947,7 @@ int esr_gather_rows_multi(const void* const* tables, const int64_t* row_offsets,
   if (n == 0) return ESR_OK;
   ESR_REQUIRE(tables && row_offsets && vids && out, "esr_gather_rows_multi: null pointer");
   FusedTables ft;
-  ft.n = ntables;
-  for (int i = 0; i < kMaxFusedTables; ++i) {
-    ft.table[i] = i < ntables ? const_cast<void*>(tables[i]) : nullptr;
-    ft.accum[i] = nullptr;
-    ft.row_offset[i] = i <= ntables ? row_offsets[i] : row_offsets[ntables];
-    if (i < ntables) ESR_REQUIRE(tables[i], "esr_gather_rows_multi: null table %d", i);
-  }
-  ft.row_offset[kMaxFusedTables] = row_offsets[ntables];
+  if (const int rc = fused_tables("esr_gather_rows_multi", ft, tables, nullptr, row_offsets, ntables)) return rc;
   const int nchunk = (int)(row_bytes / 16);
   int G = 1;
   while (G < nchunk && G < kWave) G <<= 1;
@@ -1014,19 +970,7 @@ int esr_sparse_adagrad_scatter_multi(void* const* tables, float* const* accums, 
   ESR_REQUIRE(tables && accums && row_offsets && sorted_vids && perm && grad_rows,
               "esr_sparse_adagrad_scatter_multi: null pointer");
   FusedTables ft;
-  ft.n = ntables;
-  for (int i = 0; i < kMaxFusedTables; ++i) {
-    ft.table[i] = i < ntables ? tables[i] : nullptr;
-    ft.accum[i] = i < ntables ? accums[i] : nullptr;
-    ft.row_offset[i] = i <= ntables ? row_offsets[i] : row_offsets[ntables];
-    if (i < ntables) {
-      ESR_REQUIRE(tables[i] && accums[i] && row_offsets[i + 1] >= row_offsets[i],
-                  "esr_sparse_adagrad_scatter_multi: bad table %d", i);
-    }
-  }
-  ft.row_offset[kMaxFusedTables] = row_offsets[ntables];
-  ESR_REQUIRE(row_offsets[ntables] < ((int64_t)1 << 31), "esr_sparse_adagrad_scatter_multi: %lld virtual rows >= 2^31",
-              (long long)row_offsets[ntables]);
+  if (const int rc = fused_tables("esr_sparse_adagrad_scatter_multi", ft, tables, accums, row_offsets, ntables)) return rc;
   return launch_segment_tables<kAdagrad>("esr_sparse_adagrad_scatter_multi", ft, dtype, D, sorted_vids, perm, n,
                                          grad_rows, lr, eps, as_stream(stream), long_runs == 0);
 }
@@ -1045,26 +989,18 @@ int esr_sparse_adam_step_lazy(float* const* tables, float* const* mus, float* co
   ESR_REQUIRE((((uintptr_t)sorted_vids | (uintptr_t)perm) & 3) == 0 && ((uintptr_t)grad_rows & 15) == 0,
               "esr_sparse_adam_step_lazy: misaligned ids or gradient rows");
   FusedTables ft;
-  ft.n = ntables;
+  if (const int rc = fused_tables("esr_sparse_adam_step_lazy", ft, tables, mus, row_offsets, ntables, true, 2))
+    return rc;
   AdamLazyArgs ax;
   adam_lazy_args(ax, lr, b1, b2, eps, step);
-  for (int i = 0; i < kMaxFusedTables; ++i) {
-    ft.table[i] = i < ntables ? tables[i] : nullptr;
-    ft.accum[i] = i < ntables ? mus[i] : nullptr;
-    ft.row_offset[i] = i <= ntables ? row_offsets[i] : row_offsets[ntables];
-    if (i < ntables) {
-      ESR_REQUIRE(tables[i] && mus[i] && nus[i] && lasts[i] && row_offsets[i + 1] > row_offsets[i],
-                  "esr_sparse_adam_step_lazy: bad table %d", i);
-      ESR_REQUIRE((((uintptr_t)tables[i] | (uintptr_t)mus[i] | (uintptr_t)nus[i]) & 15) == 0 && ((uintptr_t)lasts[i] & 3) == 0,
-                  "esr_sparse_adam_step_lazy: table %d: pointers must be 16-byte aligned", i);
-      ax.nu[i] = nus[i];
-      ax.last[i] = lasts[i];
-    }
+  for (int i = 0; i < ntables; ++i) {
+    ESR_REQUIRE(nus[i] && lasts[i], "esr_sparse_adam_step_lazy: bad table %d", i);
+    ESR_REQUIRE((((uintptr_t)tables[i] | (uintptr_t)mus[i] | (uintptr_t)nus[i]) & 15) == 0 && ((uintptr_t)lasts[i] & 3) == 0,
+                "esr_sparse_adam_step_lazy: table %d: pointers must be 16-byte aligned", i);
+    ax.nu[i] = nus[i];
+    ax.last[i] = lasts[i];
   }
   ESR_REQUIRE(row_offsets[0] == 0, "esr_sparse_adam_step_lazy: row_offsets[0] must be 0");
-  ft.row_offset[kMaxFusedTables] = row_offsets[ntables];
-  ESR_REQUIRE(row_offsets[ntables] < ((int64_t)1 << 31), "esr_sparse_adam_step_lazy: %lld virtual rows >= 2^31",
-              (long long)row_offsets[ntables]);
   if (n == 0) return ESR_OK;
   return launch_segment_tables<kAdamStepLazy>("esr_sparse_adam_step_lazy", ft, ESR_F32, D, sorted_vids, perm, n, grad_rows,
                                               lr, eps, as_stream(stream), false, ax);

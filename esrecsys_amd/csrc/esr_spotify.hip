@@ -13,6 +13,7 @@
 //              affinity terms through d raw and the norm term; writes the per-occurrence gradient rows
 //   finalize   fixed-order fp64 sum of the loss partials
 #include "esr_common.h"
+#include "esr_segment.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -634,11 +635,6 @@ static int sp_check(const char* who, int n, int m, int o, int F, int64_t A, int6
   }
   return ESR_OK;
 }
-
-// in esr_optim.hip
-int sparse_momentum_step_lazy2(float* const* tables, float* const* traces, int32_t* const* lasts, const int64_t* row_offsets,
-                               int ntables, int D, const int32_t* sorted_vids, const int32_t* perm, int64_t n, float* grad_rows,
-                               float lr, float momentum, int now, hipStream_t st);
 
 }  // namespace esr
 

@@ -18,7 +18,7 @@
 
 namespace esr {
 
-constexpr int kStepChunk = 32;  // == kSegChunk of esr_optim.hip: same cut points, same association of every sum
+constexpr int kStepChunk = 32;  // == kSegChunk of esr_segment.h: same cut points, same association of every sum
 constexpr uint32_t kLocBit = 0x80000000u;   // row code: the row's current value is in the second buffer
 constexpr uint32_t kSideBit = 0x40000000u;  // (GloVe plan records) the occurrence is the pair's second token
 constexpr uint32_t kIdMask = 0x3FFFFFFFu;   // row code: the (virtual) row id, < 2^30 - 1

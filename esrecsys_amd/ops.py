@@ -590,7 +590,6 @@ def segment_sort(ids, V, out=None):
 def segment_sort_multi(id_tensors, offsets, V):
     """Stable sort of the virtual list [ids_0 + offsets[0] ; ids_1 + offsets[1] ; ...] without materialising it.
     Returns (sorted virtual ids, perm)."""
-    import ctypes
     lib = _lib.load()
     k = len(id_tensors)
     for t in id_tensors:
@@ -625,7 +624,6 @@ def sparse_adagrad(table, accum, sorted_ids, perm, grad_rows, lr, eps=1e-7):
 
 def concat_offset_ids(id_tensors, offsets):
     """[ids_0 + offsets[0] ; ids_1 + offsets[1] ; ...] as one int32 tensor (virtual rows of concatenated tables)."""
-    import ctypes
     lib = _lib.load()
     n = len(id_tensors)
     for t in id_tensors:
@@ -639,23 +637,49 @@ def concat_offset_ids(id_tensors, offsets):
     return out
 
 
-def gather_rows_multi(tables, row_offsets, vids, out=None):
-    """out[i] = tables[t][vids[i] - row_offsets[t]] for virtual rows of several same-width tables."""
-    import ctypes
-    lib = _lib.load()
-    n_t = len(tables)
+def i64_array(values):
+    """host int64 array for the count / offset arguments of the multi-table and sharded calls"""
+    return (ctypes.c_int64 * len(values))(*[int(v) for v in values])
+
+
+def ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _fused_tables(tables, row_offsets, table_dtype=None, **states):
+    """What the calls on several same-width tables addressed by virtual rows share.  states = one list of fp32 tensors per
+    state plane, by name (accumulator=[...]): one per table, of its size.  The tables must share a dtype (table_dtype, if
+    given) and D.  Returns (dtype code, D, table pointers, one pointer array per state plane ..., row offsets)."""
+    if table_dtype is not None:
+        for t in tables:
+            _req(t, table_dtype, "table")
     dts = {_table_dtype(t, "table") for t in tables}
     if len(dts) != 1:
         raise TypeError("fused tables must share a dtype")
-    D = tables[0].shape[1] if tables[0].dim() > 1 else 1
+    if len(row_offsets) != len(tables) + 1:
+        raise ValueError("row_offsets must hold one entry more than there are tables")
+    width = lambda t: t.shape[1] if t.dim() > 1 else 1  # noqa: E731
+    D = width(tables[0])
+    what = " and have matching %ss" % "s / ".join(states) if states else ""
+    if any(width(t) != D for t in tables) or any(len(plane) != len(tables) for plane in states.values()):
+        raise ValueError("fused tables must share D" + what)
+    for name, plane in states.items():
+        for t, a in zip(tables, plane):
+            _req(a, torch.float32, name)
+            if a.numel() != t.numel():
+                raise ValueError("fused tables must share D" + what)
+    return (dts.pop(), D, ptr_array(tables), *map(ptr_array, states.values()), i64_array(row_offsets))
+
+
+def gather_rows_multi(tables, row_offsets, vids, out=None):
+    """out[i] = tables[t][vids[i] - row_offsets[t]] for virtual rows of several same-width tables."""
+    lib = _lib.load()
+    dt, D, tp, ro = _fused_tables(tables, row_offsets)
     vids = _req(vids, torch.int32, "vids")
     n = vids.numel()
     if out is None:
         out = torch.empty((n, D), dtype=tables[0].dtype, device=vids.device)
-    tp = (ctypes.c_void_p * n_t)(*[t.data_ptr() for t in tables])
-    ro = (ctypes.c_int64 * (n_t + 1))(*[int(o) for o in row_offsets])
-    check(lib.esr_gather_rows_multi(tp, ro, n_t, dts.pop(), D, _p(vids), n, _p(out), _stream()),
-          "esr_gather_rows_multi")
+    check(lib.esr_gather_rows_multi(tp, ro, len(tables), dt, D, _p(vids), n, _p(out), _stream()), "esr_gather_rows_multi")
     return out
 
 
@@ -663,23 +687,10 @@ def sparse_adagrad_multi(tables, accums, row_offsets, sorted_vids, perm, grad_ro
     """One launch of row-sparse Adagrad over several same-width tables addressed by virtual rows.  long_runs = 0: the
     caller knows (long_run_hint with chunk 32) that no id has a run the head chunk cannot hold -- the long-run launch
     is skipped."""
-    import ctypes
     lib = _lib.load()
-    n_t = len(tables)
-    dts = {_table_dtype(t, "table") for t in tables}
-    if len(dts) != 1:
-        raise TypeError("fused tables must share a dtype")
-    D = tables[0].shape[1] if tables[0].dim() > 1 else 1
-    for t, a in zip(tables, accums):
-        _req(a, torch.float32, "accum")
-        if (t.shape[1] if t.dim() > 1 else 1) != D or a.numel() != t.numel():
-            raise ValueError("fused tables must share D and have matching accumulators")
+    dt, D, tp, ap, ro = _fused_tables(tables, row_offsets, accumulator=accums)
     _req(grad_rows, torch.float32, "grad_rows")
-    n = sorted_vids.numel()
-    tp = (ctypes.c_void_p * n_t)(*[t.data_ptr() for t in tables])
-    ap = (ctypes.c_void_p * n_t)(*[a.data_ptr() for a in accums])
-    ro = (ctypes.c_int64 * (n_t + 1))(*[int(o) for o in row_offsets])
-    check(lib.esr_sparse_adagrad_scatter_multi(tp, ap, ro, n_t, dts.pop(), D, _p(sorted_vids), _p(perm), n,
+    check(lib.esr_sparse_adagrad_scatter_multi(tp, ap, ro, len(tables), dt, D, _p(sorted_vids), _p(perm), sorted_vids.numel(),
                                                _p(grad_rows), float(lr), float(eps), int(long_runs), _stream()),
           "esr_sparse_adagrad_scatter_multi")
 
@@ -735,19 +746,11 @@ def sparse_momentum_step(table, trace, sorted_ids, perm, grad_rows, lr, momentum
 def sparse_momentum_step_multi(tables, traces, row_offsets, sorted_vids, perm, grad_rows, lr, momentum):
     """sparse_momentum_step over several same-width f32 tables addressed by virtual rows (one sort, one launch pair)."""
     lib = _lib.load()
-    n_t = len(tables)
-    D = tables[0].shape[1] if tables[0].dim() > 1 else 1
-    for t, a in zip(tables, traces):
-        _req(t, torch.float32, "table"), _req(a, torch.float32, "trace")
-        if (t.shape[1] if t.dim() > 1 else 1) != D or a.numel() != t.numel():
-            raise ValueError("fused tables must share D and have matching traces")
+    _, D, tp, ap, ro = _fused_tables(tables, row_offsets, torch.float32, trace=traces)
     _req(grad_rows, torch.float32, "grad_rows")
-    n = sorted_vids.numel()
-    tp = (ctypes.c_void_p * n_t)(*[t.data_ptr() for t in tables])
-    ap = (ctypes.c_void_p * n_t)(*[a.data_ptr() for a in traces])
-    ro = (ctypes.c_int64 * (n_t + 1))(*[int(o) for o in row_offsets])
-    check(lib.esr_sparse_momentum_step_multi(tp, ap, ro, n_t, D, _p(sorted_vids), _p(perm), n, _p(grad_rows), float(lr),
-                                             float(momentum), _stream()), "esr_sparse_momentum_step_multi")
+    check(lib.esr_sparse_momentum_step_multi(tp, ap, ro, len(tables), D, _p(sorted_vids), _p(perm), sorted_vids.numel(),
+                                             _p(grad_rows), float(lr), float(momentum), _stream()),
+          "esr_sparse_momentum_step_multi")
 
 
 def momentum_flush(table, trace, last, step, lr, momentum):
@@ -913,6 +916,17 @@ def dense_adam(param, mu, nu, grad, lr, step, b1=0.9, b2=0.999, eps=1e-8):
 ADAM_EXACT_STEPS = 8  # include/esr_hip.h ESR_ADAM_EXACT_STEPS: lazy Adam replays gaps up to this long bit-exactly
 
 
+def _adam_tables(who, tables, mus, nus, lasts, row_offsets):
+    """One or two lazily stepped Adam tables of one launch: (D, pointers of tables, mus, nus, lasts, row offsets)"""
+    nt = len(tables)
+    if not 1 <= nt <= 2 or not (len(mus) == len(nus) == len(lasts) == nt) or len(row_offsets) != nt + 1:
+        raise ValueError("%s takes one or two tables" % who)
+    for t, m, v, l in zip(tables, mus, nus, lasts):
+        _adam_table(t, m, v, l, who)
+    _, D, tp, mp, vp, ro = _fused_tables(tables, row_offsets, torch.float32, mu=mus, nu=nus)
+    return D, tp, mp, vp, ptr_array(lasts), ro
+
+
 def _adam_table(table, mu, nu, last, what):
     _req(table, torch.float32, what + " table")
     _req(mu, torch.float32, what + " mu")
@@ -944,19 +958,10 @@ def sparse_adam_step_lazy(tables, mus, nus, lasts, row_offsets, sorted_vids, per
     """Lazy optax.adam step `step` on the touched rows of one or two same-width tables (virtual rows row_offsets[t] + id,
     sorted by segment_sort / segment_sort_multi).  Rows are caught up from their `last` first and marked `step`."""
     lib = _lib.load()
-    nt = len(tables)
-    if not 1 <= nt <= 2 or not (len(mus) == len(nus) == len(lasts) == nt) or len(row_offsets) != nt + 1:
-        raise ValueError("sparse_adam_step_lazy takes one or two tables")
-    D = tables[0].shape[1]
-    for t, m, v, l in zip(tables, mus, nus, lasts):
-        _adam_table(t, m, v, l, "sparse_adam_step_lazy")
-        if t.shape[1] != D:
-            raise ValueError("sparse_adam_step_lazy: the tables of one launch must share D")
+    D, tp, mp, vp, lp, ro = _adam_tables("sparse_adam_step_lazy", tables, mus, nus, lasts, row_offsets)
     _req(grad_rows, torch.float32, "grad_rows")
-    ptrs = lambda ts: (ctypes.c_void_p * nt)(*[t.data_ptr() for t in ts])  # noqa: E731
-    offs = (ctypes.c_int64 * (nt + 1))(*[int(o) for o in row_offsets])
-    check(lib.esr_sparse_adam_step_lazy(ptrs(tables), ptrs(mus), ptrs(nus), ptrs(lasts), offs, nt, D, _p(sorted_vids), _p(perm), sorted_vids.numel(), _p(grad_rows), float(lr),
-                                        float(b1), float(b2), float(eps), int(step), _stream()),
+    check(lib.esr_sparse_adam_step_lazy(tp, mp, vp, lp, ro, len(tables), D, _p(sorted_vids), _p(perm), sorted_vids.numel(),
+                                        _p(grad_rows), float(lr), float(b1), float(b2), float(eps), int(step), _stream()),
           "esr_sparse_adam_step_lazy")
 
 
@@ -967,14 +972,7 @@ def adam_catchup_gather(tables, mus, nus, lasts, row_offsets, sorted_rows, perm,
     out[perm[j]] = the caught-up row sorted_rows[j] -- what adam_catchup_rows followed by gather_rows_multi gives, bit for
     bit, in one pass.  serve=False: catch up only (returns None)."""
     lib = _lib.load()
-    nt = len(tables)
-    if not 1 <= nt <= 2 or not (len(mus) == len(nus) == len(lasts) == nt) or len(row_offsets) != nt + 1:
-        raise ValueError("adam_catchup_gather takes one or two tables")
-    D = tables[0].shape[1]
-    for t, m, v, l in zip(tables, mus, nus, lasts):
-        _adam_table(t, m, v, l, "adam_catchup_gather")
-        if t.shape[1] != D:
-            raise ValueError("adam_catchup_gather: the tables of one launch must share D")
+    D, tp, mp, vp, lp, ro = _adam_tables("adam_catchup_gather", tables, mus, nus, lasts, row_offsets)
     _req(sorted_rows, torch.int32, "sorted_rows")
     n = sorted_rows.numel()
     if serve:
@@ -986,9 +984,7 @@ def adam_catchup_gather(tables, mus, nus, lasts, row_offsets, sorted_rows, perm,
         _req(out, torch.float32, "out")
         if tuple(out.shape) != (n, D):
             raise ValueError("adam_catchup_gather: out must be [%d, %d], got %s" % (n, D, tuple(out.shape)))
-    ptrs = lambda ts: (ctypes.c_void_p * nt)(*[t.data_ptr() for t in ts])  # noqa: E731
-    offs = (ctypes.c_int64 * (nt + 1))(*[int(o) for o in row_offsets])
-    check(lib.esr_adam_catchup_gather(ptrs(tables), ptrs(mus), ptrs(nus), ptrs(lasts), offs, nt, D, _p(sorted_rows),
+    check(lib.esr_adam_catchup_gather(tp, mp, vp, lp, ro, len(tables), D, _p(sorted_rows),
                                       _p(perm) if serve else None, n, _p(out) if serve else None, int(step), float(lr),
                                       float(b1), float(b2), float(eps), _stream()), "esr_adam_catchup_gather")
     return out if serve else None
@@ -1303,7 +1299,6 @@ def bucket_ids_by_owner_batched(id_lists, world, offsets):
     """bucket_ids_by_owner for the lists of several coming batches in one launch pair (esr_bucket_ids_by_owner_batched).
     id_lists: per batch, the int32 segments of its virtual list [ids_k + offsets[k]] (same lengths in every batch).
     Returns (local_rows [L, n], perm [L, n], counts [L, world] int64, inverse [L, n])."""
-    import ctypes
     lib = _lib.load()
     nb, nseg = len(id_lists), len(id_lists[0])
     dev = id_lists[0][0].device
@@ -1332,7 +1327,6 @@ def segment_sort_batched(id_lists, offsets, num_rows, out=None):
     id_lists: per batch, the int32 segments of its virtual list [ids_k + offsets[k]] (same lengths in every batch).
     Returns (sorted_ids, perm), each [len(id_lists), n]: row b is what segment_sort / the multi-segment sort gives for
     batch b alone.  out = (sorted_ids, perm, workspace) to reuse buffers."""
-    import ctypes
     lib = _lib.load()
     nb, nseg = len(id_lists), len(id_lists[0])
     dev = id_lists[0][0].device
@@ -1361,7 +1355,6 @@ def bucket_ids_by_owner(ids, world, want_inverse=False, offsets=None, counts_out
     want_inverse, also inverse with inverse[perm[k]] = k.  `ids` may be a list of int32 tensors with `offsets`: the
     virtual list [ids_0 + offsets[0] ; ids_1 + offsets[1] ; ...] is bucketed in place (no concatenated copy).
     `counts_out` (contiguous int64 [world] on the device) receives the counts instead of a fresh tensor."""
-    import ctypes
     lib = _lib.load()
     segs = list(ids) if isinstance(ids, (list, tuple)) else None
     if segs is None:
@@ -1398,17 +1391,6 @@ def bucket_ids_by_owner(ids, world, want_inverse=False, offsets=None, counts_out
 
 
 # ---- a row-sharded step's exchange halves, one library call each (esr_shard_step.hip) ----------------------------------
-def i64_array(values):
-    """host int64 array for the count / offset arguments of the sharded calls (made once per plan / group, reused)."""
-    import ctypes
-    return (ctypes.c_int64 * len(values))(*[int(v) for v in values])
-
-
-def ptr_array(tensors):
-    import ctypes
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
 def sharded_lookup(comm, world, tables_c, loff_c, ntables, dtype, D, asked_rows, asked_c, ask_c, served, back):
     """esr_sharded_lookup: gather the rows asked of this rank + the rows exchange, on the current stream.  `comm`: the
     DirectExchange communicator (ctypes.c_void_p) or None at world 1; served may be None at world 1."""
@@ -1434,7 +1416,6 @@ def sharded_update(comm, world, tables_c, accums_c, loff_c, ntables, dtype, D, g
 
 def shard_group_struct(comm, world, tables_c, accums_c, loff_c, ntables, dtype, D, grad_dtype):
     """esr_shard_group_t over the host arrays of ptr_array / i64_array (the caller keeps them -- and the tensors -- alive)."""
-    import ctypes
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
     comm = getattr(comm, "value", comm)
     return _lib.ShardGroupStruct(comm, world, cast(tables_c), cast(accums_c), cast(loff_c), ntables, dtype, D, grad_dtype)
@@ -1442,7 +1423,6 @@ def shard_group_struct(comm, world, tables_c, accums_c, loff_c, ntables, dtype, 
 
 def routing_plan_struct(asked_rows, asked_c, ask_c, index, sorted_uidx, occ_perm, owner_sorted, owner_perm, long_runs=-1):
     """esr_routing_plan_t of one batch (device tensors + the host count arrays; the caller keeps them alive)."""
-    import ctypes
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
     q = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
     return _lib.RoutingPlanStruct(q(asked_rows), cast(asked_c), cast(ask_c), q(index), q(sorted_uidx), q(occ_perm),
@@ -1454,7 +1434,6 @@ def step_overlap_struct(backs, ready, stale, next_plan_s, next_backs, next_serve
     call fetched them (None: look up in line) with `ready`, that call's next_ready; stale = (rows, asked host array, pos, ask
     host array) of esrecsys_amd.sharded.StaleRows; next_*: the coming batch's plan struct and its buffers per group (None:
     last step); side_stream: a torch.cuda.Stream.  The caller keeps every tensor / array alive until the NEXT call."""
-    import ctypes
     ov = _lib.StepOverlapStruct()
     q = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
     for i, b in enumerate(backs or ()):
@@ -1484,7 +1463,6 @@ def overlap_release(ready):
 def sharded_triplet_step(group_s, plan_s, B, regularization, batch_size, lr, eps, device, overlap=None):
     """esr_sharded_triplet_step: lookup -> triplet loss on the rows where they landed -> update, one library call.
     Returns loss [1] (this rank's share).  overlap: a step_overlap_struct (esr_sharded_triplet_step_overlapped)."""
-    import ctypes
     lib = _lib.load()
     nb = int(lib.esr_sharded_triplet_step_workspace_bytes(ctypes.byref(group_s), ctypes.byref(plan_s), B))
     ov = ctypes.byref(overlap) if overlap is not None else None
@@ -1501,7 +1479,6 @@ def sharded_triplet_step(group_s, plan_s, B, regularization, batch_size, lr, eps
 def sharded_glove_step(emb_s, bias_s, plan_s, target, B, mode, lr, eps, overlap=None):
     """esr_sharded_glove_step: both lookups -> GloVe loss -> both updates, one library call.  Returns loss [1].
     overlap: a step_overlap_struct (esr_sharded_glove_step_overlapped)."""
-    import ctypes
     lib = _lib.load()
     _req(target, torch.float32, "target")
     nb = int(lib.esr_sharded_glove_step_workspace_bytes(ctypes.byref(emb_s), ctypes.byref(bias_s), ctypes.byref(plan_s), B))

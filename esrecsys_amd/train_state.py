@@ -9,6 +9,8 @@ updated IN PLACE by HIP kernels; ``apply_gradients`` returns a new TrainState ob
 buffers (functional call shape, resident memory).  Gradients of embedding tables are row-sparse
 (``RowGrads``) unless the optimizer asks for the reference's dense V x D layout.
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -16,9 +18,6 @@ from . import ops
 
 
 _side_streams = {}
-
-
-import contextlib
 
 
 @contextlib.contextmanager
@@ -179,6 +178,38 @@ def tree_map(fn, tree):
     return fn(tree)
 
 
+def _grad_leaves(params, grads, who, max_fused=None):
+    """The gradients of one step, each consumed and sorted, ready for ONE optimizer launch: yields (paths, g, sorted ids,
+    perm) -- a FusedScatter g once, for the tables `paths` it spans (one sort, one launch pair for all its members), a
+    plain RowGrads leaf g for its own path.  max_fused = the most tables the caller's kernel fuses (a larger scatter is
+    stepped leaf by leaf); 0: the caller never fuses."""
+    done = set()
+    for path, _ in tree_leaves_with_path(params):
+        g = tree_get(grads, path)
+        if g is None:
+            continue
+        if not isinstance(g, RowGrads):
+            raise TypeError("%s needs RowGrads leaves (got %s at %s)" % (who, type(g).__name__, path))
+        f = g.fused
+        if f is not None and path in f.paths and (max_fused is None or len(f.paths) <= max_fused):
+            if id(f) not in done:
+                done.add(id(f))
+                f.consume()
+                yield (f.paths, f) + tuple(f.index.sorted())
+            continue
+        _consume(g, "RowGrads")
+        yield ([path], g) + tuple(g.index.sorted())
+
+
+def _lazy_eligible(params, grads, need_f32):
+    """May this step take an optimizer's lazy form?  Every table a [V, D] tensor on the GPU (fp32 where the kernels step
+    nothing else), every gradient row-sparse or absent."""
+    return all(p.dim() == 2 and p.is_cuda and (p.dtype == torch.float32 or not need_f32)
+               for _, p in tree_leaves_with_path(params)) and \
+        all(isinstance(tree_get(grads, path), RowGrads) or tree_get(grads, path) is None
+            for path, _ in tree_leaves_with_path(params))
+
+
 class GradientTransformation:
     """Minimal optax-shaped object: ``init(params) -> opt_state`` and an in-place ``apply``."""
     wants_dense = False
@@ -235,11 +266,6 @@ class _Adam(GradientTransformation):
                 for path, p in tree_leaves_with_path(params)}}
         return lz
 
-    def _lazy_ok(self, params, grads):
-        return all(p.dim() == 2 and p.is_cuda and p.dtype == torch.float32 for _, p in tree_leaves_with_path(params)) and \
-            all(isinstance(tree_get(grads, path), RowGrads) or tree_get(grads, path) is None
-                for path, _ in tree_leaves_with_path(params))
-
     def prepare(self, params, opt_state, lookups):
         """Start of a lazy step: lookups = [(path, int32 ids, modulus)] -- the rows the step is about to read (row =
         id % modulus when modulus > 0).  They are brought up to the previous step (two tables per launch)."""
@@ -270,28 +296,13 @@ class _Adam(GradientTransformation):
     def _apply_lazy(self, params, grads, opt_state):
         lz = self._lazy_state(params, opt_state)
         count = int(opt_state["count"]) + 1
-        done = set()
-        for path, p in tree_leaves_with_path(params):
-            g = tree_get(grads, path)
-            if g is None:
-                continue
-            f = g.fused
-            if f is not None and tuple(path) in f.paths and len(f.paths) <= 2:
-                if id(f) in done:
-                    continue
-                done.add(id(f))  # the members of a fused scatter: one sort, one launch pair
-                f.consume()
-                sorted_vids, perm = f.index.sorted()
-                ops.sparse_adam_step_lazy([tree_get(params, q) for q in f.paths], [tree_get(opt_state["mu"], q) for q in f.paths],
-                                          [tree_get(opt_state["nu"], q) for q in f.paths], [lz["last"][q] for q in f.paths],
-                                          f.row_offsets, sorted_vids, perm, f.rows, self.lr, count, **self._hp())
-                continue
-            _consume(g, "RowGrads")
-            sorted_ids, perm = g.index.sorted()
-            D = p.shape[1]
-            ops.sparse_adam_step_lazy([p], [tree_get(opt_state["mu"], path)], [tree_get(opt_state["nu"], path)],
-                                      [lz["last"][tuple(path)]], [0, p.shape[0]], sorted_ids, perm, g.rows.reshape(-1, D),
-                                      self.lr, count, **self._hp())
+        for paths, g, sorted_vids, perm in _grad_leaves(params, grads, "adam(lazy=True)", max_fused=2):
+            tables = [tree_get(params, q) for q in paths]
+            V, D = tables[0].shape
+            ops.sparse_adam_step_lazy(tables, [tree_get(opt_state["mu"], q) for q in paths],
+                                      [tree_get(opt_state["nu"], q) for q in paths], [lz["last"][q] for q in paths],
+                                      g.row_offsets if isinstance(g, FusedScatter) else [0, V], sorted_vids, perm,
+                                      g.rows.reshape(-1, D), self.lr, count, **self._hp())
         lz["dirty"] = True
         return {"count": count, "mu": opt_state["mu"], "nu": opt_state["nu"], "_lazy": lz}
 
@@ -305,7 +316,7 @@ class _Adam(GradientTransformation):
 
     def apply(self, params, grads, opt_state, step):
         if self.lazy:
-            if self._lazy_ok(params, grads):
+            if _lazy_eligible(params, grads, need_f32=True):
                 return self._apply_lazy(params, grads, opt_state)
             self.flush(params, opt_state)  # a dense step on lazily stepped tables: bring every row up to date first
         count = opt_state["count"] + 1
@@ -342,29 +353,14 @@ class _SparseAdagrad(GradientTransformation):
         return {"sum_of_squares": tree["0"]["sum_of_squares"]}
 
     def apply(self, params, grads, opt_state, step):
-        done = set()
-        for path, p in tree_leaves_with_path(params):
-            g = tree_get(grads, path)
-            if g is None:
-                continue
-            if not isinstance(g, RowGrads):
-                raise TypeError("sparse_adagrad needs RowGrads leaves (got %s at %s)" % (type(g).__name__, path))
-            f = g.fused
-            if f is not None and tuple(path) in f.paths:
-                if id(f) in done:
-                    continue
-                done.add(id(f))  # all members of the fused scatter in one sort + one launch
-                f.consume()
-                sorted_vids, perm = f.index.sorted()
-                ops.sparse_adagrad_multi([tree_get(params, q) for q in f.paths],
-                                         [tree_get(opt_state["sum_of_squares"], q) for q in f.paths],
-                                         f.row_offsets, sorted_vids, perm, f.rows, self.lr, self.eps,
-                                         long_runs=f.index.long_runs)
-                continue
-            _consume(g, "RowGrads")
-            sorted_ids, perm = g.index.sorted()
-            ops.sparse_adagrad(p, tree_get(opt_state["sum_of_squares"], path), sorted_ids, perm, g.rows, self.lr,
-                               self.eps)
+        for paths, g, sorted_ids, perm in _grad_leaves(params, grads, "sparse_adagrad"):
+            tables = [tree_get(params, q) for q in paths]
+            accums = [tree_get(opt_state["sum_of_squares"], q) for q in paths]
+            if isinstance(g, FusedScatter):
+                ops.sparse_adagrad_multi(tables, accums, g.row_offsets, sorted_ids, perm, g.rows, self.lr, self.eps,
+                                         long_runs=g.index.long_runs)
+            else:
+                ops.sparse_adagrad(tables[0], accums[0], sorted_ids, perm, g.rows, self.lr, self.eps)
         return opt_state
 
 
@@ -385,13 +381,8 @@ class _SparseSgd(GradientTransformation):
         return {}
 
     def apply(self, params, grads, opt_state, step):
-        for path, p in tree_leaves_with_path(params):
-            g = tree_get(grads, path)
-            if g is None:
-                continue
-            _consume(g, "RowGrads")
-            sorted_ids, perm = g.index.sorted()
-            ops.sparse_sgd(p, sorted_ids, perm, g.rows, self.lr)
+        for (path,), g, sorted_ids, perm in _grad_leaves(params, grads, "sgd", max_fused=0):
+            ops.sparse_sgd(tree_get(params, path), sorted_ids, perm, g.rows, self.lr)
         return opt_state
 
 
@@ -458,9 +449,7 @@ class _SgdMomentum(GradientTransformation):
         lz["dirty"] = False
 
     def apply(self, params, grads, opt_state, step):
-        lazy = self.lazy and all(isinstance(tree_get(grads, path), RowGrads) or tree_get(grads, path) is None
-                                 for path, p in tree_leaves_with_path(params)) and \
-            all(p.dim() == 2 and p.is_cuda for _, p in tree_leaves_with_path(params))
+        lazy = self.lazy and _lazy_eligible(params, grads, need_f32=False)
         if self.lazy and not lazy:
             self.flush(params, opt_state)  # a dense step on lazily updated tables: bring them up to date first
         if lazy:
@@ -469,27 +458,15 @@ class _SgdMomentum(GradientTransformation):
                 self.prepare(params, opt_state, [(path, tree_get(grads, path).index.ids, 0)
                                                  for path, _ in tree_leaves_with_path(params)
                                                  if tree_get(grads, path) is not None])
-            for path, p in tree_leaves_with_path(params):
-                g = tree_get(grads, path)
-                if g is None:
-                    continue
-                _consume(g, "RowGrads")
-                sorted_ids, perm = g.index.sorted()
-                ops.sparse_momentum_step(p, tree_get(opt_state["trace"], path), sorted_ids, perm, g.rows, self.lr,
-                                         self.momentum)
+            for (path,), g, sorted_ids, perm in _grad_leaves(params, grads, "sgd(momentum)", max_fused=0):
+                ops.sparse_momentum_step(tree_get(params, path), tree_get(opt_state["trace"], path), sorted_ids, perm, g.rows,
+                                         self.lr, self.momentum)
             lz["prepared"], lz["dirty"] = False, True
             return opt_state
-        for path, p in tree_leaves_with_path(params):
-            tr = tree_get(opt_state["trace"], path)
-            ops.dense_momentum_decay(p, tr, self.lr, self.momentum)
-            g = tree_get(grads, path)
-            if g is None:
-                continue
-            if not isinstance(g, RowGrads):
-                raise TypeError("sgd(momentum) needs RowGrads leaves (got %s at %s)" % (type(g).__name__, path))
-            _consume(g, "RowGrads")
-            sorted_ids, perm = g.index.sorted()
-            ops.sparse_momentum(p, tr, sorted_ids, perm, g.rows, self.lr)
+        for path, p in tree_leaves_with_path(params):  # the decay half: every element of every table
+            ops.dense_momentum_decay(p, tree_get(opt_state["trace"], path), self.lr, self.momentum)
+        for (path,), g, sorted_ids, perm in _grad_leaves(params, grads, "sgd(momentum)", max_fused=0):
+            ops.sparse_momentum(tree_get(params, path), tree_get(opt_state["trace"], path), sorted_ids, perm, g.rows, self.lr)
         if isinstance(opt_state.get("_lazy"), dict):  # (a dense step after lazy ones: everybody is up to date with it)
             opt_state["_lazy"]["step"] += 1
             for last in opt_state["_lazy"]["last"].values():
@@ -509,10 +486,6 @@ def sparse_adagrad(learning_rate, initial_accumulator_value=0.1, eps=1e-7):
 def sgd(learning_rate, momentum=None, lazy=True):
     if momentum is not None:
         return _SgdMomentum(learning_rate, momentum, lazy=lazy)
-    return _sgd_plain(learning_rate)
-
-
-def _sgd_plain(learning_rate):
     return _SparseSgd(learning_rate)
 
 

@@ -37,7 +37,7 @@ def test_geometry_table_of_the_segment_update_tests():
 def test_geometry_constants_are_the_sources():
     """the constants geom() and the chunk plan are built on, read from the headers: a change there makes this table stale"""
     common = open(os.path.join(CSRC, "esr_common.h")).read()
-    optim = open(os.path.join(CSRC, "esr_optim.hip")).read()
+    segment = open(os.path.join(CSRC, "esr_segment.h")).read()
 
     def const(text, name):
         m = re.search(r"constexpr\s+int\s+%s\s*=\s*([^;]+);" % name, text)
@@ -45,7 +45,7 @@ def test_geometry_constants_are_the_sources():
         return int(eval(m.group(1), {"__builtins__": {}}))  # "256 * 8"
     assert const(common, "kBlock") == BLOCK and const(common, "kWave") == WAVE
     assert const(common, "kMaxChunksPerLane") == MAX_NCH and const(common, "kMaxGrid") == MAX_GRID
-    assert const(optim, "kSegChunk") == CHUNK and const(optim, "kMaxFusedTables") == 4
+    assert const(segment, "kSegChunk") == CHUNK and const(segment, "kMaxFusedTables") == 4
     # row_geom's rule and the dispatch's cut points, as text
     assert "g.vec = (D % 4 == 0) ? 4 : 1;" in common and "while (G < g.nvec && G < kWave) G <<= 1;" in common
     assert re.search(r"\(geom\)\.nch <= 1\).*NCH = 1;.*\n.*\(geom\)\.nch <= 2\).*NCH = 2;.*\n.*NCH = 4;", common)
