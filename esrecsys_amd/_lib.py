@@ -204,6 +204,12 @@ SIGNATURES = {
                                                     c_vp]),
     "esr_sharded_glove_step_overlapped": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_f32, c_f32, c_vp, c_vp,
                                                   c_size, c_vp]),
+    "esr_cooccur_table_bytes": (c_size, [c_i64]),
+    "esr_cooccur_table_init": (c_int, [c_vp, c_i64, c_vp]),
+    "esr_cooccur_accumulate": (c_int, [c_i32p, c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp]),
+    "esr_cooccur_rehash": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "esr_cooccur_finalize_workspace_bytes": (c_size, [c_i64]),
+    "esr_cooccur_finalize": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_i32p, c_i32p, c_f32p, c_vp, c_size, c_vp]),
 }
 
 

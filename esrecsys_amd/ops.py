@@ -1501,3 +1501,49 @@ def rows_f32_to_bf16(rows):
     out = torch.empty(rows.shape, dtype=torch.bfloat16, device=rows.device)
     check(lib.esr_rows_f32_to_bf16(_p(rows), rows.shape[0], rows.shape[1], _p(out), _stream()), "esr_rows_f32_to_bf16")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# co-occurrence builder (esr_cooccur.hip): the table is one uint8 tensor, header words read through an int64 view
+def cooccur_table(capacity, device):
+    """A fresh, empty pair table of `capacity` (a power of two >= 2) slots."""
+    lib = _lib.load()
+    table = _ws(_ws_bytes("esr_cooccur_table_bytes", int(capacity)), device)
+    check(lib.esr_cooccur_table_init(_p(table), int(capacity), _stream()), "esr_cooccur_table_init")
+    return table
+
+
+def cooccur_header(table):
+    """(occupied slots, failure bits) of a pair table: one read-back, i.e. a sync."""
+    used, fail = table[:16].view(torch.int64).tolist()
+    return used, fail
+
+
+def cooccur_accumulate(table, capacity, tokens, doc_offsets, tok_begin, tok_end, context_window):
+    """Adds the window pairs whose later position lies in [tok_begin, tok_end) to the table."""
+    lib = _lib.load()
+    _req(tokens, torch.int32, "tokens"), _req(doc_offsets, torch.int64, "doc_offsets")
+    check(lib.esr_cooccur_accumulate(_p(tokens), tokens.numel(), _p(doc_offsets), doc_offsets.numel() - 1,
+                                     int(tok_begin), int(tok_end), int(context_window), _p(table), int(capacity),
+                                     _stream()), "esr_cooccur_accumulate")
+
+
+def cooccur_rehash(table, capacity, new_capacity):
+    """A table of new_capacity slots holding every pair of `table` with its sum."""
+    lib = _lib.load()
+    new = _ws(_ws_bytes("esr_cooccur_table_bytes", int(new_capacity)), table.device)
+    check(lib.esr_cooccur_rehash(_p(table), int(capacity), _p(new), int(new_capacity), _stream()), "esr_cooccur_rehash")
+    return new
+
+
+def cooccur_finalize(table, capacity, nnz, num_ids, context_window):
+    """(index int32[nnz], other int32[nnz], count float32[nnz]) ascending by (index, other)."""
+    lib = _lib.load()
+    dev = table.device
+    index = torch.empty(nnz, dtype=torch.int32, device=dev)
+    other = torch.empty(nnz, dtype=torch.int32, device=dev)
+    count = torch.empty(nnz, dtype=torch.float32, device=dev)
+    ws = _ws(int(lib.esr_cooccur_finalize_workspace_bytes(int(nnz))), dev)
+    check(lib.esr_cooccur_finalize(_p(table), int(capacity), int(nnz), int(num_ids), int(context_window), _p(index),
+                                   _p(other), _p(count), _p(ws), ws.numel(), _stream()), "esr_cooccur_finalize")
+    return index, other, count

@@ -852,6 +852,35 @@ int esr_sharded_glove_step_overlapped(const esr_shard_group_t* emb, const esr_sh
                                       int64_t B, int mode, float lr, float eps, float* loss, void* workspace,
                                       size_t workspace_bytes, esr_stream_t stream);
 
+/* ---- GloVe co-occurrence matrix from token-id streams (esr_cooccur.hip; the reference's wikipedia/make_cooccurrence.py) ----
+ * Position i of a document pairs with j in [max(0, i - W), min(n, i + W)) and adds 1 / |i - j| to the entry
+ * (index = t[i], other = t[j]) when t[i] > t[j]; nothing crosses a document boundary.  Sums are kept in fixed point
+ * (units of 1 / lcm(1 .. W), uint64), so they do not depend on the order of the atomics or on how the corpus is cut into
+ * calls; 1 <= W <= 22.
+ * The table is device memory of esr_cooccur_table_bytes(capacity) bytes, 16-byte aligned, capacity a power of two >= 2:
+ * a 256-byte header -- uint64 word 0: occupied slots, word 1: failure bits (1: a probe wrapped the whole table, 2: a
+ * negative token id, 4: doc_offsets[0] / doc_offsets[ndocs] outside [0, N], 8: finalize's nnz below the table's) --
+ * then keys uint64[capacity] (index << 32 | other, all ones = empty) and sums uint64[capacity].  The caller reads the
+ * header and must keep capacity >= occupied + (tok_end - tok_begin) * W before a call: a full table raises failure bit 1,
+ * it never spins and never drops an increment silently.
+ *   accumulate  the pairs whose LATER position lies in [tok_begin, tok_end) (any cut of [0, N) into such ranges gives
+ *               the same table); tokens int32[N] >= 0, doc_offsets int64[ndocs + 1] in CSR form (device memory; empty
+ *               documents allowed).
+ *   rehash      new_table (initialised here) receives every occupied slot of table: same keys, same sums.
+ *   finalize    nnz = the header's occupied count, num_ids > every id: (index, other, count) ascending by (index, other),
+ *               count = (float)((double)sum / lcm(1 .. W)). */
+size_t esr_cooccur_table_bytes(int64_t capacity);
+int esr_cooccur_table_init(void* table, int64_t capacity, esr_stream_t stream);
+int esr_cooccur_accumulate(const int32_t* tokens, int64_t N, const int64_t* doc_offsets, int64_t ndocs,
+                           int64_t tok_begin, int64_t tok_end, int context_window, void* table, int64_t capacity,
+                           esr_stream_t stream);
+int esr_cooccur_rehash(const void* table, int64_t capacity, void* new_table, int64_t new_capacity,
+                       esr_stream_t stream);
+size_t esr_cooccur_finalize_workspace_bytes(int64_t nnz);
+int esr_cooccur_finalize(void* table, int64_t capacity, int64_t nnz, int64_t num_ids, int context_window,
+                         int32_t* index, int32_t* other, float* count, void* workspace, size_t workspace_bytes,
+                         esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
