@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 namespace esr {
 
@@ -27,6 +28,15 @@ struct SortSegs {
   int64_t offset[kMaxSortSegs];     // added to every id of the segment
   int n;
 };
+// (the lists of a batch: blockIdx.y -- blockIdx.x in the one-tile kernel -- picks the list)
+constexpr int kMaxSortBatch = 8;
+struct SortSegsBatch {
+  SortSegs b[kMaxSortBatch];
+};
+// Slots k >= sg.n are never read (seg_id tests k < sg.n) and lists b >= nbatch of a batch are never launched.  The
+// builders below -- the only code that fills these structs -- still give them one defined value: an unused slot has
+// ids = nullptr, offset = 0, start = the list's length (the running sums carried on with zero counts), and an unused
+// list is a copy of list 0.
 __device__ __forceinline__ int32_t seg_id(const SortSegs& sg, int64_t i) {
   const int32_t* src = sg.ids[0];
   int64_t start = 0, off = sg.offset[0];
@@ -42,6 +52,66 @@ __device__ __forceinline__ int32_t seg_id(const SortSegs& sg, int64_t i) {
 __global__ __launch_bounds__(kBlock) void concat_segs_kernel(SortSegs sg, int64_t n, int32_t* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
     out[i] = seg_id(sg, i);
+}
+
+// The list [ids[k] + offsets[k] : k < nseg] as a SortSegs.  Returns its length, or -1 with the error set under the
+// caller's name `who` (a negative count, a null segment that is not empty, 2^31 ids or more); `list` >= 0 names the
+// list of a batch in the message.
+static int64_t fill_segs(const char* who, SortSegs* sg, const int32_t* const* ids, const int64_t* counts,
+                         const int64_t* offsets, int nseg, int list = -1) {
+  sg->n = nseg;
+  sg->start[0] = 0;
+  for (int i = 0; i < kMaxSortSegs; ++i) {
+    const bool used = i < nseg;
+    if (used && (counts[i] < 0 || (counts[i] > 0 && !ids[i]))) {
+      if (list < 0) set_error("%s: bad segment %d", who, i);
+      else set_error("%s: bad segment %d of list %d", who, i, list);
+      return -1;
+    }
+    sg->ids[i] = used ? ids[i] : nullptr;
+    sg->offset[i] = used ? offsets[i] : 0;
+    sg->start[i + 1] = sg->start[i] + (used ? counts[i] : 0);
+  }
+  const int64_t n = sg->start[nseg];
+  if (n >= ((int64_t)1 << 31)) {
+    set_error("%s: n=%lld", who, (long long)n);
+    return -1;
+  }
+  return n;
+}
+// one array of n ids or keys (the caller has checked n and the pointer: this cannot fail)
+static SortSegs one_seg(const int32_t* ids, int64_t n) {
+  SortSegs sg;
+  const int64_t zero = 0;
+  fill_segs("", &sg, &ids, &n, &zero, 1);
+  return sg;
+}
+static void pad_batch(SortSegsBatch* sb, int nbatch) {
+  for (int b = nbatch; b < kMaxSortBatch; ++b) sb->b[b] = sb->b[0];
+}
+// the lists of a batch from the flattened [nbatch][nseg] pointer array (every list has the same counts and offsets);
+// returns the length of one list, or -1 as fill_segs
+static int64_t fill_batch(const char* who, SortSegsBatch* sb, const int32_t* const* ids, const int64_t* counts,
+                          const int64_t* offsets, int nseg, int nbatch) {
+  int64_t n = 0;
+  for (int b = 0; b < nbatch; ++b)
+    if ((n = fill_segs(who, &sb->b[b], ids + (size_t)b * nseg, counts, offsets, nseg, b)) < 0) return -1;
+  pad_batch(sb, nbatch);
+  return n;
+}
+// nb consecutive rows of a key matrix (row r = n keys at base + r * stride) as the lists of a batch
+static void fill_row_batch(SortSegsBatch* sb, const int32_t* base, int64_t stride, int64_t n, int nb) {
+  for (int b = 0; b < nb; ++b) sb->b[b] = one_seg(base + (int64_t)b * stride, n);
+  pad_batch(sb, nb);
+}
+
+// f(std::integral_constant<int, TB>) for the smallest tile of 2^TB = 512 / 1024 / 2048 keys of which `tiles` cover n keys
+// (n <= tiles << kMaxTileBits)
+template <class F>
+static void with_tile_bits(int64_t n, int tiles, F&& f) {
+  if (n <= 512 * tiles) f(std::integral_constant<int, 9>{});
+  else if (n <= 1024 * tiles) f(std::integral_constant<int, 10>{});
+  else f(std::integral_constant<int, 11>{});
 }
 
 // Short occurrence lists (one playlist of the Spotify step, the reference's own batch sizes of 16-128): one
@@ -145,10 +215,6 @@ __device__ __forceinline__ void tile_bitonic(uint32_t& k0, uint32_t& k1, uint32_
 
 // (bodies shared by the one-list kernels and the batched ones, where blockIdx.y picks the list: `bx` = the workgroup's
 // index inside its own list)
-constexpr int kMaxSortBatch = 8;
-struct SortSegsBatch {
-  SortSegs b[kMaxSortBatch];
-};
 template <int TB>
 __device__ __forceinline__ void tile_sort_body(const SortSegs& ids, int n, uint32_t* __restrict__ tiles,
                                                uint32_t* __restrict__ splitters, uint32_t* key, int bx) {
@@ -163,8 +229,8 @@ __device__ __forceinline__ void tile_sort_body(const SortSegs& ids, int n, uint3
   tile_bitonic<TB>(k0, k1, key);
   tiles[base + t] = k0;
   tiles[base + t + kHalf] = k1;
-  // the last key of every 32-key block, packed: the rank kernel stages these (it used to gather them from the tiles,
-  // one cache line per splitter and workgroup)
+  // the last key of every 8-key block (kSplitEvery), packed: the rank kernel stages these (it used to gather them from
+  // the tiles, one cache line per splitter and workgroup)
   if ((t & (kSplitEvery - 1)) == kSplitEvery - 1) {
     constexpr int kSplitPerTile = kTile / kSplitEvery;
     splitters[bx * kSplitPerTile + t / kSplitEvery] = k0;
@@ -224,8 +290,8 @@ __global__ __launch_bounds__((1 << TB) / 2) void tile_sort_single_batched_kernel
   tile_sort_single_body<TB>(sb.b[y], n, sorted_ids + (int64_t)y * n, perm + (int64_t)y * n, key);
 }
 
-// Two-level search: the last id of every 32-key block of every tile ("splitters", <= 4 KB) is staged in LDS and
-// searched there; only the final 32-key window -- one 128-byte line -- is searched in global memory.  A plain
+// Two-level search: the last id of every 8-key block of every tile ("splitters", <= 16 KB) is staged in LDS and
+// searched there; only the final 8-key window -- one 32-byte block -- is read from global memory, and counted.  A plain
 // binary search over the tiles touched ~12 scattered lines per (element, tile) and was bound by L1 line rate.
 // 16 lanes per element, one per tile: the searches of one element run side by side and their counts are summed
 // with shuffles (one thread walking all tiles was latency-bound at one wave per SIMD: 26 us for 24 576 keys).
@@ -299,12 +365,14 @@ __global__ __launch_bounds__(kBlock) void tile_rank_batched_kernel(const uint32_
   tile_rank_body<TB>(tiles + y * ws_stride, splitters + y * ws_stride, n, ntiles, sorted_ids + (int64_t)y * n,
                      perm + (int64_t)y * n, spl, blockIdx.x, reps);
 }
+constexpr int64_t kMidWsWords = kMidSortMax + kMidSortMax / kSplitEvery;  // one list's (tiles | splitters) area
+static size_t mid_ws_bytes(int nbatch = 1) { return (size_t)nbatch * kMidWsWords * 4; }
 template <int TB>
 static void launch_tile_sort(const SortSegs& sg, int n, uint32_t* tiles, int32_t* sorted_ids, int32_t* perm,
                              hipStream_t st) {
   constexpr int kTile = 1 << TB;
   const int ntiles = (int)cdiv(n, kTile);
-  uint32_t* splitters = tiles + kMidSortMax;  // [ntiles][kTile / 32], behind the tiles
+  uint32_t* splitters = tiles + kMidSortMax;  // [ntiles][kTile / kSplitEvery], behind the tiles
   hipLaunchKernelGGL((tile_sort_kernel<TB>), dim3(ntiles), dim3(kTile / 2), 0, st, sg, n, tiles, splitters);
   const int64_t blocks = cdiv((int64_t)ntiles * kTile * kMidTiles, kBlock);
   const int reps = rank_reps(blocks);
@@ -312,7 +380,6 @@ static void launch_tile_sort(const SortSegs& sg, int n, uint32_t* tiles, int32_t
                      (const uint32_t*)splitters, n, ntiles, sorted_ids, perm, reps);
 }
 
-constexpr int64_t kMidWsWords = kMidSortMax + kMidSortMax / kSplitEvery;  // one list's (tiles | splitters) area
 template <int TB>
 static void launch_tile_sort_batched(const SortSegsBatch& sb, int nbatch, int n, uint32_t* tiles, int32_t* sorted_ids,
                                      int32_t* perm, hipStream_t st) {
@@ -606,6 +673,12 @@ static size_t radix_ws_layout(int64_t n, char* base, RadixWs* ws) {
   if (ws) *ws = w;
   return off;
 }
+// f(std::bool_constant<FIRST>): the kernels of a pass with FIRST chosen once
+template <class F>
+static void with_first(bool first, F&& f) {
+  if (first) f(std::true_type{});
+  else f(std::false_type{});
+}
 template <int TB>
 static void launch_radix_sort(const SortSegs& sg, int n, int key_bits, const RadixWs& ws, int32_t* sorted_ids,
                               int32_t* perm, hipStream_t st) {
@@ -622,23 +695,16 @@ static void launch_radix_sort(const SortSegs& sg, int n, int key_bits, const Rad
     const bool tall = ntiles > (kRadixMaxN >> TB);  // more tiles than a scatter workgroup should re-reduce itself
     const int32_t* segsum = tall ? ws.segsum : nullptr;
     const dim3 seg_grid((kTile / 2 + kBlock - 1) / kBlock, (ntiles + kRadixSeg - 1) / kRadixSeg);
-    if (p == 0) {
-      hipLaunchKernelGGL((radix_tile_kernel<TB, true>), dim3(ntiles), dim3(kThreads), 0, st, sg, kin, n, shift, ws.tiles,
+    with_first(p == 0, [&](auto first) {
+      constexpr bool FIRST = decltype(first)::value;
+      hipLaunchKernelGGL((radix_tile_kernel<TB, FIRST>), dim3(ntiles), dim3(kThreads), 0, st, sg, kin, n, shift, ws.tiles,
                          ws.hist);
       if (tall)
         hipLaunchKernelGGL((radix_segsum_kernel<TB>), seg_grid, dim3(kBlock), 0, st, (const int32_t*)ws.hist, ntiles,
                            ws.segsum);
-      hipLaunchKernelGGL((radix_scatter_kernel<TB, true>), dim3(ntiles), dim3(kThreads), 0, st, sg, kin, vin, n, ntiles,
+      hipLaunchKernelGGL((radix_scatter_kernel<TB, FIRST>), dim3(ntiles), dim3(kThreads), 0, st, sg, kin, vin, n, ntiles,
                          (const uint32_t*)ws.tiles, (const int32_t*)ws.hist, kout, vout, segsum);
-    } else {
-      hipLaunchKernelGGL((radix_tile_kernel<TB, false>), dim3(ntiles), dim3(kThreads), 0, st, sg, kin, n, shift, ws.tiles,
-                         ws.hist);
-      if (tall)
-        hipLaunchKernelGGL((radix_segsum_kernel<TB>), seg_grid, dim3(kBlock), 0, st, (const int32_t*)ws.hist, ntiles,
-                           ws.segsum);
-      hipLaunchKernelGGL((radix_scatter_kernel<TB, false>), dim3(ntiles), dim3(kThreads), 0, st, sg, kin, vin, n, ntiles,
-                         (const uint32_t*)ws.tiles, (const int32_t*)ws.hist, kout, vout, segsum);
-    }
+    });
     kin = kout;
     vin = vout;
   }
@@ -666,27 +732,18 @@ static void launch_radix_sort_batched(const SortSegsBatch& sb, int nbatch, int n
     const int shift = p * TB;
     const bool tall = ntiles > 128;
     const dim3 scan_grid(kTile / (tall ? 16 : 64), nbatch);
-    auto colscan = [&]() {
+    with_first(p == 0, [&](auto first) {
+      constexpr bool FIRST = decltype(first)::value;
+      hipLaunchKernelGGL((radix_tile_batched_kernel<TB, FIRST>), grid, dim3(kThreads), 0, st, sb, kin, in_stride, n, shift,
+                         ws.tiles, ws.hist, stride);
       if (tall)
         hipLaunchKernelGGL((radix_colscan_kernel<TB, 16>), scan_grid, dim3(kBlock), 0, st, ws.hist, ntiles, ws.segsum, stride);
       else
         hipLaunchKernelGGL((radix_colscan_kernel<TB, 64>), scan_grid, dim3(kBlock), 0, st, ws.hist, ntiles, ws.segsum, stride);
-    };
-    if (p == 0) {
-      hipLaunchKernelGGL((radix_tile_batched_kernel<TB, true>), grid, dim3(kThreads), 0, st, sb, kin, in_stride, n, shift,
-                         ws.tiles, ws.hist, stride);
-      colscan();
-      hipLaunchKernelGGL((radix_scatter_batched_kernel<TB, true>), grid, dim3(kThreads), 0, st, sb, kin, vin, in_stride, n,
+      hipLaunchKernelGGL((radix_scatter_batched_kernel<TB, FIRST>), grid, dim3(kThreads), 0, st, sb, kin, vin, in_stride, n,
                          ntiles, (const uint32_t*)ws.tiles, (const int32_t*)ws.hist, (const int32_t*)ws.segsum, stride,
                          kout, vout, out_stride);
-    } else {
-      hipLaunchKernelGGL((radix_tile_batched_kernel<TB, false>), grid, dim3(kThreads), 0, st, sb, kin, in_stride, n, shift,
-                         ws.tiles, ws.hist, stride);
-      colscan();
-      hipLaunchKernelGGL((radix_scatter_batched_kernel<TB, false>), grid, dim3(kThreads), 0, st, sb, kin, vin, in_stride,
-                         n, ntiles, (const uint32_t*)ws.tiles, (const int32_t*)ws.hist, (const int32_t*)ws.segsum, stride,
-                         kout, vout, out_stride);
-    }
+    });
     kin = kout;
     vin = vout;
     in_stride = out_stride;
@@ -1093,8 +1150,31 @@ static void radix_any(const SortSegs& sg, int64_t n, int key_bits, char* workspa
     return;
   }
   SortSegsBatch sb;
-  for (int b = 0; b < kMaxSortBatch; ++b) sb.b[b] = sg;
+  sb.b[0] = sg;
+  pad_batch(&sb, 1);
   launch_radix_sort_batched<11>(sb, 1, (int)n, key_bits, workspace, sorted_ids, perm, st);
+}
+
+// Which way a list of n ids below V goes.  nbatch == 0: one list (segment_sort_segs); nbatch >= 1: the equally long
+// lists of esr_segment_sort_ids_batched, whose one-tile and mid kernels take all the lists at once.  The two differ on
+// purpose: the wide-id small kernel exists for single lists only, and the batched radix passes want more than one list
+// (one list is better off with the single-list form, which launches less) of at most kRadixLongN ids.
+enum class SortPath { kOneTile, kWideSmall, kMid, kRadix, kRadixBatched, kListByList };
+static SortPath sort_path(int64_t n, int64_t V, int nbatch) {
+  const bool fits32 = V <= ((int64_t)1 << (32 - kMaxTileBits));  // (id << 11 | position) is a 32-bit composite
+  if (fits32 && n <= (1 << kMaxTileBits)) return SortPath::kOneTile;              // one launch
+  if (nbatch == 0 && !fits32 && n <= kSmallSortMax) return SortPath::kWideSmall;  // 64-bit composites in one workgroup
+  if (fits32 && n <= kMidSortMax) return SortPath::kMid;                          // two launches
+  if (nbatch == 0) return SortPath::kRadix;                                       // radix_any
+  if (n <= kRadixLongN && bits_for(V) <= kRadixMaxPasses * 11 && nbatch > 1) return SortPath::kRadixBatched;
+  return SortPath::kListByList;  // every list through segment_sort_segs, one after the other
+}
+
+// ESR_OK, or the error set under the caller's name and ESR_EWORKSPACE
+static int workspace_ok(const char* who, const void* workspace, size_t have, size_t need) {
+  if (workspace && have >= need && ((uintptr_t)workspace & 15) == 0) return ESR_OK;
+  set_error("%s: workspace %zu bytes < %zu required (or misaligned)", who, have, need);
+  return ESR_EWORKSPACE;
 }
 
 }  // namespace esr
@@ -1104,45 +1184,39 @@ using namespace esr;
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------
+// (sized without V: enough for whichever path sort_path picks for a list of n ids, which segment_sort_segs checks against
+// this very figure)
 size_t esr_segment_sort_workspace_bytes(int64_t n) {
   if (n <= 0) return 256;
-  const size_t tiles = n <= kMidSortMax ? align_up((size_t)(kMidSortMax + kMidSortMax / kSplitEvery) * 4, 256) : 0;
+  const size_t tiles = n <= kMidSortMax ? align_up(mid_ws_bytes(), 256) : 0;
   return std::max(tiles, radix_ws_layout(n, nullptr, nullptr));
 }
 
 static int segment_sort_segs(const char* who, const SortSegs& sg, int64_t n, int64_t V, int32_t* sorted_ids,
                              int32_t* perm, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  const bool fits32 = V <= ((int64_t)1 << (32 - kMaxTileBits));  // (id << 11 | position) is a 32-bit composite
-  if (fits32 && n <= (1 << kMaxTileBits)) {  // one tile: one launch
-    if (n <= 512) hipLaunchKernelGGL(tile_sort_single_kernel<9>, dim3(1), dim3(256), 0, st, sg, (int)n, sorted_ids, perm);
-    else if (n <= 1024) hipLaunchKernelGGL(tile_sort_single_kernel<10>, dim3(1), dim3(512), 0, st, sg, (int)n, sorted_ids, perm);
-    else hipLaunchKernelGGL(tile_sort_single_kernel<11>, dim3(1), dim3(1024), 0, st, sg, (int)n, sorted_ids, perm);
+  const SortPath path = sort_path(n, V, 0);
+  if (path == SortPath::kOneTile) {
+    with_tile_bits(n, 1, [&](auto tb) {
+      constexpr int TB = decltype(tb)::value;
+      hipLaunchKernelGGL(tile_sort_single_kernel<TB>, dim3(1), dim3((1 << TB) / 2), 0, st, sg, (int)n, sorted_ids, perm);
+    });
     return check_launch(who);
   }
-  if (n <= kSmallSortMax && !fits32) {  // short list of wide ids: 64-bit composites in one workgroup's LDS
+  if (path == SortPath::kWideSmall) {
     hipLaunchKernelGGL(segment_sort_small_kernel, dim3(1), dim3(kSmallSortThreads), 0, st, sg, (int)n, sorted_ids, perm);
     return check_launch(who);
   }
-  if (n <= kMidSortMax && fits32) {
-    if ((size_t)(kMidSortMax + kMidSortMax / kSplitEvery) * 4 > workspace_bytes || ((uintptr_t)workspace & 15)) {
-      set_error("%s: workspace %zu bytes too small (or misaligned)", who, workspace_bytes);
-      return ESR_EWORKSPACE;
-    }
-    uint32_t* tiles = (uint32_t*)workspace;
-    if (n <= 512 * kMidTiles) launch_tile_sort<9>(sg, (int)n, tiles, sorted_ids, perm, st);
-    else if (n <= 1024 * kMidTiles) launch_tile_sort<10>(sg, (int)n, tiles, sorted_ids, perm, st);
-    else launch_tile_sort<11>(sg, (int)n, tiles, sorted_ids, perm, st);
-    return check_launch(who);
-  }
-  if (n > kSortMaxN) {
+  if (path == SortPath::kRadix && n > kSortMaxN) {
     set_error("%s: n=%lld ids exceed 2^30", who, (long long)n);
     return ESR_EINVAL;
   }
-  if (radix_ws_layout(n, nullptr, nullptr) > workspace_bytes || ((uintptr_t)workspace & 15)) {
-    set_error("%s: workspace %zu bytes too small (or misaligned)", who, workspace_bytes);
-    return ESR_EWORKSPACE;
-  }
-  radix_any(sg, n, bits_for(V), (char*)workspace, sorted_ids, perm, st);
+  if (int rc = workspace_ok(who, workspace, workspace_bytes, esr_segment_sort_workspace_bytes(n))) return rc;
+  if (path == SortPath::kMid)
+    with_tile_bits(n, kMidTiles, [&](auto tb) {
+      launch_tile_sort<decltype(tb)::value>(sg, (int)n, (uint32_t*)workspace, sorted_ids, perm, st);
+    });
+  else
+    radix_any(sg, n, bits_for(V), (char*)workspace, sorted_ids, perm, st);
   return check_launch(who);
 }
 
@@ -1152,15 +1226,7 @@ int esr_segment_sort_ids(const int32_t* ids, int64_t n, int64_t V, int32_t* sort
               (long long)n, (long long)V);
   if (n == 0) return ESR_OK;
   ESR_REQUIRE(ids && sorted_ids && perm && workspace, "esr_segment_sort_ids: null pointer");
-  SortSegs sg;
-  sg.n = 1;
-  for (int i = 0; i < kMaxSortSegs; ++i) {
-    sg.ids[i] = i == 0 ? ids : nullptr;
-    sg.offset[i] = 0;
-    sg.start[i] = i == 0 ? 0 : n;
-  }
-  sg.start[kMaxSortSegs] = n;
-  return segment_sort_segs("esr_segment_sort_ids", sg, n, V, sorted_ids, perm, workspace, workspace_bytes,
+  return segment_sort_segs("esr_segment_sort_ids", one_seg(ids, n), n, V, sorted_ids, perm, workspace, workspace_bytes,
                            as_stream(stream));
 }
 
@@ -1171,17 +1237,8 @@ int esr_segment_sort_ids_multi(const int32_t* const* ids, const int64_t* counts,
   ESR_REQUIRE(nseg >= 1 && nseg <= kMaxSortSegs && ids && counts && offsets && V > 0,
               "esr_segment_sort_ids_multi: nseg=%d not in [1, %d] or null argument", nseg, kMaxSortSegs);
   SortSegs sg;
-  sg.n = nseg;
-  sg.start[0] = 0;
-  for (int i = 0; i < kMaxSortSegs; ++i) {
-    ESR_REQUIRE(i >= nseg || (counts[i] >= 0 && (counts[i] == 0 || ids[i])), "esr_segment_sort_ids_multi: bad segment %d",
-                i);
-    sg.ids[i] = i < nseg ? ids[i] : nullptr;
-    sg.offset[i] = i < nseg ? offsets[i] : 0;
-    sg.start[i + 1] = sg.start[i] + (i < nseg ? counts[i] : 0);
-  }
-  const int64_t n = sg.start[nseg];
-  ESR_REQUIRE(n < ((int64_t)1 << 31), "esr_segment_sort_ids_multi: n=%lld", (long long)n);
+  const int64_t n = fill_segs("esr_segment_sort_ids_multi", &sg, ids, counts, offsets, nseg);
+  if (n < 0) return ESR_EINVAL;
   if (n == 0) return ESR_OK;
   ESR_REQUIRE(sorted_ids && perm && workspace, "esr_segment_sort_ids_multi: null pointer");
   return segment_sort_segs("esr_segment_sort_ids_multi", sg, n, V, sorted_ids, perm, workspace, workspace_bytes,
@@ -1190,8 +1247,8 @@ int esr_segment_sort_ids_multi(const int32_t* const* ids, const int64_t* counts,
 
 size_t esr_segment_sort_batched_workspace_bytes(int64_t n, int nbatch) {
   if (n <= 0 || nbatch <= 0) return 256;
-  const size_t one = esr_segment_sort_workspace_bytes(n);  // the fallback sorts list after list in this much
-  const size_t mid = n <= kMidSortMax ? align_up((size_t)nbatch * kMidWsWords * 4, 256) : 0;
+  const size_t one = esr_segment_sort_workspace_bytes(n);  // kListByList sorts list after list in this much
+  const size_t mid = n <= kMidSortMax ? align_up(mid_ws_bytes(nbatch), 256) : 0;
   // (any n: lists of wide ids -- V beyond 2^21 -- take the batched radix passes even when they are short)
   const size_t radix = n <= kRadixLongN ? (size_t)nbatch * radix_ws_layout(n, nullptr, nullptr) : 0;  // (longer: list by list)
   return std::max({one, mid, radix});
@@ -1200,63 +1257,57 @@ size_t esr_segment_sort_batched_workspace_bytes(int64_t n, int nbatch) {
 int esr_segment_sort_ids_batched(const int32_t* const* ids, const int64_t* counts, const int64_t* offsets, int nseg,
                                  int nbatch, int64_t V, int32_t* sorted_ids, int32_t* perm, void* workspace,
                                  size_t workspace_bytes, esr_stream_t stream) {
-  TraceScope trace_scope_("esr_segment_sort_ids_batched");
+  const char* who = "esr_segment_sort_ids_batched";
+  TraceScope trace_scope_(who);
   ESR_REQUIRE(nseg >= 1 && nseg <= kMaxSortSegs && nbatch >= 1 && nbatch <= kMaxSortBatch && ids && counts && offsets &&
                   V > 0,
               "esr_segment_sort_ids_batched: nseg=%d not in [1, %d], nbatch=%d not in [1, %d], or null argument", nseg,
               kMaxSortSegs, nbatch, kMaxSortBatch);
   SortSegsBatch sb;
-  int64_t n = 0;
-  for (int b = 0; b < nbatch; ++b) {
-    SortSegs& sg = sb.b[b];
-    sg.n = nseg;
-    sg.start[0] = 0;
-    for (int i = 0; i < kMaxSortSegs; ++i) {
-      const int32_t* src = i < nseg ? ids[(size_t)b * nseg + i] : nullptr;
-      ESR_REQUIRE(i >= nseg || (counts[i] >= 0 && (counts[i] == 0 || src)),
-                  "esr_segment_sort_ids_batched: bad segment %d of list %d", i, b);
-      sg.ids[i] = src;
-      sg.offset[i] = i < nseg ? offsets[i] : 0;
-      sg.start[i + 1] = sg.start[i] + (i < nseg ? counts[i] : 0);
-    }
-    n = sg.start[nseg];
-  }
-  for (int b = nbatch; b < kMaxSortBatch; ++b) sb.b[b] = sb.b[0];
-  ESR_REQUIRE(n < ((int64_t)1 << 31), "esr_segment_sort_ids_batched: n=%lld", (long long)n);
+  const int64_t n = fill_batch(who, &sb, ids, counts, offsets, nseg, nbatch);
+  if (n < 0) return ESR_EINVAL;
   if (n == 0) return ESR_OK;
   ESR_REQUIRE(sorted_ids && perm && workspace, "esr_segment_sort_ids_batched: null pointer");
-  if (workspace_bytes < esr_segment_sort_batched_workspace_bytes(n, nbatch) || ((uintptr_t)workspace & 15)) {
-    set_error("esr_segment_sort_ids_batched: workspace %zu bytes < %zu required (or misaligned)", workspace_bytes,
-              esr_segment_sort_batched_workspace_bytes(n, nbatch));
-    return ESR_EWORKSPACE;
-  }
+  if (int rc = workspace_ok(who, workspace, workspace_bytes, esr_segment_sort_batched_workspace_bytes(n, nbatch))) return rc;
   hipStream_t st = as_stream(stream);
-  const bool fits32 = V <= ((int64_t)1 << (32 - kMaxTileBits));
-  if (fits32 && n <= (1 << kMaxTileBits)) {  // every list is one tile: one launch for all of them
-    if (n <= 512)
-      hipLaunchKernelGGL(tile_sort_single_batched_kernel<9>, dim3(nbatch), dim3(256), 0, st, sb, (int)n, sorted_ids, perm);
-    else if (n <= 1024)
-      hipLaunchKernelGGL(tile_sort_single_batched_kernel<10>, dim3(nbatch), dim3(512), 0, st, sb, (int)n, sorted_ids, perm);
-    else
-      hipLaunchKernelGGL(tile_sort_single_batched_kernel<11>, dim3(nbatch), dim3(1024), 0, st, sb, (int)n, sorted_ids, perm);
-    return check_launch("esr_segment_sort_ids_batched");
+  switch (sort_path(n, V, nbatch)) {
+    case SortPath::kOneTile:  // every list is one tile: one launch for all of them
+      with_tile_bits(n, 1, [&](auto tb) {
+        constexpr int TB = decltype(tb)::value;
+        hipLaunchKernelGGL(tile_sort_single_batched_kernel<TB>, dim3(nbatch), dim3((1 << TB) / 2), 0, st, sb, (int)n,
+                           sorted_ids, perm);
+      });
+      return check_launch(who);
+    case SortPath::kMid:  // two launches for all the lists
+      with_tile_bits(n, kMidTiles, [&](auto tb) {
+        launch_tile_sort_batched<decltype(tb)::value>(sb, nbatch, (int)n, (uint32_t*)workspace, sorted_ids, perm, st);
+      });
+      return check_launch(who);
+    case SortPath::kRadixBatched:  // four launches per pass pair for all lists
+      launch_radix_sort_batched<11>(sb, nbatch, (int)n, bits_for(V), (char*)workspace, sorted_ids, perm, st);
+      return check_launch(who);
+    default:  // one after the other (stream order: the workspace is reused)
+      for (int b = 0; b < nbatch; ++b)
+        if (int rc = segment_sort_segs(who, sb.b[b], n, V, sorted_ids + (int64_t)b * n, perm + (int64_t)b * n, workspace,
+                                       workspace_bytes, st))
+          return rc;
+      return ESR_OK;
   }
-  if (fits32 && n <= kMidSortMax) {  // two launches for all the lists
-    uint32_t* tiles = (uint32_t*)workspace;
-    if (n <= 512 * kMidTiles) launch_tile_sort_batched<9>(sb, nbatch, (int)n, tiles, sorted_ids, perm, st);
-    else if (n <= 1024 * kMidTiles) launch_tile_sort_batched<10>(sb, nbatch, (int)n, tiles, sorted_ids, perm, st);
-    else launch_tile_sort_batched<11>(sb, nbatch, (int)n, tiles, sorted_ids, perm, st);
-    return check_launch("esr_segment_sort_ids_batched");
-  }
-  if (n <= kRadixLongN && bits_for(V) <= kRadixMaxPasses * 11 && nbatch > 1) {  // four launches per pass pair for all lists
-    launch_radix_sort_batched<11>(sb, nbatch, (int)n, bits_for(V), (char*)workspace, sorted_ids, perm, st);
-    return check_launch("esr_segment_sort_ids_batched");
-  }
-  for (int b = 0; b < nbatch; ++b)  // longer lists: one after the other (stream order: the workspace is reused)
-    if (int rc = segment_sort_segs("esr_segment_sort_ids_batched", sb.b[b], n, V, sorted_ids + (int64_t)b * n,
-                                   perm + (int64_t)b * n, workspace, workspace_bytes, st))
-      return rc;
+}
+
+// `nb` (<= kMaxSortBatch) rows of n 32-bit keys each, row r at keys + r * stride, stably sorted: (sorted keys, positions)
+// into [nb][n] arrays.  More than one row: the batched radix passes in nb * radix_ws_layout(n) bytes; one row: as any list.
+static int sort_key_rows(const char* who, const int32_t* keys, int64_t stride, int64_t n, int nb, int32_t* sorted,
+                         int32_t* idx, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  SortSegsBatch sb;
+  fill_row_batch(&sb, keys, stride, n, nb);
+  if (nb == 1) return segment_sort_segs(who, sb.b[0], n, (int64_t)1 << 32, sorted, idx, workspace, workspace_bytes, st);
+  launch_radix_sort_batched<11>(sb, nb, (int)n, 32, (char*)workspace, sorted, idx, st);
   return ESR_OK;
+}
+static size_t sort_key_rows_bytes(int64_t n, int rows) {
+  return std::max((size_t)std::min(rows, kMaxSortBatch) * radix_ws_layout(n, nullptr, nullptr),
+                  esr_segment_sort_workspace_bytes(n));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1279,8 +1330,7 @@ static size_t argsort_own_layout(int64_t V, int T, size_t* keysT, size_t* idxT, 
   *idxT = off;    off += align_up((size_t)V * T * 4, 256);
   *ksorted = off; off += align_up((size_t)V * 4 * kMaxSortBatch, 256);
   *sort_ws = off;
-  off += std::max((size_t)std::min(T, kMaxSortBatch) * radix_ws_layout(V, nullptr, nullptr),
-                  esr_segment_sort_workspace_bytes(V));
+  off += sort_key_rows_bytes(V, T);
   return off;
 }
 
@@ -1294,57 +1344,32 @@ int esr_argsort_columns(const float* scores, int64_t V, int T, int32_t* indices,
                         size_t workspace_bytes, esr_stream_t stream) {
   ESR_REQUIRE(V > 0 && T > 0 && V <= kSortMaxN, "esr_argsort_columns: bad sizes V=%lld T=%d", (long long)V, T);
   ESR_REQUIRE(scores && indices && workspace, "esr_argsort_columns: null pointer");
-  if (workspace_bytes < esr_argsort_columns_workspace_bytes(V, T) || ((uintptr_t)workspace & 15)) {
-    set_error("esr_argsort_columns: workspace %zu bytes < %zu required (or misaligned)", workspace_bytes,
-              esr_argsort_columns_workspace_bytes(V, T));
-    return ESR_EWORKSPACE;
-  }
+  size_t o_keys, o_idx, o_sorted, o_ws;
+  const size_t total = argsort_own_layout(V, T, &o_keys, &o_idx, &o_sorted, &o_ws);
+  if (int rc = workspace_ok("esr_argsort_columns", workspace, workspace_bytes, total)) return rc;
   hipStream_t st = as_stream(stream);
-  size_t o_keys, o_idx, o_sorted;
+  // stable ascending sort of every column by the keys' unsigned images: three 11-bit passes of the radix sort above,
+  // eight columns per launch sequence (jnp.argsort(scores, axis=0): wikipedia/train_cooccurence.py:95)
   char* base = (char*)workspace;
-  {
-    // stable ascending sort of every column by the keys' unsigned images: three 11-bit passes of the radix sort above,
-    // eight columns per launch sequence (jnp.argsort(scores, axis=0): wikipedia/train_cooccurence.py:95)
-    size_t o_ws;
-    const size_t total = argsort_own_layout(V, T, &o_keys, &o_idx, &o_sorted, &o_ws);
-    int32_t* keysT = (int32_t*)(base + o_keys);     // [T][V]
-    int32_t* idxT = (int32_t*)(base + o_idx);       // [T][V]
-    int32_t* ksorted = (int32_t*)(base + o_sorted);  // [<= 8][V] (not read)
-    const int grid = (int)std::min<int64_t>(kMaxGrid, cdiv(V * T, kBlock));
-    hipLaunchKernelGGL(transpose_cols_keys_kernel, dim3(grid), dim3(kBlock), 0, st, scores, V, T, keysT);
-    for (int t0 = 0; t0 < T; t0 += kMaxSortBatch) {
-      const int nb = std::min(kMaxSortBatch, T - t0);
-      SortSegsBatch sb;
-      for (int b = 0; b < kMaxSortBatch; ++b) {
-        SortSegs& sg = sb.b[b];
-        sg.n = 1;
-        for (int i = 0; i < kMaxSortSegs; ++i) {
-          sg.ids[i] = i == 0 ? keysT + (int64_t)(t0 + std::min(b, nb - 1)) * V : nullptr;
-          sg.offset[i] = 0;
-          sg.start[i + 1] = V;
-        }
-        sg.start[0] = 0;
-      }
-      if (nb > 1) {
-        launch_radix_sort_batched<11>(sb, nb, (int)V, 32, base + o_ws, ksorted, idxT + (int64_t)t0 * V, st);
-      } else if (int rc = segment_sort_segs("esr_argsort_columns", sb.b[0], V, (int64_t)1 << 32, ksorted,
-                                            idxT + (int64_t)t0 * V, base + o_ws, total - o_ws, st)) {
-        return rc;
-      }
-    }
-    hipLaunchKernelGGL(untranspose_idx_kernel, dim3(grid), dim3(kBlock), 0, st, (const int32_t*)idxT, V, T, indices);
-    return check_launch("esr_argsort_columns");
-  }
+  int32_t* keysT = (int32_t*)(base + o_keys);      // [T][V]
+  int32_t* idxT = (int32_t*)(base + o_idx);        // [T][V]
+  int32_t* ksorted = (int32_t*)(base + o_sorted);  // [<= 8][V] (not read)
+  const int grid = (int)std::min<int64_t>(kMaxGrid, cdiv(V * T, kBlock));
+  hipLaunchKernelGGL(transpose_cols_keys_kernel, dim3(grid), dim3(kBlock), 0, st, scores, V, T, keysT);
+  for (int t0 = 0; t0 < T; t0 += kMaxSortBatch)
+    if (int rc = sort_key_rows("esr_argsort_columns", keysT + (int64_t)t0 * V, V, V, std::min(kMaxSortBatch, T - t0),
+                               ksorted, idxT + (int64_t)t0 * V, base + o_ws, total - o_ws, st))
+      return rc;
+  hipLaunchKernelGGL(untranspose_idx_kernel, dim3(grid), dim3(kBlock), 0, st, (const int32_t*)idxT, V, T, indices);
+  return check_launch("esr_argsort_columns");
 }
 
 // ------------------------------------------------------------------------------------------------
 size_t esr_score_topk_workspace_bytes(int64_t nq, int64_t N, int k) {
-  (void)k;
   if (nq <= 0 || N <= 0) return 256;
   const size_t row = align_up((size_t)N * 4, 256);
   if (k > kSelectMaxK)  // own radix sort, kMaxSortBatch rows per launch sequence (see esr_score_topk)
-    return row * (size_t)nq + 3 * row * kMaxSortBatch +
-           std::max((size_t)kMaxSortBatch * radix_ws_layout(N, nullptr, nullptr), esr_segment_sort_workspace_bytes(N));
+    return row * (size_t)nq + 3 * row * kMaxSortBatch + sort_key_rows_bytes(N, kMaxSortBatch);
   return row * (size_t)nq + 2 * row;
 }
 
@@ -1357,11 +1382,8 @@ int esr_score_topk(const float* queries, const float* candidates, int64_t nq, in
   ESR_REQUIRE(queries && candidates && out_scores && out_indices && workspace, "esr_score_topk: null pointer");
   const RowGeom g = row_geom(D);
   ESR_REQUIRE(g.nch <= kMaxChunksPerLane, "esr_score_topk: D=%d not supported", D);
-  if (workspace_bytes < esr_score_topk_workspace_bytes(nq, N, k) || ((uintptr_t)workspace & 15)) {
-    set_error("esr_score_topk: workspace %zu bytes < %zu required (or misaligned)", workspace_bytes,
-              esr_score_topk_workspace_bytes(nq, N, k));
-    return ESR_EWORKSPACE;
-  }
+  if (int rc = workspace_ok("esr_score_topk", workspace, workspace_bytes, esr_score_topk_workspace_bytes(nq, N, k)))
+    return rc;
   hipStream_t st = as_stream(stream);
   const size_t row = align_up((size_t)N * 4, 256);
   char* base = (char*)workspace;
@@ -1372,63 +1394,52 @@ int esr_score_topk(const float* queries, const float* candidates, int64_t nq, in
   // launch for all queries; only the k survivors are sorted) instead of a full device sort of all N scores per query
   if (k <= kSelectMaxK)
     return select_topk_dense(scores, (int64_t)(row / 4), nq, (int)N, k, out_scores, out_indices, st);
-  {
-    // k beyond the select's 1024: every row sorted in full, descending and stable (lower index first among equal scores,
-    // as jax.lax.top_k), by this file's radix sort over the complemented images, eight rows per launch sequence
-    char* p = base + row * nq;
-    int32_t* keys = (int32_t*)p;                                   // [8][row / 4]
-    int32_t* ksorted = (int32_t*)(p + row * kMaxSortBatch);        // [8][N] (not read)
-    int32_t* idx = (int32_t*)(p + 2 * row * kMaxSortBatch);        // [8][N]
-    char* sort_ws = p + 3 * row * kMaxSortBatch;
-    const size_t sort_ws_bytes = workspace_bytes - (size_t)(sort_ws - base);
-    for (int64_t q0 = 0; q0 < nq; q0 += kMaxSortBatch) {
-      const int nb = (int)std::min<int64_t>(kMaxSortBatch, nq - q0);
-      const dim3 kg((unsigned)std::min<int64_t>(1024, cdiv(N, kBlock)), nb);
-      hipLaunchKernelGGL(desc_keys_kernel, kg, dim3(kBlock), 0, st, (const float*)((char*)scores + row * q0),
-                         (int64_t)(row / 4), N, keys);
-      SortSegsBatch sb;
-      for (int b = 0; b < kMaxSortBatch; ++b) {
-        SortSegs& sg = sb.b[b];
-        sg.n = 1;
-        for (int i = 0; i < kMaxSortSegs; ++i) {
-          sg.ids[i] = i == 0 ? keys + (int64_t)std::min(b, nb - 1) * N : nullptr;
-          sg.offset[i] = 0;
-          sg.start[i + 1] = N;
-        }
-        sg.start[0] = 0;
-      }
-      if (nb > 1) {
-        launch_radix_sort_batched<11>(sb, nb, (int)N, 32, sort_ws, ksorted, idx, st);
-      } else if (int rc = segment_sort_segs("esr_score_topk", sb.b[0], N, (int64_t)1 << 32, ksorted, idx, sort_ws,
-                                            sort_ws_bytes, st)) {
-        return rc;
-      }
-      const dim3 tg((unsigned)cdiv(k, kBlock), nb);
-      hipLaunchKernelGGL(take_k_rows_kernel, tg, dim3(kBlock), 0, st, (const float*)((char*)scores + row * q0),
-                         (int64_t)(row / 4), (const int32_t*)idx, N, k, out_scores + q0 * k, out_indices + q0 * k);
-    }
-    return check_launch("esr_score_topk");
+  // k beyond the select's 1024: every row sorted in full, descending and stable (lower index first among equal scores,
+  // as jax.lax.top_k), by this file's radix sort over the complemented images, eight rows per launch sequence
+  char* p = base + row * nq;
+  int32_t* keys = (int32_t*)p;                             // [8][row / 4]
+  int32_t* ksorted = (int32_t*)(p + row * kMaxSortBatch);  // [8][N] (not read)
+  int32_t* idx = (int32_t*)(p + 2 * row * kMaxSortBatch);  // [8][N]
+  char* sort_ws = p + 3 * row * kMaxSortBatch;
+  const size_t sort_ws_bytes = workspace_bytes - (size_t)(sort_ws - base);
+  for (int64_t q0 = 0; q0 < nq; q0 += kMaxSortBatch) {
+    const int nb = (int)std::min<int64_t>(kMaxSortBatch, nq - q0);
+    const dim3 kg((unsigned)std::min<int64_t>(1024, cdiv(N, kBlock)), nb);
+    hipLaunchKernelGGL(desc_keys_kernel, kg, dim3(kBlock), 0, st, (const float*)((char*)scores + row * q0),
+                       (int64_t)(row / 4), N, keys);
+    if (int rc = sort_key_rows("esr_score_topk", keys, N, N, nb, ksorted, idx, sort_ws, sort_ws_bytes, st)) return rc;
+    const dim3 tg((unsigned)cdiv(k, kBlock), nb);
+    hipLaunchKernelGGL(take_k_rows_kernel, tg, dim3(kBlock), 0, st, (const float*)((char*)scores + row * q0),
+                       (int64_t)(row / 4), (const int32_t*)idx, N, k, out_scores + q0 * k, out_indices + q0 * k);
   }
+  return check_launch("esr_score_topk");
 }
 
 // ------------------------------------------------------------------------------------------------
+// the tiled path's counts of one list, in ints: [tiles][16 waves][8 owners] per wave + [tiles][8] per tile
+static int64_t bucket_tiled_cells(int64_t n) {
+  return cdiv(n, kBucketThreads) * (kBucketThreads / 64 + 1) * kBucketMaxWorld;
+}
+static size_t bucket_tiled_bytes(int64_t n) { return (size_t)bucket_tiled_cells(n) * sizeof(int); }
+static bool bucket_tiled_applies(int64_t n, int world) {
+  return n > 2048 && cdiv(n, kBucketThreads) <= kBucketTileMax && world <= kBucketMaxWorld;
+}
+
 // Workspace: the larger of the tiled path's counts and the radix path's key columns + sort workspace, behind a column
 // for the concatenated ids of the segmented entry point when it has to fall back to the radix path.
 size_t esr_bucket_workspace_bytes(int64_t n) {
   if (n <= 0) return 256;
-  const size_t tiled = (size_t)cdiv(n, kBucketThreads) * (kBucketThreads / 64 + 1) * kBucketMaxWorld * sizeof(int);
   return align_up((size_t)n * 4, 256) +
-         std::max(tiled, align_up((size_t)n * 4, 256) * 2 + radix_ws_layout(n, nullptr, nullptr));
+         std::max(bucket_tiled_bytes(n), align_up((size_t)n * 4, 256) * 2 + radix_ws_layout(n, nullptr, nullptr));
 }
 
 // tiled two-launch path; false when it does not apply (then nothing was launched)
 static bool bucket_tiled(const SortSegs& sg, int64_t n, int world, int32_t* local_rows, int32_t* perm, int32_t* inverse,
                          int64_t* counts, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  const int64_t ntiles = cdiv(n, kBucketThreads);
-  const size_t need = (size_t)ntiles * (kBucketThreads / 64 + 1) * kBucketMaxWorld * sizeof(int);
-  if (!(n > 2048 && ntiles <= kBucketTileMax && world <= kBucketMaxWorld && workspace && workspace_bytes >= need &&
+  if (!(bucket_tiled_applies(n, world) && workspace && workspace_bytes >= bucket_tiled_bytes(n) &&
         ((uintptr_t)workspace & 15) == 0))
     return false;
+  const int64_t ntiles = cdiv(n, kBucketThreads);
   int* wave_cells = (int*)workspace;
   int* tile_tot = wave_cells + ntiles * (kBucketThreads / 64) * kBucketMaxWorld;
   hipLaunchKernelGGL(bucket_count_kernel, dim3((int)ntiles), dim3(kBucketThreads), 0, st, sg, (int)n, world, wave_cells,
@@ -1438,22 +1449,22 @@ static bool bucket_tiled(const SortSegs& sg, int64_t n, int world, int32_t* loca
   return true;
 }
 
-// one-workgroup kernel (n <= 32768) or device radix sort; ids is one device array
+// one-workgroup kernel (n <= 32768) or device radix sort; ids is one device array.  `head`: the bytes of the caller's
+// workspace in front of `workspace` (the concatenated ids of the segmented entry point) -- what esr_bucket_workspace_bytes
+// states for n, less those, is what must be here
 static int bucket_plain(const char* who, const int32_t* ids, int64_t n, int world, int32_t* local_rows, int32_t* perm,
-                        int32_t* inverse, int64_t* counts, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                        int32_t* inverse, int64_t* counts, void* workspace, size_t workspace_bytes, size_t head,
+                        hipStream_t st) {
   if (n > 0 && n <= kBucketMaxN && world <= kBucketMaxWorld) {
     hipLaunchKernelGGL(bucket_small_kernel, dim3(1), dim3(kBucketThreads), 0, st, ids, (int)n, world, inverse,
                        local_rows, perm, counts);
     return check_launch(who);
   }
+  if (n > 0)
+    if (int rc = workspace_ok(who, workspace, workspace_bytes, esr_bucket_workspace_bytes(n) - head)) return rc;
   if (hipMemsetAsync(counts, 0, sizeof(int64_t) * world, st) != hipSuccess) return check_launch(who);
   if (n == 0) return ESR_OK;
   const size_t col = align_up((size_t)n * 4, 256);
-  const size_t need = 2 * col + radix_ws_layout(n, nullptr, nullptr);
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) {
-    set_error("%s: workspace %zu bytes < %zu required (or misaligned)", who, workspace_bytes, need);
-    return ESR_EWORKSPACE;
-  }
   char* base = (char*)workspace;
   uint32_t* keys = (uint32_t*)base;
   uint32_t* keys_sorted = (uint32_t*)(base + col);
@@ -1466,11 +1477,8 @@ static int bucket_plain(const char* who, const int32_t* ids, int64_t n, int worl
     set_error("%s: n=%lld ids exceed 2^30", who, (long long)n);
     return ESR_EINVAL;
   }
-  SortSegs ks = {};
-  ks.n = 1;
-  ks.ids[0] = reinterpret_cast<const int32_t*>(keys);
-  for (int i = 1; i <= kMaxSortSegs; ++i) ks.start[i] = n;
-  radix_any(ks, n, bits_for(world), base + 2 * col, reinterpret_cast<int32_t*>(keys_sorted), perm, st);
+  radix_any(one_seg(reinterpret_cast<const int32_t*>(keys), n), n, bits_for(world), base + 2 * col,
+            reinterpret_cast<int32_t*>(keys_sorted), perm, st);
   hipLaunchKernelGGL(local_rows_kernel, dim3(grid), dim3(kBlock), 0, st, ids, (const int32_t*)perm, n, world,
                      local_rows, inverse);
   return check_launch(who);
@@ -1484,14 +1492,10 @@ int esr_bucket_ids_by_owner(const int32_t* ids, int64_t n, int world, int32_t* l
   ESR_REQUIRE(counts, "esr_bucket_ids_by_owner: null counts");
   ESR_REQUIRE(n == 0 || (ids && local_rows && perm), "esr_bucket_ids_by_owner: null pointer");
   hipStream_t st = as_stream(stream);
-  SortSegs sg = {};
-  sg.n = 1;
-  sg.ids[0] = ids;
-  for (int i = 1; i <= kMaxSortSegs; ++i) sg.start[i] = n;
-  if (bucket_tiled(sg, n, world, local_rows, perm, inverse, counts, workspace, workspace_bytes, st))
+  if (bucket_tiled(one_seg(ids, n), n, world, local_rows, perm, inverse, counts, workspace, workspace_bytes, st))
     return check_launch("esr_bucket_ids_by_owner(tiled)");
   return bucket_plain("esr_bucket_ids_by_owner", ids, n, world, local_rows, perm, inverse, counts, workspace,
-                      workspace_bytes, st);
+                      workspace_bytes, 0, st);
 }
 
 int esr_bucket_ids_by_owner_multi(const int32_t* const* ids, const int64_t* seg_counts, const int64_t* offsets, int nseg,
@@ -1501,96 +1505,64 @@ int esr_bucket_ids_by_owner_multi(const int32_t* const* ids, const int64_t* seg_
               "esr_bucket_ids_by_owner_multi: nseg=%d not in [1, %d], world=%d or null argument", nseg, kMaxSortSegs,
               world);
   SortSegs sg;
-  sg.n = nseg;
-  sg.start[0] = 0;
-  for (int i = 0; i < kMaxSortSegs; ++i) {
-    ESR_REQUIRE(i >= nseg || (seg_counts[i] >= 0 && (seg_counts[i] == 0 || ids[i])),
-                "esr_bucket_ids_by_owner_multi: bad segment %d", i);
-    sg.ids[i] = i < nseg ? ids[i] : nullptr;
-    sg.offset[i] = i < nseg ? offsets[i] : 0;
-    sg.start[i + 1] = sg.start[i] + (i < nseg ? seg_counts[i] : 0);
-  }
-  const int64_t n = sg.start[nseg];
-  ESR_REQUIRE(n < ((int64_t)1 << 31), "esr_bucket_ids_by_owner_multi: n=%lld", (long long)n);
+  const int64_t n = fill_segs("esr_bucket_ids_by_owner_multi", &sg, ids, seg_counts, offsets, nseg);
+  if (n < 0) return ESR_EINVAL;
   ESR_REQUIRE(n == 0 || (local_rows && perm), "esr_bucket_ids_by_owner_multi: null pointer");
   hipStream_t st = as_stream(stream);
   if (bucket_tiled(sg, n, world, local_rows, perm, inverse, counts, workspace, workspace_bytes, st))
     return check_launch("esr_bucket_ids_by_owner_multi(tiled)");
   // the other paths want one array: materialise the virtual ids at the head of the workspace
-  const size_t col = align_up((size_t)std::max<int64_t>(n, 1) * 4, 256);
-  if (n > 0 && (!workspace || workspace_bytes < col || ((uintptr_t)workspace & 15))) {
-    set_error("esr_bucket_ids_by_owner_multi: workspace %zu bytes < %zu required (or misaligned)", workspace_bytes,
-              esr_bucket_workspace_bytes(n));
-    return ESR_EWORKSPACE;
-  }
+  const size_t col = align_up((size_t)n * 4, 256);
   int32_t* vids = (int32_t*)workspace;
-  if (n > 0)
+  if (n > 0) {
+    if (int rc = workspace_ok("esr_bucket_ids_by_owner_multi", workspace, workspace_bytes, col)) return rc;
     hipLaunchKernelGGL(concat_segs_kernel, dim3((int)std::min<int64_t>(kMaxGrid, cdiv(n, kBlock))), dim3(kBlock), 0, st, sg,
                        n, vids);
+  }
   return bucket_plain("esr_bucket_ids_by_owner_multi", vids, n, world, local_rows, perm, inverse, counts,
-                      n > 0 ? (char*)workspace + col : nullptr, n > 0 ? workspace_bytes - col : 0, st);
+                      (char*)workspace + col, workspace_bytes - col, col, st);
 }
 
 size_t esr_bucket_batched_workspace_bytes(int64_t n, int nbatch) {
   if (n <= 0 || nbatch <= 0) return 256;
-  const size_t tiled = (size_t)cdiv(n, kBucketThreads) * (kBucketThreads / 64 + 1) * kBucketMaxWorld * sizeof(int);
-  return std::max(esr_bucket_workspace_bytes(n), align_up((size_t)nbatch * tiled, 256));
+  return std::max(esr_bucket_workspace_bytes(n), align_up((size_t)nbatch * bucket_tiled_bytes(n), 256));
 }
 
 int esr_bucket_ids_by_owner_batched(const int32_t* const* ids, const int64_t* seg_counts, const int64_t* offsets,
                                     int nseg, int nbatch, int world, int32_t* local_rows, int32_t* perm,
                                     int32_t* inverse, int64_t* counts, void* workspace, size_t workspace_bytes,
                                     esr_stream_t stream) {
+  const char* who = "esr_bucket_ids_by_owner_batched";
   ESR_REQUIRE(nseg >= 1 && nseg <= kMaxSortSegs && nbatch >= 1 && nbatch <= kMaxSortBatch && ids && seg_counts &&
                   offsets && world > 0 && counts,
               "esr_bucket_ids_by_owner_batched: nseg=%d not in [1, %d], nbatch=%d not in [1, %d], world=%d or null "
               "argument", nseg, kMaxSortSegs, nbatch, kMaxSortBatch, world);
   SortSegsBatch sb;
-  int64_t n = 0;
-  for (int b = 0; b < nbatch; ++b) {
-    SortSegs& sg = sb.b[b];
-    sg.n = nseg;
-    sg.start[0] = 0;
-    for (int i = 0; i < kMaxSortSegs; ++i) {
-      const int32_t* src = i < nseg ? ids[(size_t)b * nseg + i] : nullptr;
-      ESR_REQUIRE(i >= nseg || (seg_counts[i] >= 0 && (seg_counts[i] == 0 || src)),
-                  "esr_bucket_ids_by_owner_batched: bad segment %d of list %d", i, b);
-      sg.ids[i] = src;
-      sg.offset[i] = i < nseg ? offsets[i] : 0;
-      sg.start[i + 1] = sg.start[i] + (i < nseg ? seg_counts[i] : 0);
-    }
-    n = sg.start[nseg];
-  }
-  for (int b = nbatch; b < kMaxSortBatch; ++b) sb.b[b] = sb.b[0];
-  ESR_REQUIRE(n < ((int64_t)1 << 31), "esr_bucket_ids_by_owner_batched: n=%lld", (long long)n);
+  const int64_t n = fill_batch(who, &sb, ids, seg_counts, offsets, nseg, nbatch);
+  if (n < 0) return ESR_EINVAL;
   ESR_REQUIRE(n == 0 || (local_rows && perm), "esr_bucket_ids_by_owner_batched: null pointer");
-  if (workspace_bytes < esr_bucket_batched_workspace_bytes(n, nbatch) || (n > 0 && (!workspace || ((uintptr_t)workspace & 15)))) {
-    set_error("esr_bucket_ids_by_owner_batched: workspace %zu bytes < %zu required (or misaligned)", workspace_bytes,
-              esr_bucket_batched_workspace_bytes(n, nbatch));
-    return ESR_EWORKSPACE;
-  }
+  const size_t need = esr_bucket_batched_workspace_bytes(n, nbatch);
+  if (n > 0 || workspace_bytes < need)  // (empty lists use no workspace: only its stated size is checked)
+    if (int rc = workspace_ok(who, workspace, workspace_bytes, need)) return rc;
   hipStream_t st = as_stream(stream);
-  const int64_t ntiles = cdiv(n, kBucketThreads);
-  if (n > 2048 && ntiles <= kBucketTileMax && world <= kBucketMaxWorld) {  // two launches for all the lists
-    const int64_t cells = ntiles * (kBucketThreads / 64 + 1) * kBucketMaxWorld;
+  if (bucket_tiled_applies(n, world)) {  // two launches for all the lists
+    const int64_t ntiles = cdiv(n, kBucketThreads);
     int* wave_cells = (int*)workspace;
     int* tile_tot = wave_cells + ntiles * (kBucketThreads / 64) * kBucketMaxWorld;
     hipLaunchKernelGGL(bucket_count_batched_kernel, dim3((int)ntiles, nbatch), dim3(kBucketThreads), 0, st, sb, (int)n,
-                       world, wave_cells, tile_tot, cells);
+                       world, wave_cells, tile_tot, bucket_tiled_cells(n));
     hipLaunchKernelGGL(bucket_scatter_batched_kernel, dim3((int)ntiles, nbatch), dim3(kBucketThreads), 0, st, sb, (int)n,
-                       world, (const int*)wave_cells, (const int*)tile_tot, cells, inverse, local_rows, perm, counts);
-    return check_launch("esr_bucket_ids_by_owner_batched");
+                       world, (const int*)wave_cells, (const int*)tile_tot, bucket_tiled_cells(n), inverse, local_rows,
+                       perm, counts);
+    return check_launch(who);
   }
-  for (int b = 0; b < nbatch; ++b) {  // short or very long lists: one after the other (the workspace is reused)
-    const int32_t* segs[kMaxSortSegs];
-    for (int i = 0; i < nseg; ++i) segs[i] = ids[(size_t)b * nseg + i];
-    if (int rc = esr_bucket_ids_by_owner_multi(segs, seg_counts, offsets, nseg, world, local_rows + (int64_t)b * n,
-                                               perm + (int64_t)b * n, inverse ? inverse + (int64_t)b * n : nullptr,
-                                               counts + (int64_t)b * world, workspace, workspace_bytes, stream))
+  for (int b = 0; b < nbatch; ++b)  // short or very long lists: one after the other (the workspace is reused)
+    if (int rc = esr_bucket_ids_by_owner_multi(ids + (size_t)b * nseg, seg_counts, offsets, nseg, world,
+                                               local_rows + (int64_t)b * n, perm + (int64_t)b * n,
+                                               inverse ? inverse + (int64_t)b * n : nullptr, counts + (int64_t)b * world,
+                                               workspace, workspace_bytes, stream))
       return rc;
-  }
   return ESR_OK;
 }
-
 
 }  // extern "C"

@@ -587,23 +587,36 @@ def segment_sort(ids, V, out=None):
     return sorted_ids, perm
 
 
+def _id_segments(id_tensors, offsets):
+    """The (ptrs, counts, offsets) host arrays that the sort and bucket entry points take for the virtual list
+    [ids_0 + offsets[0] ; ids_1 + offsets[1] ; ...].  Returns (ptrs, cnt, off, counts, n, device)."""
+    for t in id_tensors:
+        _req(t, torch.int32, "ids")
+    counts = [int(t.numel()) for t in id_tensors]
+    return ptr_array(id_tensors), i64_array(counts), i64_array(offsets), counts, sum(counts), id_tensors[0].device
+
+
+def _id_segments_batched(id_lists, offsets):
+    """_id_segments for the lists of several batches (same segment lengths in every batch): ptrs is the flattened
+    [batch][segment] array, the counts are one list's.  Returns (ptrs, cnt, off, counts, n, device)."""
+    counts = [int(t.numel()) for t in id_lists[0]]
+    for segs in id_lists:
+        if [int(t.numel()) for t in segs] != counts:
+            raise ValueError("every batch must have the same segment lengths")
+    ptrs, _, off, _, _, dev = _id_segments([t for segs in id_lists for t in segs], offsets)
+    return ptrs, i64_array(counts), off, counts, sum(counts), dev
+
+
 def segment_sort_multi(id_tensors, offsets, V):
     """Stable sort of the virtual list [ids_0 + offsets[0] ; ids_1 + offsets[1] ; ...] without materialising it.
     Returns (sorted virtual ids, perm)."""
     lib = _lib.load()
-    k = len(id_tensors)
-    for t in id_tensors:
-        _req(t, torch.int32, "ids")
-    counts = [int(t.numel()) for t in id_tensors]
-    n, dev = sum(counts), id_tensors[0].device
+    ptrs, cnt, off, counts, n, dev = _id_segments(id_tensors, offsets)
     sorted_ids = torch.empty(n, dtype=torch.int32, device=dev)
     perm = torch.empty(n, dtype=torch.int32, device=dev)
     ws = _ws(_ws_bytes("esr_segment_sort_workspace_bytes", n), dev)
-    ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in id_tensors])
-    cnt = (ctypes.c_int64 * k)(*counts)
-    off = (ctypes.c_int64 * k)(*[int(x) for x in offsets])
-    check(lib.esr_segment_sort_ids_multi(ptrs, cnt, off, k, V, _p(sorted_ids), _p(perm), _p(ws), ws.numel(), _stream()),
-          "esr_segment_sort_ids_multi")
+    check(lib.esr_segment_sort_ids_multi(ptrs, cnt, off, len(counts), V, _p(sorted_ids), _p(perm), _p(ws), ws.numel(),
+                                         _stream()), "esr_segment_sort_ids_multi")
     return sorted_ids, perm
 
 
@@ -1301,21 +1314,12 @@ def bucket_ids_by_owner_batched(id_lists, world, offsets):
     Returns (local_rows [L, n], perm [L, n], counts [L, world] int64, inverse [L, n])."""
     lib = _lib.load()
     nb, nseg = len(id_lists), len(id_lists[0])
-    dev = id_lists[0][0].device
-    seg_counts = [int(t.numel()) for t in id_lists[0]]
-    for segs in id_lists:
-        if len(segs) != nseg or [int(t.numel()) for t in segs] != seg_counts:
-            raise ValueError("every batch must have the same segment lengths")
-    id_lists = [[_req(t, torch.int32, "ids") for t in segs] for segs in id_lists]
-    n = sum(seg_counts)
+    ptrs, cnt, off, _, n, dev = _id_segments_batched(id_lists, offsets)
     local_rows = torch.empty((nb, n), dtype=torch.int32, device=dev)
     perm = torch.empty((nb, n), dtype=torch.int32, device=dev)
     inverse = torch.empty((nb, n), dtype=torch.int32, device=dev)
     counts = torch.empty((nb, world), dtype=torch.int64, device=dev)
     ws = _ws(_ws_bytes("esr_bucket_batched_workspace_bytes", n, nb), dev)
-    ptrs = (ctypes.c_void_p * (nb * nseg))(*[t.data_ptr() for segs in id_lists for t in segs])
-    cnt = (ctypes.c_int64 * nseg)(*seg_counts)
-    off = (ctypes.c_int64 * nseg)(*[int(x) for x in offsets])
     check(lib.esr_bucket_ids_by_owner_batched(ptrs, cnt, off, nseg, nb, int(world), _p(local_rows), _p(perm), _p(inverse),
                                               _p(counts), _p(ws), ws.numel(), _stream()),
           "esr_bucket_ids_by_owner_batched")
@@ -1329,22 +1333,13 @@ def segment_sort_batched(id_lists, offsets, num_rows, out=None):
     batch b alone.  out = (sorted_ids, perm, workspace) to reuse buffers."""
     lib = _lib.load()
     nb, nseg = len(id_lists), len(id_lists[0])
-    dev = id_lists[0][0].device
-    counts = [int(t.numel()) for t in id_lists[0]]
-    for segs in id_lists:
-        if len(segs) != nseg or [int(t.numel()) for t in segs] != counts:
-            raise ValueError("every batch must have the same segment lengths")
-    id_lists = [[_req(t, torch.int32, "ids") for t in segs] for segs in id_lists]
-    n = sum(counts)
+    ptrs, cnt, off, _, n, dev = _id_segments_batched(id_lists, offsets)
     if out is None:
         sorted_ids = torch.empty((nb, n), dtype=torch.int32, device=dev)
         perm = torch.empty((nb, n), dtype=torch.int32, device=dev)
         ws = _ws(_ws_bytes("esr_segment_sort_batched_workspace_bytes", n, nb), dev)
     else:
         sorted_ids, perm, ws = out
-    ptrs = (ctypes.c_void_p * (nb * nseg))(*[t.data_ptr() for segs in id_lists for t in segs])
-    cnt = (ctypes.c_int64 * nseg)(*counts)
-    off = (ctypes.c_int64 * nseg)(*[int(x) for x in offsets])
     check(lib.esr_segment_sort_ids_batched(ptrs, cnt, off, nseg, nb, int(num_rows), _p(sorted_ids), _p(perm), _p(ws),
                                            ws.numel(), _stream()), "esr_segment_sort_ids_batched")
     return sorted_ids, perm
@@ -1361,9 +1356,7 @@ def bucket_ids_by_owner(ids, world, want_inverse=False, offsets=None, counts_out
         ids = _req(ids, torch.int32, "ids")
         n, dev = ids.numel(), ids.device
     else:
-        for t in segs:
-            _req(t, torch.int32, "ids")
-        n, dev = sum(int(t.numel()) for t in segs), segs[0].device
+        ptrs, cnt, off, _, n, dev = _id_segments(segs, offsets if offsets is not None else [0] * len(segs))
     local_rows = torch.empty(n, dtype=torch.int32, device=dev)
     perm = torch.empty(n, dtype=torch.int32, device=dev)
     inverse = torch.empty(n, dtype=torch.int32, device=dev) if want_inverse else None
@@ -1378,11 +1371,7 @@ def bucket_ids_by_owner(ids, world, want_inverse=False, offsets=None, counts_out
         check(lib.esr_bucket_ids_by_owner(_p(ids), n, world, _p(local_rows), _p(perm), _p(inverse), _p(counts), _p(ws),
                                           ws.numel(), _stream()), "esr_bucket_ids_by_owner")
     else:
-        k = len(segs)
-        ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in segs])
-        cnt = (ctypes.c_int64 * k)(*[int(t.numel()) for t in segs])
-        off = (ctypes.c_int64 * k)(*[int(x) for x in (offsets if offsets is not None else [0] * k)])
-        check(lib.esr_bucket_ids_by_owner_multi(ptrs, cnt, off, k, world, _p(local_rows), _p(perm), _p(inverse),
+        check(lib.esr_bucket_ids_by_owner_multi(ptrs, cnt, off, len(segs), world, _p(local_rows), _p(perm), _p(inverse),
                                                 _p(counts), _p(ws), ws.numel(), _stream()),
               "esr_bucket_ids_by_owner_multi")
     if want_inverse:
