@@ -210,6 +210,9 @@ SIGNATURES = {
     "esr_cooccur_rehash": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
     "esr_cooccur_finalize_workspace_bytes": (c_size, [c_i64]),
     "esr_cooccur_finalize": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_i32p, c_i32p, c_f32p, c_vp, c_size, c_vp]),
+    "esr_dice_max_doc": (c_int, []),
+    "esr_dice_workspace_bytes": (c_size, [c_i64]),
+    "esr_dice_accumulate": (c_int, [c_i32p, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_size, c_vp]),
 }
 
 

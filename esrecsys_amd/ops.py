@@ -1536,3 +1536,24 @@ def cooccur_finalize(table, capacity, nnz, num_ids, context_window):
     check(lib.esr_cooccur_finalize(_p(table), int(capacity), int(nnz), int(num_ids), int(context_window), _p(index),
                                    _p(other), _p(count), _p(ws), ws.numel(), _stream()), "esr_cooccur_finalize")
     return index, other, count
+
+
+# ---------------------------------------------------------------------------------------------
+# set co-occurrence (Dice) builder (esr_dice.hip): it fills the pair table of the co-occurrence builder above
+def dice_max_doc():
+    """Ids a document may hold (esr_dice.hip sorts a document in LDS)."""
+    return int(_lib.load().esr_dice_max_doc())
+
+
+def dice_workspace(n_indices, device):
+    """The workspace of dice_accumulate for an index array of n_indices ids."""
+    return _ws(_ws_bytes("esr_dice_workspace_bytes", int(n_indices)), device)
+
+
+def dice_accumulate(table, capacity, indices, doc_offsets, doc_begin, doc_end, workspace):
+    """Adds the set pairs (and the document frequencies, on the diagonal keys) of documents [doc_begin, doc_end)."""
+    lib = _lib.load()
+    _req(indices, torch.int32, "indices"), _req(doc_offsets, torch.int64, "doc_offsets")
+    check(lib.esr_dice_accumulate(_p(indices), indices.numel(), _p(doc_offsets), doc_offsets.numel() - 1,
+                                  int(doc_begin), int(doc_end), _p(table), int(capacity), _p(workspace),
+                                  workspace.numel(), _stream()), "esr_dice_accumulate")

@@ -859,7 +859,8 @@ int esr_sharded_glove_step_overlapped(const esr_shard_group_t* emb, const esr_sh
  * calls; 1 <= W <= 22.
  * The table is device memory of esr_cooccur_table_bytes(capacity) bytes, 16-byte aligned, capacity a power of two >= 2:
  * a 256-byte header -- uint64 word 0: occupied slots, word 1: failure bits (1: a probe wrapped the whole table, 2: a
- * negative token id, 4: doc_offsets[0] / doc_offsets[ndocs] outside [0, N], 8: finalize's nnz below the table's) --
+ * negative token id, 4: doc_offsets[0] / doc_offsets[ndocs] outside [0, N], 8: finalize's nnz below the table's, 16:
+ * esr_dice_accumulate met a document above esr_dice_max_doc()) --
  * then keys uint64[capacity] (index << 32 | other, all ones = empty) and sums uint64[capacity].  The caller reads the
  * header and must keep capacity >= occupied + (tok_end - tok_begin) * W before a call: a full table raises failure bit 1,
  * it never spins and never drops an increment silently.
@@ -880,6 +881,24 @@ size_t esr_cooccur_finalize_workspace_bytes(int64_t nnz);
 int esr_cooccur_finalize(void* table, int64_t capacity, int64_t nnz, int64_t num_ids, int context_window,
                          int32_t* index, int32_t* other, float* count, void* workspace, size_t workspace_bytes,
                          esr_stream_t stream);
+
+/* ---- Set co-occurrence (Dice) matrix from id sets (esr_dice.hip; the reference's wikipedia/make_dice.py) ----
+ * A document is the SET of indices[doc_offsets[d] .. doc_offsets[d + 1]); with u = its sorted distinct ids every i < j adds
+ * 1 to the entry (index = u[i], other = u[j]) of an esr_cooccur_* pair table -- index < other, the opposite orientation to
+ * the windowed matrix -- and every distinct id adds 1 to the diagonal key id << 32 | id, which no pair makes: the number
+ * of documents that hold the id.  Counts are uint64: nothing depends on the order of the atomics or on how the documents
+ * are cut into calls.  esr_cooccur_rehash grows the table; esr_cooccur_finalize with context_window = 1 returns pairs and
+ * diagonal together, ascending by (index, other), count = (float)sum.
+ *   accumulate  the documents [doc_begin, doc_end) of doc_offsets int64[ndocs + 1] (CSR over indices int32[N] >= 0, device
+ *               memory; empty documents allowed), at most 2^31 - 1 of them.  The caller keeps capacity >= occupied +
+ *               sum over those documents of n (n - 1) / 2 + n (n = the document's length).  A document longer than
+ *               esr_dice_max_doc() (its sort lives in LDS) raises failure bit 16 and adds nothing: check lengths on the host.
+ *               workspace: esr_dice_workspace_bytes(N) bytes, 16-byte aligned (the work list of the long documents). */
+int esr_dice_max_doc(void);
+size_t esr_dice_workspace_bytes(int64_t N);
+int esr_dice_accumulate(const int32_t* indices, int64_t N, const int64_t* doc_offsets, int64_t ndocs,
+                        int64_t doc_begin, int64_t doc_end, void* table, int64_t capacity, void* workspace,
+                        size_t workspace_bytes, esr_stream_t stream);
 
 #ifdef __cplusplus
 }
