@@ -375,6 +375,39 @@ __device__ __forceinline__ float row_dot_partial(const RowRegs<VEC, NCH>& a, con
     for (int e = 0; e < VEC; ++e) acc = fmaf(a.v[k][e], b.v[k][e], acc);
   return acc;
 }
+// Element-wise row arithmetic.  RN picks the spelling of the addition: `+` (the segment kernels) or __fadd_rn (the triplet
+// step's direct mode).  hipcc compiles both to the same add (see the NOTE above); every site keeps the form it had.
+template <int VEC, int NCH>
+__device__ __forceinline__ void row_zero(RowRegs<VEC, NCH>& r) {
+#pragma unroll
+  for (int k = 0; k < NCH; ++k)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) r.v[k][e] = 0.f;
+}
+template <bool RN = false, int VEC, int NCH>
+__device__ __forceinline__ void row_add(RowRegs<VEC, NCH>& acc, const RowRegs<VEC, NCH>& t) {
+#pragma unroll
+  for (int k = 0; k < NCH; ++k)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      if constexpr (RN) acc.v[k][e] = __fadd_rn(acc.v[k][e], t.v[k][e]);
+      else acc.v[k][e] += t.v[k][e];
+    }
+}
+// (((acc + t0) + t1) + t2) + t3: four rows loaded together, added strictly in order
+template <bool RN = false, int VEC, int NCH>
+__device__ __forceinline__ void row_add4(RowRegs<VEC, NCH>& acc, const RowRegs<VEC, NCH>& t0, const RowRegs<VEC, NCH>& t1,
+                                         const RowRegs<VEC, NCH>& t2, const RowRegs<VEC, NCH>& t3) {
+#pragma unroll
+  for (int k = 0; k < NCH; ++k)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      if constexpr (RN)
+        acc.v[k][e] = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(acc.v[k][e], t0.v[k][e]), t1.v[k][e]), t2.v[k][e]), t3.v[k][e]);
+      else
+        acc.v[k][e] = (((acc.v[k][e] + t0.v[k][e]) + t1.v[k][e]) + t2.v[k][e]) + t3.v[k][e];
+    }
+}
 
 // optax.adagrad [upstream]: acc += g^2 ; p -= lr * g * rsqrt(acc + eps)  (0 where acc == 0).  ONE definition for every
 // kernel that applies it (esr_optim.hip, esr_glove_step.hip), so their results are bit-identical.
@@ -384,6 +417,15 @@ __device__ __forceinline__ void adagrad_elem(float& w, float& a, float gv, float
   a = acc;
   const float inv = acc > 0.f ? __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(acc, eps))) : 0.f;
   w = __fsub_rn(w, __fmul_rn(__fmul_rn(lr, gv), inv));
+}
+// a whole row: w, a = the row and its accumulator, g = its summed gradient
+template <int VEC, int NCH>
+__device__ __forceinline__ void row_adagrad(RowRegs<VEC, NCH>& w, RowRegs<VEC, NCH>& a, const RowRegs<VEC, NCH>& g, float lr,
+                                            float eps) {
+#pragma unroll
+  for (int k = 0; k < NCH; ++k)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) adagrad_elem(w.v[k][e], a.v[k][e], g.v[k][e], lr, eps);
 }
 
 // One element of a Shop-The-Look gradient row: (a x + c own) / B with a = +-[margin > 0], x = the

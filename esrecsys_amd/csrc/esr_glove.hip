@@ -428,10 +428,7 @@ __device__ __forceinline__ void step_apply(TR* __restrict__ emb0, TR* __restrict
                                            float eps) {
   const int64_t id = code & kIdMask;
   RowRegs<VEC, NCH> w = own;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k)
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) adagrad_elem(w.v[k][e], a.v[k][e], g.v[k][e], lr, eps);
+  row_adagrad(w, a, g, lr, eps);
   row_store(a, accum + id * D, lig, G, nvec);
   row_store(w, ((code & kLocBit) ? emb0 : emb1) + id * D, lig, G, nvec);
   if (lig == 0) loc[id] = loc_written((code & kLocBit) ? 0u : 1u, T);
@@ -872,10 +869,7 @@ __device__ __forceinline__ void step_apply_resolved(TR* __restrict__ emb0, TR* _
                                            int nvec, float lr, float eps) {
   const int64_t id = code & kIdMask;
   RowRegs<VEC, NCH> w = own;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k)
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) adagrad_elem(w.v[k][e], a.v[k][e], g.v[k][e], lr, eps);
+  row_adagrad(w, a, g, lr, eps);
   row_store(a, accum + id * D, lig, G, nvec);
   row_store(w, ((code & kLocBit) ? emb0 : emb1) + id * D, lig, G, nvec);
   if (lig == 0) loc[id] = (code & kLocBit) ? 0 : 1;
@@ -1062,106 +1056,34 @@ __global__ __launch_bounds__(kBlock) void glove_step_long_kernel(
   }
   // no run of the batch outgrew its head chunk: nothing to combine -- one load instead of screening the chunk boundaries
   if (*parked == 0) return;
-  __shared__ float red[kBlock * VEC * NCH];
   __shared__ double smd[8];
-  constexpr int kPass = 4;
-  __shared__ long long s_long[kPass];
-  __shared__ int s_nlong, s_hoff;
-  const int tid = threadIdx.x, lig = tid & (G - 1), gidx = tid / G, NG = kBlock / G;
-  const int nvec = D / VEC;
-  auto id_at = [&](int64_t pos) { return (uint32_t)sorted_ids[pos]; };
-  const int64_t nbound = (n - 1) / kStepChunk;
-  for (int64_t b0 = (int64_t)blockIdx.x * kPass; b0 < nbound; b0 += (int64_t)gridDim.x * kPass) {
-    __syncthreads();
-    if (tid == 0) s_nlong = 0;
-    __syncthreads();
-    {
-      const int64_t Bd = (b0 + tid + 1) * kStepChunk;
-      if (tid < kPass && b0 + tid < nbound) {
-        const uint32_t id_b = id_at(Bd);
-        const bool first = Bd < 2 * kStepChunk || id_at(Bd - 2 * kStepChunk) != id_b;
-        if (id_at(Bd - kStepChunk) == id_b && first) s_long[atomicAdd(&s_nlong, 1)] = Bd;
-      }
-    }
-    __syncthreads();
-    const int nlong = s_nlong;
-    for (int li = 0; li < nlong; ++li) {
-      const int64_t nxt = s_long[li];
-      const uint32_t id = id_at(nxt);
-      const int64_t win = max<int64_t>(nxt - 2 * kStepChunk + 1, 0);
-      if (tid < 64) {
-        const int64_t pos = win + tid;
-        const bool is_head = pos <= nxt - kStepChunk && id_at(pos) == id && (pos == 0 || id_at(pos - 1) != id);
-        const unsigned long long m = __ballot(is_head);
-        if (tid == 0) s_hoff = __ffsll((long long)m) - 1;
-      }
-      __syncthreads();
-      const int64_t h = win + s_hoff;
-      int64_t K = 0;  // continuation chunks
-      for (int64_t k0 = 0;; k0 += kBlock) {
-        const int64_t pos = nxt + (k0 + tid) * kStepChunk;
-        const int cnt = __syncthreads_count(pos < n && id_at(pos) == id);
-        K += cnt;
-        if (cnt < kBlock) break;
-      }
-      auto part_row = [&](int64_t i) {
-        return (i == 0 ? 2 * (h / kStepChunk) + 1 : 2 * ((nxt + (i - 1) * kStepChunk) / kStepChunk)) * (int64_t)D;
-      };
-      auto part_pos = [&](int64_t i) { return i == 0 ? h : nxt + (i - 1) * kStepChunk; };
-      RowRegs<VEC, NCH> acc;
-      row_zero(acc);
-      int64_t i = gidx;
-      for (; i + 3 * NG <= K; i += 4 * NG) {
-        RowRegs<VEC, NCH> t0, t1, t2, t3;
-        row_load(t0, chunk_rows + part_row(i), lig, G, nvec);
-        row_load(t1, chunk_rows + part_row(i + NG), lig, G, nvec);
-        row_load(t2, chunk_rows + part_row(i + 2 * NG), lig, G, nvec);
-        row_load(t3, chunk_rows + part_row(i + 3 * NG), lig, G, nvec);
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-          for (int e = 0; e < VEC; ++e)
-            acc.v[k][e] = (((acc.v[k][e] + t0.v[k][e]) + t1.v[k][e]) + t2.v[k][e]) + t3.v[k][e];
-      }
-      for (; i <= K; i += NG) {
-        RowRegs<VEC, NCH> t;
-        row_load(t, chunk_rows + part_row(i), lig, G, nvec);
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) acc.v[k][e] += t.v[k][e];
-      }
-#pragma unroll
-      for (int k = 0; k < NCH; ++k)
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) red[((gidx * G + lig) * NCH + k) * VEC + e] = acc.v[k][e];
-      // the run's bias sums: chunk entries added in a fixed tree (fp64 carries them exactly enough to be order-free)
-      double bs = 0.0, bc = 0.0;
-      for (int64_t c = tid; c <= K; c += kBlock) {
-        const double2 v = bias_info[part_pos(c)];
-        bs += v.x;
-        bc += v.y;
-      }
-      const double tbs = block_sum_d(bs, smd);  // (its barriers also publish `red`)
-      const double tbc = block_sum_d(bc, smd + 4);
-      if (tid == 0) bias_info[h] = make_double2(tbs, tbc);
-      if (gidx == 0) {
-        const int used = (int)min<int64_t>(NG, K + 1);
-        for (int gg = 1; gg < used; ++gg)
-#pragma unroll
-          for (int k = 0; k < NCH; ++k)
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc.v[k][e] += red[((gg * G + lig) * NCH + k) * VEC + e];
+  const int lig = threadIdx.x & (G - 1);
+  combine_long_runs<VEC, NCH, kStepChunk>(
+      sorted_ids, n, D, G,
+      // partial 0 sits in the odd slot of the head's chunk, partial i >= 1 in the even slot of its own
+      [&](int64_t h, int64_t nxt, int64_t i) {
+        return chunk_rows + (i == 0 ? 2 * (h / kStepChunk) + 1 : 2 * ((nxt + (i - 1) * kStepChunk) / kStepChunk)) * (int64_t)D;
+      },
+      [&](int32_t id, int64_t, int64_t, int64_t, const RowRegs<VEC, NCH>& acc) {
         // (nobody has rewritten this row during the step: its head parked its partial instead)
-        const uint32_t code = id | (loc_at_step_begin(loc[id], T) ? kLocBit : 0u);
+        const uint32_t code = (uint32_t)id | (loc_at_step_begin(loc[id], T) ? kLocBit : 0u);
         RowRegs<VEC, NCH> own, a;
-        row_load(own, ((code & kLocBit) ? emb1 : emb0) + (int64_t)id * D, lig, G, nvec);
-        row_load(a, accum + (int64_t)id * D, lig, G, nvec);
-        step_apply<VEC, NCH, TR>(emb0, emb1, loc, accum, code, T, own, a, acc, D, lig, G, nvec, lr, eps);
-      }
-      __syncthreads();
-    }
-  }
+        row_load(own, ((code & kLocBit) ? emb1 : emb0) + (int64_t)id * D, lig, G, D / VEC);
+        row_load(a, accum + (int64_t)id * D, lig, G, D / VEC);
+        step_apply<VEC, NCH, TR>(emb0, emb1, loc, accum, code, T, own, a, acc, D, lig, G, D / VEC, lr, eps);
+      },
+      // the run's bias sums: chunk entries added in a fixed tree (fp64 carries them exactly enough to be order-free)
+      [&](int64_t h, int64_t nxt, int64_t K) {
+        double bs = 0.0, bc = 0.0;
+        for (int64_t c = threadIdx.x; c <= K; c += kBlock) {
+          const double2 v = bias_info[long_part_pos(h, nxt, c, kStepChunk)];
+          bs += v.x;
+          bc += v.y;
+        }
+        const double tbs = block_sum_d(bs, smd);  // (its barriers also publish the group sums)
+        const double tbc = block_sum_d(bc, smd + 4);
+        if (threadIdx.x == 0) bias_info[h] = make_double2(tbs, tbc);
+      });
 }
 
 // finalize: the loss (same formula as glove_finalize_kernel) and the bias table's Adagrad step, one thread per sorted

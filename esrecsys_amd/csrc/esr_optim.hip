@@ -274,6 +274,7 @@ __global__ __launch_bounds__(kBlock) void segment_update_kernel(FusedTables ft, 
 // per boundary; in a batch without hot rows that is all this kernel does).  A workgroup then combines one run at a
 // time: its row groups sum the run's chunk partials round-robin, the group sums are added in group order through
 // LDS, and the row is updated once.  Fixed association: the result does not depend on scheduling.
+// (combine_long_runs in esr_segment.h is this body as a template, for the one-pass steps: keep the two alike.)
 template <int VEC, int NCH, int OP>
 __global__ __launch_bounds__(kBlock) void segment_long_kernel(FusedTables ft, int dtype, int D, int G,
                                                              const int32_t* __restrict__ sorted_ids,

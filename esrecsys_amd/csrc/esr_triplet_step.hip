@@ -75,7 +75,8 @@ struct TripPlan {
   int32_t* long_heads;          // [n / 9 + 1]  direct mode: head positions of the runs longer than kDirectMaxRun
   double* loss_part;            // [kMaxGrid]  direct mode: the update kernel's loss partial per workgroup
 };
-static size_t trip_plan_layout(int64_t B, char* base, TripPlan* out) {
+// the one place that knows where a plan's fields are (host: sizes and launch arguments; device: the plan kernels)
+__host__ __device__ static size_t trip_plan_layout(int64_t B, char* base, TripPlan* out) {
   const int64_t n = 3 * B;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -146,10 +147,11 @@ __global__ __launch_bounds__(kBlock) void triplet_plan_kernel(PlanBatch pb, cons
   const int32_t* __restrict__ scene_ids = pb.scene[list];
   const int32_t* __restrict__ pos_ids = pb.pos[list];
   const int32_t* __restrict__ neg_ids = pb.neg[list];
-  char* base = plans + (size_t)list * plan_stride;
-  int* flags = (int*)base;
-  unsigned long long* loss_acc = (unsigned long long*)(base + 256);
-  uint2* meta = (uint2*)(base + 256 + align_up(sizeof(unsigned long long) * kFixAccWords, 256));
+  TripPlan pl;
+  trip_plan_layout(B, plans + (size_t)list * plan_stride, &pl);
+  int* const flags = pl.flags;
+  unsigned long long* const loss_acc = pl.loss_acc;
+  uint2* const meta = pl.meta;
   if (blockIdx.x == 0) {
     if (threadIdx.x < 64) flags[threadIdx.x] = 0;
     for (int i = threadIdx.x; i < kFixAccWords; i += kBlock) loss_acc[i] = 0ull;
@@ -174,10 +176,7 @@ __device__ __forceinline__ void step_apply2(const TwoTowers& tt, uint32_t code, 
   const bool prod = vid >= tt.Vs, second = (code & kLocBit) != 0;
   const int64_t id = prod ? vid - tt.Vs : vid;
   RowRegs<VEC, NCH> w = own;
-#pragma unroll
-  for (int k = 0; k < NCH; ++k)
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) adagrad_elem(w.v[k][e], a.v[k][e], g.v[k][e], lr, eps);
+  row_adagrad(w, a, g, lr, eps);
   row_store(a, (prod ? tt.pacc : tt.sacc) + id * D, lig, G, nvec);
   float* dst = prod ? (second ? tt.p0 : tt.p1) : (second ? tt.s0 : tt.s1);  // the OTHER buffer
   row_store(w, dst + id * D, lig, G, nvec);
@@ -385,95 +384,21 @@ __global__ __launch_bounds__(kBlock) void triplet_step_long_kernel(TwoTowers tt,
   // no run of the batch outgrew its head chunk (every batch of uniform ids): nothing to combine -- one load instead of
   // the screening of the chunk boundaries (three dependent loads and three barriers per workgroup)
   if (*parked == 0) return;
-  __shared__ float red[kBlock * VEC * NCH];
-  constexpr int kPass = 4;
-  __shared__ long long s_long[kPass];
-  __shared__ int s_nlong, s_hoff;
-  const int tid = threadIdx.x, lig = tid & (G - 1), gidx = tid / G, NG = kBlock / G;
-  const int nvec = D / VEC;
-  auto id_at = [&](int64_t pos) { return (uint32_t)sorted_ids[pos]; };
-  const int64_t nbound = (n - 1) / kTripChunk;
-  for (int64_t b0 = (int64_t)blockIdx.x * kPass; b0 < nbound; b0 += (int64_t)gridDim.x * kPass) {
-    __syncthreads();
-    if (tid == 0) s_nlong = 0;
-    __syncthreads();
-    {
-      const int64_t Bd = (b0 + tid + 1) * kTripChunk;
-      if (tid < kPass && b0 + tid < nbound) {
-        const uint32_t id_b = id_at(Bd);
-        const bool first = Bd < 2 * kTripChunk || id_at(Bd - 2 * kTripChunk) != id_b;
-        if (id_at(Bd - kTripChunk) == id_b && first) s_long[atomicAdd(&s_nlong, 1)] = Bd;
-      }
-    }
-    __syncthreads();
-    const int nlong = s_nlong;
-    for (int li = 0; li < nlong; ++li) {
-      const int64_t nxt = s_long[li];
-      const uint32_t id = id_at(nxt);
-      const int64_t win = max<int64_t>(nxt - 2 * kTripChunk + 1, 0);
-      if (tid < 64) {
-        const int64_t pos = win + tid;
-        const bool is_head = pos <= nxt - kTripChunk && id_at(pos) == id && (pos == 0 || id_at(pos - 1) != id);
-        const unsigned long long m = __ballot(is_head);
-        if (tid == 0) s_hoff = __ffsll((long long)m) - 1;
-      }
-      __syncthreads();
-      const int64_t h = win + s_hoff;
-      int64_t K = 0;
-      for (int64_t k0 = 0;; k0 += kBlock) {
-        const int64_t pos = nxt + (k0 + tid) * kTripChunk;
-        const int cnt = __syncthreads_count(pos < n && id_at(pos) == id);
-        K += cnt;
-        if (cnt < kBlock) break;
-      }
-      auto part_row = [&](int64_t i) {
-        return (i == 0 ? 2 * (h / kTripChunk) + 1 : 2 * ((nxt + (i - 1) * kTripChunk) / kTripChunk)) * (int64_t)D;
-      };
-      RowRegs<VEC, NCH> acc;
-      row_zero(acc);
-      int64_t i = gidx;
-      for (; i + 3 * NG <= K; i += 4 * NG) {
-        RowRegs<VEC, NCH> t0, t1, t2, t3;
-        row_load(t0, chunk_rows + part_row(i), lig, G, nvec);
-        row_load(t1, chunk_rows + part_row(i + NG), lig, G, nvec);
-        row_load(t2, chunk_rows + part_row(i + 2 * NG), lig, G, nvec);
-        row_load(t3, chunk_rows + part_row(i + 3 * NG), lig, G, nvec);
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-          for (int e = 0; e < VEC; ++e)
-            acc.v[k][e] = (((acc.v[k][e] + t0.v[k][e]) + t1.v[k][e]) + t2.v[k][e]) + t3.v[k][e];
-      }
-      for (; i <= K; i += NG) {
-        RowRegs<VEC, NCH> t;
-        row_load(t, chunk_rows + part_row(i), lig, G, nvec);
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) acc.v[k][e] += t.v[k][e];
-      }
-#pragma unroll
-      for (int k = 0; k < NCH; ++k)
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) red[((gidx * G + lig) * NCH + k) * VEC + e] = acc.v[k][e];
-      __syncthreads();
-      if (gidx == 0) {
-        const int used = (int)min<int64_t>(NG, K + 1);
-        for (int gg = 1; gg < used; ++gg)
-#pragma unroll
-          for (int k = 0; k < NCH; ++k)
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc.v[k][e] += red[((gg * G + lig) * NCH + k) * VEC + e];
+  const int lig = threadIdx.x & (G - 1);
+  combine_long_runs<VEC, NCH, kTripChunk>(
+      sorted_ids, n, D, G,
+      // partial 0 sits in the odd slot of the head's chunk, partial i >= 1 in the even slot of its own
+      [&](int64_t h, int64_t nxt, int64_t i) {
+        return chunk_rows + (i == 0 ? 2 * (h / kTripChunk) + 1 : 2 * ((nxt + (i - 1) * kTripChunk) / kTripChunk)) * (int64_t)D;
+      },
+      [&](int32_t id, int64_t, int64_t, int64_t, const RowRegs<VEC, NCH>& acc) {
         // (nobody has rewritten this row during the step: its head parked its partial instead)
-        const uint32_t code = code_of(id, loc_byte(tt, id), tt.stamp);
+        const uint32_t code = code_of((uint32_t)id, loc_byte(tt, (uint32_t)id), tt.stamp);
         RowRegs<VEC, NCH> own, a;
-        row_load(own, tower_row(tt, code, D), lig, G, nvec);
-        row_load(a, tower_acc(tt, id, D), lig, G, nvec);
-        step_apply2<VEC, NCH>(tt, code, own, a, acc, D, lig, G, nvec, lr, eps);
-      }
-      __syncthreads();
-    }
-  }
+        row_load(own, tower_row(tt, code, D), lig, G, D / VEC);
+        row_load(a, tower_acc(tt, (uint32_t)id, D), lig, G, D / VEC);
+        step_apply2<VEC, NCH>(tt, code, own, a, acc, D, lig, G, D / VEC, lr, eps);
+      });
 }
 
 // clear the stamps of a location array (bit 0 stays): 16 bytes per thread
@@ -527,15 +452,13 @@ __global__ __launch_bounds__(kBlock) void triplet_direct_plan_kernel(const int32
   const int64_t n = 3 * B;
   const int32_t* __restrict__ sorted = sorted_all + (int64_t)list * n;
   const int32_t* __restrict__ perm = perm_all + (int64_t)list * n;
-  char* base = plans + (size_t)list * plan_stride;
-  int* flags = (int*)base;
-  unsigned long long* loss_acc = (unsigned long long*)(base + 256);
-  char* q = base + 256 + align_up(sizeof(unsigned long long) * kFixAccWords, 256);
-  uint2* code = (uint2*)q;
-  q += align_up(sizeof(uint2) * (size_t)n, 256);
-  uint32_t* cnt = (uint32_t*)q;
-  q += align_up(sizeof(uint32_t) * (size_t)n, 256);
-  int32_t* long_heads = (int32_t*)q;
+  TripPlan pl;
+  trip_plan_layout(B, plans + (size_t)list * plan_stride, &pl);
+  int* const flags = pl.flags;
+  unsigned long long* const loss_acc = pl.loss_acc;
+  uint2* const code = pl.meta;
+  uint32_t* const cnt = pl.cnt;
+  int32_t* const long_heads = pl.long_heads;
   if (blockIdx.x == 0) {
     // (flags[2..3], the generation-tagged long-run count, is claimed by whichever workgroup finds the first long run)
     if (threadIdx.x < 64 && (threadIdx.x >> 1) != 1) flags[threadIdx.x] = 0;
@@ -727,10 +650,7 @@ __global__ __launch_bounds__(kBlock) void triplet_direct_kernel(DirectTowers<T> 
     // that completed its run sum it.
     auto step_here = [&](T* row, float* accrow, RowRegs<VEC, NCH>& own, RowRegs<VEC, NCH>& a,
                          const RowRegs<VEC, NCH>& g) {
-#pragma unroll
-      for (int k = 0; k < NCH; ++k)
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) adagrad_elem(own.v[k][e], a.v[k][e], g.v[k][e], lr, eps);
+      row_adagrad(own, a, g, lr, eps);
       row_store(a, accrow, lig, G, nvec);
       row_store(own, row, lig, G, nvec);
     };
@@ -774,10 +694,7 @@ __global__ __launch_bounds__(kBlock) void triplet_direct_kernel(DirectTowers<T> 
         for (uint32_t j = 0; j < len; ++j) {
           RowRegs<VEC, NCH> t;
           side_load(t, side + (head + j) * D, lig, G, nvec);
-#pragma unroll
-          for (int k = 0; k < NCH; ++k)
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) sum.v[k][e] = __fadd_rn(sum.v[k][e], t.v[k][e]);
+          row_add<true>(sum, t);
         }
         // every arrival of the run has been counted (this one completed it): the counter goes back to zero, so the plan
         // can feed another step (the same batch stepped again: ops.triplet_train_step(plan=...))
@@ -820,7 +737,6 @@ __global__ __launch_bounds__(kBlock) void triplet_direct_long_kernel(DirectTower
                                                                     const int* __restrict__ flags,
                                                                     const int32_t* __restrict__ long_heads) {
   if (flags[0] == 0) return;  // nothing was parked
-  __shared__ float red[kBlock * VEC * NCH];
   const int tid = threadIdx.x, lig = tid & (G - 1), gidx = tid / G, NG = kBlock / G;
   const int nvec = D / VEC;
   // (generation << 32 | count in flags[2..3]: something was parked, so the count is this plan's)
@@ -853,37 +769,16 @@ __global__ __launch_bounds__(kBlock) void triplet_direct_long_kernel(DirectTower
         row_load(t1, side + (q + 1) * D, lig, G, nvec);
         row_load(t2, side + (q + 2) * D, lig, G, nvec);
         row_load(t3, side + (q + 3) * D, lig, G, nvec);
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-          for (int e = 0; e < VEC; ++e)
-            c.v[k][e] = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(c.v[k][e], t0.v[k][e]), t1.v[k][e]), t2.v[k][e]), t3.v[k][e]);
+        row_add4<true>(c, t0, t1, t2, t3);
       }
       for (; q < q1; ++q) {
         RowRegs<VEC, NCH> t;
         row_load(t, side + q * D, lig, G, nvec);
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) c.v[k][e] = __fadd_rn(c.v[k][e], t.v[k][e]);
+        row_add<true>(c, t);
       }
-#pragma unroll
-      for (int k = 0; k < NCH; ++k)
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) acc.v[k][e] += c.v[k][e];
+      row_add(acc, c);
     }
-#pragma unroll
-    for (int k = 0; k < NCH; ++k)
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) red[((gidx * G + lig) * NCH + k) * VEC + e] = acc.v[k][e];
-    __syncthreads();
-    if (gidx == 0) {
-      const int used = (int)min<int64_t>(NG, K + 1);
-      for (int gg = 1; gg < used; ++gg)
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) acc.v[k][e] += red[((gg * G + lig) * NCH + k) * VEC + e];
+    if (combine_groups(acc, K, G)) {
       const bool prod = (int64_t)id >= Vs;
       const int64_t r = prod ? (int64_t)id - Vs : (int64_t)id;
       T* row = (prod ? tt.p : tt.s) + r * D;
@@ -891,10 +786,7 @@ __global__ __launch_bounds__(kBlock) void triplet_direct_long_kernel(DirectTower
       RowRegs<VEC, NCH> own, a;
       row_load(own, row, lig, G, nvec);
       row_load(a, accrow, lig, G, nvec);
-#pragma unroll
-      for (int k = 0; k < NCH; ++k)
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) adagrad_elem(own.v[k][e], a.v[k][e], acc.v[k][e], lr, eps);
+      row_adagrad(own, a, acc, lr, eps);
       row_store(a, accrow, lig, G, nvec);
       row_store(own, row, lig, G, nvec);
     }
@@ -902,14 +794,24 @@ __global__ __launch_bounds__(kBlock) void triplet_direct_long_kernel(DirectTower
   }
 }
 
-// ESR_TRIPLET_STEP=stamped keeps the double-buffered walk over the sorted occurrences (rounds 2-3); default: direct
-static bool trip_direct_mode() {
-  const char* e = getenv("ESR_TRIPLET_STEP");
-  return !(e && e[0] == 's');
+// The unit's environment switches, read ONCE per entry-point call (not per process: a caller may change them between
+// two calls) and passed down.
+struct TripMode {
+  bool direct;     // ESR_TRIPLET_STEP=stamped keeps the double-buffered walk over the sorted occurrences (rounds 2-3);
+                   // default: direct
+  bool few_lanes;  // ESR_TRIPLET_DIRECT_LANES=few: the direct step with step_geom_few_lanes (default: row_geom)
+  bool vec8;       // ESR_BF16_VEC8=1: bf16 rows of the direct step as 8 elements (16 bytes) per lane when the width allows
+                   // -- measured slower (136 registers, three waves per SIMD instead of five; the step lives on its
+                   // occupancy): 0.496 against 0.438 ms per 262 144 triplets
+};
+static TripMode trip_mode() {
+  const char *e = getenv("ESR_TRIPLET_STEP"), *le = getenv("ESR_TRIPLET_DIRECT_LANES"), *v8 = getenv("ESR_BF16_VEC8");
+  return TripMode{!(e && e[0] == 's'), le && le[0] == 'f', v8 && v8[0] == '1'};
 }
 
-static int launch_trip_plan(const int32_t* const* ids, int nbatch, const int32_t* sorted_ids, const int32_t* perm,
-                            int64_t B, int64_t Vs, char* plans, size_t stride, int* hints, int gen, hipStream_t st) {
+static int launch_trip_plan(const TripMode& mode, const int32_t* const* ids, int nbatch, const int32_t* sorted_ids,
+                            const int32_t* perm, int64_t B, int64_t Vs, char* plans, size_t stride, int* hints, int gen,
+                            hipStream_t st) {
   PlanBatch pb;
   for (int b = 0; b < kMaxPlanBatch; ++b) {
     const int s = b < nbatch ? b : 0;
@@ -919,7 +821,7 @@ static int launch_trip_plan(const int32_t* const* ids, int nbatch, const int32_t
   }
   const int64_t n = 3 * B;
   const int gx = (int)std::min<int64_t>(kMaxGrid, cdiv(n, kBlock));
-  if (trip_direct_mode()) {
+  if (mode.direct) {
     // The long-run counters carry the plan call's full 32-bit generation (see the kernel): nothing to clear in front of
     // it.  gen == 0 (a plan made in line, inside a step call, in scratch memory that may hold anything -- also a word of
     // generation 0): the word is cleared first.
@@ -968,7 +870,7 @@ int esr_triplet_plan(const int32_t* const* ids, int nbatch, int64_t B, int64_t V
               (long long)B, (long long)Vs);
   ESR_REQUIRE(ids && sorted_ids && perm && plans && !((uintptr_t)plans & 255), "esr_triplet_plan: null or misaligned pointer");
   for (int i = 0; i < 3 * nbatch; ++i) ESR_REQUIRE(ids[i], "esr_triplet_plan: null id list %d", i);
-  launch_trip_plan(ids, nbatch, sorted_ids, perm, B, Vs, (char*)plans, esr_triplet_plan_bytes(B), hints, gen,
+  launch_trip_plan(trip_mode(), ids, nbatch, sorted_ids, perm, B, Vs, (char*)plans, esr_triplet_plan_bytes(B), hints, gen,
                    as_stream(stream));
   return check_launch("esr_triplet_plan");
 }
@@ -984,115 +886,146 @@ int esr_rows_restamp(uint8_t* loc, int64_t V, esr_stream_t stream) {
 
 }  // extern "C"
 
-// one step's launches (arguments validated by the callers)
-// what a direct step leaves for its caller: where its loss partials are (triplet_direct_loss_kernel turns them into losses)
-struct DirectLoss {
-  int nparts = 0;
-  const char* plan = nullptr;
-  size_t part_off = 0;
+// what both step entry points are given besides their id lists, and what they check of it
+struct TripStepArgs {
+  const char* who;
+  void* scene; void* scene_shadow; uint8_t* scene_loc; float* scene_accum; int64_t Vs;
+  void* product; void* product_shadow; uint8_t* product_loc; float* product_accum; int64_t Vp;
+  int dtype, D;
+  int64_t B;
+  float regularization, batch_size, lr, eps;
+  void* workspace;
+  size_t workspace_bytes;
+  TwoTowers towers(uint32_t stamp) const {
+    return TwoTowers{(float*)scene, (float*)scene_shadow, (float*)product, (float*)product_shadow, scene_loc, product_loc,
+                     scene_accum, product_accum, Vs, stamp};
+  }
 };
-static void launch_direct_losses(const DirectLoss& d, size_t stride, int nb, float batch_size, float* losses,
-                                 hipStream_t st) {
-  ESR_KT("triplet_direct_loss_kernel", st,
-         hipLaunchKernelGGL(triplet_direct_loss_kernel, dim3(nb), dim3(kBlock), 0, st, d.plan, stride, d.part_off, d.nparts,
-                            1.0 / (double)batch_size, losses));
-}
-
-static int launch_trip_step(const TwoTowers& tt, int dtype, int D, const RowGeom& g, const int32_t* scene_ids, const int32_t* pos_ids,
-                            const int32_t* neg_ids, int64_t B, float regularization, float batch_size, float lr, float eps,
-                            const int32_t* sorted, const int32_t* perm, void* plan, int long_runs, float* loss,
-                            const TripWs& ws, hipStream_t st, DirectLoss* direct = nullptr) {
-  const int64_t n = 3 * B;
-  if (!plan) {  // no plan made ahead: make it here (and nobody told us whether a run is long: screen for it)
-    const int32_t* ids3[3] = {scene_ids, pos_ids, neg_ids};
-    launch_trip_plan(ids3, 1, sorted, perm, B, tt.Vs, ws.plan, 0, nullptr, 0, st);
-    plan = ws.plan;
-    long_runs = -1;
+static int trip_step_checks(const TripStepArgs& a, const TripMode& mode, RowGeom* geom) {
+  const char* who = a.who;
+  ESR_REQUIRE(a.B > 0 && a.D > 0 && a.Vs > 0 && a.Vp > 0, "%s: bad sizes Vs=%lld Vp=%lld D=%d B=%lld", who, (long long)a.Vs,
+              (long long)a.Vp, a.D, (long long)a.B);
+  ESR_REQUIRE(a.Vs + a.Vp <= (int64_t)kIdMask, "%s: %lld virtual rows exceed 2^30 - 1", who, (long long)(a.Vs + a.Vp));
+  ESR_REQUIRE(3 * a.B < ((int64_t)1 << 31), "%s: B=%lld too large", who, (long long)a.B);
+  ESR_REQUIRE(!mode.direct || 3 * a.B < ((int64_t)1 << 29),
+              "%s: B=%lld too large for the direct step's 29-bit run heads (ESR_TRIPLET_STEP=stamped)", who, (long long)a.B);
+  ESR_REQUIRE(a.scene && a.scene_accum && a.product && a.product_accum, "%s: null table pointer", who);
+  // direct mode (the default) steps rows in place: the second buffers and location bytes are not used, may be NULL
+  ESR_REQUIRE(mode.direct || (a.scene_shadow && a.scene_loc && a.product_shadow && a.product_loc),
+              "%s: null second buffer / location bytes (ESR_TRIPLET_STEP=stamped needs them)", who);
+  ESR_REQUIRE(mode.direct || (a.scene != a.scene_shadow && a.product != a.product_shadow),
+              "%s: a shadow table must be a second buffer", who);
+  ESR_REQUIRE(a.batch_size != 0.f, "%s: batch_size must be non-zero", who);
+  ESR_REQUIRE(a.dtype == ESR_F32 || (a.dtype == ESR_BF16 && mode.direct), "%s: dtype %d (f32, or bf16 rows in the direct step)",
+              who, a.dtype);
+  ESR_REQUIRE(a.dtype == ESR_F32 || a.D % 4 != 0 || !(((uintptr_t)a.scene | (uintptr_t)a.product) & 7),
+              "%s: bf16 tables must be 8-byte aligned", who);
+  *geom = step_geom_few_lanes(a.D);
+  ESR_REQUIRE(geom->nch <= kMaxChunksPerLane, "%s: D=%d not supported", who, a.D);
+  const size_t need = esr_triplet_step_workspace_bytes(a.B, a.D);
+  if (!a.workspace || a.workspace_bytes < need || ((uintptr_t)a.workspace & 15)) {
+    set_error("%s: workspace %zu bytes < %zu required (or misaligned)", who, a.workspace_bytes, need);
+    return ESR_EWORKSPACE;
   }
-  TripPlan pl;
-  trip_plan_layout(B, (char*)plan, &pl);
-  int grid = grid_for_groups(n, g.G);
-  const int grid2 = (int)std::min<int64_t>(kMaxGrid, cdiv(cdiv(n, kTripChunk), 4));
-  const float inv_bs = 1.0f / batch_size;
-  if (trip_direct_mode()) {
-    // rows are stepped in place in the primary buffers (the second buffers and location bytes are not touched: the
-    // caller's rows never leave home)
-    // lanes per row: a triplet's five dot products are a small part of its work (the stamped walk had six per occurrence
-    // and wanted few lanes); ESR_TRIPLET_DIRECT_LANES=few keeps step_geom_few_lanes
-    const char* le = getenv("ESR_TRIPLET_DIRECT_LANES");
-    // bf16 rows: 8 elements (16 bytes) per lane when the width allows (row_geom8)
-    // -- ESR_BF16_VEC8=1 only: measured slower (136 registers, three waves per SIMD instead of five; the step lives on
-    // its occupancy): 0.496 against 0.438 ms per 262 144 triplets
-    const char* v8 = getenv("ESR_BF16_VEC8");
-    const bool vec8 = v8 && v8[0] == '1' && dtype == ESR_BF16 && D % 8 == 0 && !(((uintptr_t)tt.s0 | (uintptr_t)tt.p0) & 15);
-    const RowGeom gd = vec8 ? row_geom8(D) : ((le && le[0] == 'f') ? g : row_geom(D));
-    const RowGeom& g = gd;
-#define ESR_TRIP_DIRECT_LAUNCH(T, DISPATCH)                                                                            \
-    DISPATCH(g, {                                                                                                      \
-      const DirectTowers<T> dt{(T*)tt.s0, (T*)tt.p0, tt.sacc, tt.pacc};                                                \
-      static const int resident = resident_blocks((const void*)triplet_direct_kernel<VEC, NCH, T>);                    \
-      const int gridd = std::min(grid_for_groups(B, g.G), resident);                                                   \
-      ESR_KT("triplet_direct_kernel", st, hipLaunchKernelGGL((triplet_direct_kernel<VEC, NCH, T>), dim3(gridd), dim3(kBlock), 0, st, dt, D, g.G, scene_ids, \
-                         pos_ids, neg_ids, (const uint2*)pl.meta, B, regularization, inv_bs, 1, lr, eps, ws.chunk_rows, \
-                         pl.cnt, pl.flags, pl.loss_part));                                                             \
-      if (direct) {  /* the caller adds the partials up (one launch for a whole group of steps) */                     \
-        direct->nparts = gridd;                                                                                        \
-        direct->plan = (const char*)plan;                                                                              \
-        direct->part_off = (size_t)((const char*)pl.loss_part - (const char*)plan);                                    \
-      }                                                                                                                \
-      if (long_runs != 0)  /* 0 = the caller knows (the plan's hint) that no run is longer than kDirectMaxRun */       \
-        ESR_KT("triplet_direct_long_kernel", st, hipLaunchKernelGGL((triplet_direct_long_kernel<VEC, NCH, T>), dim3(256), dim3(kBlock), 0, st, dt, D, g.G, \
-                           tt.Vs, sorted, n, lr, eps, (const float*)ws.chunk_rows, (const int*)pl.flags,               \
-                           (const int32_t*)pl.long_heads));                                                            \
-    })
-    if (vec8) {
-      ESR_TRIP_DIRECT_LAUNCH(uint16_t, ESR_DISPATCH_ROW8);
-    } else if (dtype == ESR_BF16) {
-      ESR_TRIP_DIRECT_LAUNCH(uint16_t, ESR_DISPATCH_ROW);
-    } else {
-      ESR_TRIP_DIRECT_LAUNCH(float, ESR_DISPATCH_ROW);
-    }
-#undef ESR_TRIP_DIRECT_LAUNCH
-    return ESR_OK;
-  }
-  ESR_DISPATCH_ROW(g, {
-    static const int resident = resident_blocks((const void*)triplet_step_kernel<VEC, NCH>);  // (one query per process)
-    grid = std::min(grid, resident);
-    ESR_KT("triplet_step_kernel", st, hipLaunchKernelGGL((triplet_step_kernel<VEC, NCH>), dim3(grid), dim3(kBlock), 0, st, tt, D, g.G, sorted,
-                       (const uint2*)pl.meta, n, regularization, inv_bs, 1, lr, eps, ws.chunk_rows, pl.flags,
-                       pl.loss_acc, loss_frac_bits(B), 1.0 / (double)batch_size, loss));
-    if (long_runs != 0)  // 0 = the caller knows (esr_triplet_plan's hint) that no run outgrows its head chunk
-      ESR_KT("triplet_step_long_kernel", st, hipLaunchKernelGGL((triplet_step_long_kernel<VEC, NCH>), dim3(grid2), dim3(kBlock), 0, st, tt, D, g.G, sorted, n,
-                         lr, eps, (const float*)ws.chunk_rows, (const int*)pl.flags));
-  });
   return ESR_OK;
 }
 
-#define ESR_TRIP_STEP_CHECKS(who)                                                                                      \
-  ESR_REQUIRE(B > 0 && D > 0 && Vs > 0 && Vp > 0, who ": bad sizes Vs=%lld Vp=%lld D=%d B=%lld", (long long)Vs,        \
-              (long long)Vp, D, (long long)B);                                                                         \
-  ESR_REQUIRE(Vs + Vp <= (int64_t)kIdMask, who ": %lld virtual rows exceed 2^30 - 1", (long long)(Vs + Vp));           \
-  ESR_REQUIRE(3 * B < ((int64_t)1 << 31), who ": B=%lld too large", (long long)B);                                     \
-  ESR_REQUIRE(!trip_direct_mode() || 3 * B < ((int64_t)1 << 29),                                                       \
-              who ": B=%lld too large for the direct step's 29-bit run heads (ESR_TRIPLET_STEP=stamped)", (long long)B); \
-  ESR_REQUIRE(scene && scene_accum && product && product_accum, who ": null table pointer");                           \
-  /* direct mode (the default) steps rows in place: the second buffers and location bytes are not used, may be NULL */ \
-  ESR_REQUIRE(trip_direct_mode() || (scene_shadow && scene_loc && product_shadow && product_loc),                      \
-              who ": null second buffer / location bytes (ESR_TRIPLET_STEP=stamped needs them)");                      \
-  ESR_REQUIRE(trip_direct_mode() || (scene != scene_shadow && product != product_shadow),                              \
-              who ": a shadow table must be a second buffer");                                                         \
-  ESR_REQUIRE(batch_size != 0.f, who ": batch_size must be non-zero");                                                 \
-  ESR_REQUIRE(dtype == ESR_F32 || (dtype == ESR_BF16 && trip_direct_mode()),                                           \
-              who ": dtype %d (f32, or bf16 rows in the direct step)", dtype);                                         \
-  ESR_REQUIRE(dtype == ESR_F32 || D % 4 != 0 || !(((uintptr_t)scene | (uintptr_t)product) & 7),                        \
-              who ": bf16 tables must be 8-byte aligned");                                                             \
-  const RowGeom g = step_geom_few_lanes(D);                                                                            \
-  ESR_REQUIRE(g.nch <= kMaxChunksPerLane, who ": D=%d not supported", D);                                              \
-  if (!workspace || workspace_bytes < esr_triplet_step_workspace_bytes(B, D) || ((uintptr_t)workspace & 15)) {         \
-    set_error(who ": workspace %zu bytes < %zu required (or misaligned)", workspace_bytes,                             \
-              esr_triplet_step_workspace_bytes(B, D));                                                                 \
-    return ESR_EWORKSPACE;                                                                                             \
+// one batch: its id lists, sorted occurrence list and plan (null: made in line), and what the caller knows about long runs
+struct TripBatch {
+  const int32_t *scene_ids, *pos_ids, *neg_ids;
+  const int32_t *sorted, *perm;
+  void* plan;
+  int long_runs;  // 0 = the plan's hint says that no run is long: the `long` launch is left out
+};
+
+// the direct step's two launches for one row geometry and table element type; returns the update kernel's grid (= the
+// number of loss partials it leaves in the plan)
+template <int VEC, int NCH, class T>
+static int launch_direct(const TripStepArgs& a, const TwoTowers& tt, const RowGeom& g, const TripBatch& b, const TripPlan& pl,
+                         float* side, hipStream_t st) {
+  const DirectTowers<T> dt{(T*)tt.s0, (T*)tt.p0, tt.sacc, tt.pacc};
+  static const int resident = resident_blocks((const void*)triplet_direct_kernel<VEC, NCH, T>);  // (one query per process)
+  const int gridd = std::min(grid_for_groups(a.B, g.G), resident);
+  ESR_KT("triplet_direct_kernel", st,
+         hipLaunchKernelGGL((triplet_direct_kernel<VEC, NCH, T>), dim3(gridd), dim3(kBlock), 0, st, dt, a.D, g.G, b.scene_ids,
+                            b.pos_ids, b.neg_ids, (const uint2*)pl.meta, a.B, a.regularization, 1.0f / a.batch_size, 1, a.lr,
+                            a.eps, side, pl.cnt, pl.flags, pl.loss_part));
+  if (b.long_runs != 0)
+    ESR_KT("triplet_direct_long_kernel", st,
+           hipLaunchKernelGGL((triplet_direct_long_kernel<VEC, NCH, T>), dim3(256), dim3(kBlock), 0, st, dt, a.D, g.G, tt.Vs,
+                              b.sorted, 3 * a.B, a.lr, a.eps, (const float*)side, (const int*)pl.flags,
+                              (const int32_t*)pl.long_heads));
+  return gridd;
+}
+
+// one step's launches (arguments validated by the callers).  Returns the number of loss partials a direct step left in its
+// plan (the caller adds them up: one launch for a whole group of steps), 0 in stamped mode (the loss is written).
+static int launch_trip_step(const TripStepArgs& a, const TripMode& mode, const RowGeom& g, const TwoTowers& tt, TripBatch b,
+                            float* loss, const TripWs& ws, hipStream_t st) {
+  const int64_t n = 3 * a.B;
+  if (!b.plan) {  // no plan made ahead: make it here (and nobody told us whether a run is long: screen for it)
+    const int32_t* ids3[3] = {b.scene_ids, b.pos_ids, b.neg_ids};
+    launch_trip_plan(mode, ids3, 1, b.sorted, b.perm, a.B, tt.Vs, ws.plan, 0, nullptr, 0, st);
+    b.plan = ws.plan;
+    b.long_runs = -1;
   }
+  TripPlan pl;
+  trip_plan_layout(a.B, (char*)b.plan, &pl);
+  if (mode.direct) {
+    // rows are stepped in place in the primary buffers (the second buffers and location bytes are not touched: the
+    // caller's rows never leave home)
+    // lanes per row: a triplet's five dot products are a small part of its work (the stamped walk had six per occurrence
+    // and wanted few lanes)
+    const bool vec8 = mode.vec8 && a.dtype == ESR_BF16 && a.D % 8 == 0 && !(((uintptr_t)tt.s0 | (uintptr_t)tt.p0) & 15);
+    const RowGeom gd = vec8 ? row_geom8(a.D) : (mode.few_lanes ? g : row_geom(a.D));
+    int nparts = 0;
+    if (vec8)
+      ESR_DISPATCH_ROW8(gd, nparts = (launch_direct<VEC, NCH, uint16_t>(a, tt, gd, b, pl, ws.chunk_rows, st)));
+    else if (a.dtype == ESR_BF16)
+      ESR_DISPATCH_ROW(gd, nparts = (launch_direct<VEC, NCH, uint16_t>(a, tt, gd, b, pl, ws.chunk_rows, st)));
+    else
+      ESR_DISPATCH_ROW(gd, nparts = (launch_direct<VEC, NCH, float>(a, tt, gd, b, pl, ws.chunk_rows, st)));
+    return nparts;
+  }
+  int grid = grid_for_groups(n, g.G);
+  const int grid2 = (int)std::min<int64_t>(kMaxGrid, cdiv(cdiv(n, kTripChunk), 4));
+  ESR_DISPATCH_ROW(g, {
+    static const int resident = resident_blocks((const void*)triplet_step_kernel<VEC, NCH>);  // (one query per process)
+    grid = std::min(grid, resident);
+    ESR_KT("triplet_step_kernel", st, hipLaunchKernelGGL((triplet_step_kernel<VEC, NCH>), dim3(grid), dim3(kBlock), 0, st, tt, a.D, g.G, b.sorted,
+                       (const uint2*)pl.meta, n, a.regularization, 1.0f / a.batch_size, 1, a.lr, a.eps, ws.chunk_rows, pl.flags,
+                       pl.loss_acc, loss_frac_bits(a.B), 1.0 / (double)a.batch_size, loss));
+    if (b.long_runs != 0)  // 0 = the caller knows (esr_triplet_plan's hint) that no run outgrows its head chunk
+      ESR_KT("triplet_step_long_kernel", st, hipLaunchKernelGGL((triplet_step_long_kernel<VEC, NCH>), dim3(grid2), dim3(kBlock), 0, st, tt, a.D, g.G, b.sorted, n,
+                         a.lr, a.eps, (const float*)ws.chunk_rows, (const int*)pl.flags));
+  });
+  return 0;
+}
+
+// nbatch steps with stamps first_stamp, first_stamp + 1, ...: batch(i) names step i's lists and plan (plans `stride`
+// bytes apart).  Direct mode: the losses of the whole group by ONE launch (same grid for every step).
+template <class Batch>
+static int run_trip_steps(const TripStepArgs& a, const TripMode& mode, const RowGeom& g, int nbatch, uint32_t first_stamp,
+                          Batch batch, size_t stride, float* losses, const TripWs& ws, hipStream_t st) {
+  int nparts = 0;
+  const void* plan0 = nullptr;
+  for (int i = 0; i < nbatch; ++i) {
+    const TripBatch b = batch(i);
+    const int np = launch_trip_step(a, mode, g, a.towers(first_stamp + (uint32_t)i), b, losses + i, ws, st);
+    if (i == 0) {
+      nparts = np;
+      plan0 = b.plan ? b.plan : ws.plan;
+    }
+  }
+  if (nparts) {
+    TripPlan pl;
+    trip_plan_layout(a.B, (char*)plan0, &pl);
+    ESR_KT("triplet_direct_loss_kernel", st,
+           hipLaunchKernelGGL(triplet_direct_loss_kernel, dim3(nbatch), dim3(kBlock), 0, st, (const char*)pl.loss_part, stride,
+                              (size_t)0, nparts, 1.0 / (double)a.batch_size, losses));
+  }
+  return check_launch(a.who);
+}
 
 extern "C" {
 
@@ -1104,36 +1037,33 @@ int esr_triplet_train_step(void* scene, void* scene_shadow, uint8_t* scene_loc, 
                            void* plan, int long_runs, float* loss, void* workspace, size_t workspace_bytes,
                            esr_stream_t stream) {
   TraceScope trace_scope_("esr_triplet_train_step");
-  ESR_TRIP_STEP_CHECKS("esr_triplet_train_step")
+  const TripMode mode = trip_mode();
+  const TripStepArgs a{"esr_triplet_train_step", scene, scene_shadow, scene_loc, scene_accum, Vs, product, product_shadow,
+                       product_loc, product_accum, Vp, dtype, D, B, regularization, batch_size, lr, eps, workspace,
+                       workspace_bytes};
+  RowGeom g;
+  if (int rc = trip_step_checks(a, mode, &g)) return rc;
   ESR_REQUIRE(scene_ids && pos_ids && neg_ids && loss, "esr_triplet_train_step: null pointer");
-  ESR_REQUIRE(trip_direct_mode() || (stamp >= 1 && stamp <= kStampMax), "esr_triplet_train_step: stamp %u not in [1, %u]",
+  ESR_REQUIRE(mode.direct || (stamp >= 1 && stamp <= kStampMax), "esr_triplet_train_step: stamp %u not in [1, %u]",
               stamp, kStampMax);
   ESR_REQUIRE((presorted_ids == nullptr) == (presorted_perm == nullptr),
               "esr_triplet_train_step: presorted_ids and presorted_perm must both be set or both be NULL");
   ESR_REQUIRE(!plan || presorted_ids, "esr_triplet_train_step: a plan goes with the sorted ids it was made from");
   ESR_REQUIRE(!plan || !((uintptr_t)plan & 255), "esr_triplet_train_step: misaligned plan");
-  hipStream_t st = as_stream(stream);
   TripWs ws;
   trip_ws_layout(B, D, (char*)workspace, &ws);
-  const int32_t* sorted = presorted_ids;
-  const int32_t* perm = presorted_perm;
-  if (!sorted) {
+  TripBatch b{scene_ids, pos_ids, neg_ids, presorted_ids, presorted_perm, plan, long_runs};
+  if (!b.sorted) {
     const int32_t* segs[3] = {scene_ids, pos_ids, neg_ids};
     const int64_t counts[3] = {B, B, B};
     const int64_t offsets[3] = {0, Vs, Vs};
     if (int rc = esr_segment_sort_ids_multi(segs, counts, offsets, 3, Vs + Vp, ws.sorted_ids, ws.perm, ws.sort_ws,
                                             ws.sort_ws_bytes, stream))
       return rc;
-    sorted = ws.sorted_ids;
-    perm = ws.perm;
+    b.sorted = ws.sorted_ids;
+    b.perm = ws.perm;
   }
-  TwoTowers tt{(float*)scene, (float*)scene_shadow, (float*)product, (float*)product_shadow, scene_loc, product_loc,
-               scene_accum, product_accum, Vs, stamp};
-  DirectLoss dl;
-  launch_trip_step(tt, dtype, D, g, scene_ids, pos_ids, neg_ids, B, regularization, batch_size, lr, eps, sorted, perm, plan,
-                   long_runs, loss, ws, st, &dl);
-  if (dl.nparts) launch_direct_losses(dl, 0, 1, batch_size, loss, st);
-  return check_launch("esr_triplet_train_step");
+  return run_trip_steps(a, mode, g, 1, stamp, [&](int) { return b; }, 0, loss, ws, as_stream(stream));
 }
 
 int esr_triplet_train_steps(void* scene, void* scene_shadow, uint8_t* scene_loc, float* scene_accum, int64_t Vs,
@@ -1143,30 +1073,26 @@ int esr_triplet_train_steps(void* scene, void* scene_shadow, uint8_t* scene_loc,
                             const int32_t* perm, void* plans, const int32_t* long_runs, float* losses, void* workspace,
                             size_t workspace_bytes, esr_stream_t stream) {
   TraceScope trace_scope_("esr_triplet_train_steps");
-  ESR_TRIP_STEP_CHECKS("esr_triplet_train_steps")
+  const TripMode mode = trip_mode();
+  const TripStepArgs a{"esr_triplet_train_steps", scene, scene_shadow, scene_loc, scene_accum, Vs, product, product_shadow,
+                       product_loc, product_accum, Vp, dtype, D, B, regularization, batch_size, lr, eps, workspace,
+                       workspace_bytes};
+  RowGeom g;
+  if (int rc = trip_step_checks(a, mode, &g)) return rc;
   ESR_REQUIRE(nbatch >= 1 && nbatch <= kMaxPlanBatch && ids && sorted_ids && perm && plans && losses &&
                   !((uintptr_t)plans & 255),
               "esr_triplet_train_steps: nbatch=%d not in [1, %d], or a null / misaligned pointer", nbatch, kMaxPlanBatch);
-  ESR_REQUIRE(trip_direct_mode() || (first_stamp >= 1 && first_stamp + (uint32_t)nbatch - 1 <= kStampMax),
+  ESR_REQUIRE(mode.direct || (first_stamp >= 1 && first_stamp + (uint32_t)nbatch - 1 <= kStampMax),
               "esr_triplet_train_steps: stamps %u .. %u leave [1, %u]", first_stamp, first_stamp + nbatch - 1, kStampMax);
   for (int i = 0; i < 3 * nbatch; ++i) ESR_REQUIRE(ids[i], "esr_triplet_train_steps: null id list %d", i);
-  hipStream_t st = as_stream(stream);
   TripWs ws;
   trip_ws_layout(B, D, (char*)workspace, &ws);
   const size_t stride = esr_triplet_plan_bytes(B);
-  DirectLoss first;
-  for (int b = 0; b < nbatch; ++b) {
-    TwoTowers tt{(float*)scene, (float*)scene_shadow, (float*)product, (float*)product_shadow, scene_loc, product_loc,
-                 scene_accum, product_accum, Vs, first_stamp + (uint32_t)b};
-    DirectLoss dl;
-    launch_trip_step(tt, dtype, D, g, ids[3 * b], ids[3 * b + 1], ids[3 * b + 2], B, regularization, batch_size, lr, eps,
-                     sorted_ids + (int64_t)b * 3 * B, perm + (int64_t)b * 3 * B, (char*)plans + (size_t)b * stride,
-                     long_runs ? long_runs[b] : -1, losses + b, ws, st, &dl);
-    if (b == 0) first = dl;
-  }
-  // direct mode: the losses of the whole group by ONE launch (plans are `stride` apart, same grid for every step)
-  if (first.nparts) launch_direct_losses(first, stride, nbatch, batch_size, losses, st);
-  return check_launch("esr_triplet_train_steps");
+  auto batch = [&](int i) {
+    return TripBatch{ids[3 * i], ids[3 * i + 1], ids[3 * i + 2], sorted_ids + (int64_t)i * 3 * B, perm + (int64_t)i * 3 * B,
+                     (char*)plans + (size_t)i * stride, long_runs ? long_runs[i] : -1};
+  };
+  return run_trip_steps(a, mode, g, nbatch, first_stamp, batch, stride, losses, ws, as_stream(stream));
 }
 
 }  // extern "C"

@@ -15,10 +15,11 @@
 // one pass over V bytes) each time its counter wraps.
 #pragma once
 #include "esr_common.h"
+#include "esr_segment.h"
 
 namespace esr {
 
-constexpr int kStepChunk = 32;  // == kSegChunk of esr_segment.h: same cut points, same association of every sum
+constexpr int kStepChunk = kSegChunk;  // same cut points, same association of every sum (combine_long_runs)
 constexpr uint32_t kLocBit = 0x80000000u;   // row code: the row's current value is in the second buffer
 constexpr uint32_t kSideBit = 0x40000000u;  // (GloVe plan records) the occurrence is the pair's second token
 constexpr uint32_t kIdMask = 0x3FFFFFFFu;   // row code: the (virtual) row id, < 2^30 - 1
@@ -134,14 +135,6 @@ __device__ __forceinline__ unsigned coherent_load(const unsigned* p) {
 __device__ __forceinline__ void announce_start(uint32_t* flag, uint32_t value) {
   if (flag && blockIdx.x == 0 && threadIdx.x == 0)
     __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <int VEC, int NCH>
-__device__ __forceinline__ void row_zero(RowRegs<VEC, NCH>& r) {
-#pragma unroll
-  for (int k = 0; k < NCH; ++k)
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) r.v[k][e] = 0.f;
 }
 #endif
 

@@ -134,6 +134,49 @@ def _ids_uniform(rng, Vs, Vp, B):
             rng.integers(0, Vp, B).astype(np.int32))
 
 
+# ---- one hot row per tower: the long-run combination of the stamped step -------------------------------------------------
+HOT_CHUNK = 8    # kTripChunk: the stamped step cuts a run at the multiples of 8 sorted positions
+HOT_GROUPS = 32  # row groups per workgroup of the stamped step (step_geom_few_lanes: 8 lanes per row at D = 128 and D = 6)
+# partial sums of the hot run: 2, around the group count, around four times it (the four-in-flight loop's last round),
+# and more than 256 continuation chunks (the count of the chunks needs a second pass)
+HOT_PARTIALS = (2, HOT_GROUPS - 1, HOT_GROUPS, HOT_GROUPS + 1, 4 * HOT_GROUPS - 1, 4 * HOT_GROUPS, 4 * HOT_GROUPS + 1, 258)
+HOT_ALIGN = (0, HOT_CHUNK - 1)
+
+
+def hot_run_length(partials, align, chunk):
+    """The shortest run, its head at `align` inside a chunk, that is cut into `partials` partial sums: the head chunk
+    runs to the first chunk boundary at least `chunk` positions on, every further chunk holds `chunk` positions."""
+    return chunk + (chunk - align) % chunk + (partials - 2) * chunk + 1
+
+
+def hot_batch_size(partials, align):
+    return hot_run_length(partials, align, HOT_CHUNK) + HOT_CHUNK + 24
+
+
+def _ids_hot(partials, align):
+    def make(rng, Vs, Vp, B):
+        """Scene id 1 and product id 1 (in the pos list) occur L times, L cut into `partials` partial sums; `align` scene
+        ids 0 sort in front of the scene run, and as many product ids 0 in front of the product run as put ITS head (sorted
+        position B + their number) at the other alignment; every other id occurs once."""
+        L = hot_run_length(partials, align, HOT_CHUNK)
+        other = HOT_ALIGN[1] if align == HOT_ALIGN[0] else HOT_ALIGN[0]
+        # (the product run starts elsewhere in its chunk, so its head chunk may hold up to 7 positions more or fewer:
+        # its number of partials is `partials` or one off)
+        front = (other - B) % HOT_CHUNK
+        sid = ids_with_runs(Vs, B, {0: align, 1: L}, rng)
+        pid, nid = _split_pos_neg(rng, B, Vp, {0: front, 1: L}, {}, (1,))
+        return sid, pid, nid
+    return make
+
+
+def hot_partials(sorted_ids, vid, chunk):
+    """(number of partial sums, alignment of the head) of virtual row vid's run in a sorted list"""
+    pos = np.flatnonzero(np.asarray(sorted_ids) == vid)
+    h, end = int(pos[0]), int(pos[-1]) + 1
+    nxt = (h + 2 * chunk - 1) // chunk * chunk
+    return 1 + max(0, -(-(end - nxt) // chunk)), h % chunk
+
+
 class Spec:
     def __init__(self, name, D, B, ids=_ids_small_runs, Vs=300, Vp=400, lam=LAM, batch_size=None, redraw_neg=False):
         self.name, self.D, self.B, self.ids, self.Vs, self.Vp, self.lam = name, D, B, ids, Vs, Vp, lam
@@ -182,6 +225,13 @@ SPECS["twostep-a-D128"] = Spec("twostep-a-D128", 128, 1152, _ids_all_runs(9))
 SPECS["twostep-b-D128"] = Spec("twostep-b-D128", 128, 1152, _ids_all_runs(8))  # (ids only: make_second_step)
 
 RUN_CASES = [s.name[:-5] for s in _run_specs(128)]  # names without the "-D128"
+HOT_CASES = ["hot-P%d-a%d" % (p, a) for p in HOT_PARTIALS for a in HOT_ALIGN]
+for _D in RUN_WIDTHS:
+    for _p in HOT_PARTIALS:
+        for _a in HOT_ALIGN:
+            _B = hot_batch_size(_p, _a)
+            _n = "hot-P%d-a%d-D%d" % (_p, _a, _D)
+            SPECS[_n] = Spec(_n, _D, _B, _ids_hot(_p, _a), Vs=_B + 64, Vp=2 * _B + 64)
 
 
 # ---- towers ------------------------------------------------------------------------------------------------------------

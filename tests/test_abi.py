@@ -233,6 +233,18 @@ def test_workspace_queries_are_monotone(lib):
     assert lib.esr_inbatch_workspace_bytes(8192, 128) > 8192 * 4
 
 
+@pytest.mark.parametrize("B", [1, 2, 33, 8192, 262144])
+def test_triplet_plan_bytes_is_the_restated_layout(lib, B):
+    """esr_triplet_plan_bytes against the plan's fields written out (esr_triplet_step.hip, TripPlan): 64 flag words, the
+    fixed-point loss accumulator (16 x 17 words of 8 bytes), a record and a counter per occurrence, the list of long runs,
+    one loss partial per workgroup of the largest grid -- each rounded up to 256 bytes.  The plan kernels and the host
+    take their offsets from one function; a plan buffer sized here must keep fitting it."""
+    n = 3 * B
+    up = lambda x: (x + 255) // 256 * 256  # noqa: E731
+    want = up(4 * 64) + up(8 * 16 * 17) + up(8 * n) + up(4 * n) + up(4 * (n // 9 + 1)) + up(8 * 2048)
+    assert lib.esr_triplet_plan_bytes(B) == want
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     from esrecsys_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

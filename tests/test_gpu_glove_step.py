@@ -45,11 +45,16 @@ def test_fused_step_equals_two_call_path(dev, mode, kind, V, D, B):
         grads, lb = apply_model(b, inputs, target)
         b = update_model(b, grads)
         assert abs(float(la) - float(lb)) <= 2e-6 * abs(float(lb)), (step, float(la), float(lb))
+    _assert_same_tables(a, b, 3)
+
+
+def _assert_same_tables(a, b, steps):
+    """a: the state after `steps` one-pass steps, b: after the same steps on the two-call path"""
     rv = a.versions[("_token_embedding", "embedding")]
     assert rv.dirty and int((rv.loc & 1).sum()) > 0, "some rows must live in the second buffer before consolidation"
     pa, pb = a.params, b.params            # reading .params consolidates
     assert not rv.dirty and int(rv.loc.sum()) == 0
-    assert int(a.step) == int(b.step) == 3
+    assert int(a.step) == int(b.step) == steps
     assert rel_err(pa["_token_embedding"]["embedding"].cpu().numpy(), pb["_token_embedding"]["embedding"].cpu().numpy()) <= 1e-6
     assert rel_err(a.opt_state["sum_of_squares"]["_token_embedding"]["embedding"].cpu().numpy(),
                    b.opt_state["sum_of_squares"]["_token_embedding"]["embedding"].cpu().numpy()) <= 1e-6
