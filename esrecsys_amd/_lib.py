@@ -213,6 +213,13 @@ SIGNATURES = {
     "esr_dice_max_doc": (c_int, []),
     "esr_dice_workspace_bytes": (c_size, [c_i64]),
     "esr_dice_accumulate": (c_int, [c_i32p, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_size, c_vp]),
+    "esr_terms_accumulate": (c_int, [c_i32p, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                     c_vp]),
+    "esr_terms_fold": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "esr_terms_stats": (c_int, [c_vp, c_i64, c_i64, c_i32p, c_vp, c_vp, c_vp, c_vp]),
+    "esr_terms_lookup_build": (c_int, [c_i32p, c_i32p, c_i64, c_vp, c_i64, c_vp]),
+    "esr_terms_lookup": (c_int, [c_i32p, c_i64, c_vp, c_i64, c_int, c_int32, c_i32p, c_i32p, c_vp, c_vp]),
+    "esr_terms_tfidf_rows": (c_int, [c_vp, c_i64, c_i32p, c_i32p, c_i64, c_i64, c_vp, c_i64, c_f32p, c_vp]),
 }
 
 

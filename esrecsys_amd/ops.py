@@ -1557,3 +1557,66 @@ def dice_accumulate(table, capacity, indices, doc_offsets, doc_begin, doc_end, w
     check(lib.esr_dice_accumulate(_p(indices), indices.numel(), _p(doc_offsets), doc_offsets.numel() - 1,
                                   int(doc_begin), int(doc_end), _p(table), int(capacity), _p(workspace),
                                   workspace.numel(), _stream()), "esr_dice_accumulate")
+
+
+# ---------------------------------------------------------------------------------------------
+# term statistics, dictionary lookup, tf-idf rows (esr_terms.hip): pair tables of the co-occurrence builder above
+def terms_accumulate(scratch, capacity, tokens, doc_offsets, doc_begin, doc_end, tok_begin, tok_end, lookup=None,
+                     lookup_capacity=0):
+    """tf of the whole documents [doc_begin, doc_end) = tokens [tok_begin, tok_end) into the scratch table, keyed
+    (document - doc_begin) << 32 | id; id = the raw id, or its value in `lookup` (ids the lookup lacks are dropped)."""
+    lib = _lib.load()
+    _req(tokens, torch.int32, "tokens"), _req(doc_offsets, torch.int64, "doc_offsets")
+    check(lib.esr_terms_accumulate(_p(tokens), tokens.numel(), _p(doc_offsets), doc_offsets.numel() - 1, int(doc_begin),
+                                   int(doc_end), int(tok_begin), int(tok_end), _p(lookup), int(lookup_capacity),
+                                   _p(scratch), int(capacity), _stream()), "esr_terms_accumulate")
+
+
+def terms_fold(scratch, scratch_capacity, table, capacity):
+    """Every (document, id, tf) of the scratch table: frequency[id] += tf, doc_frequency[id] += 1 in `table`."""
+    check(_lib.load().esr_terms_fold(_p(scratch), int(scratch_capacity), _p(table), int(capacity), _stream()),
+          "esr_terms_fold")
+
+
+def terms_stats(table, capacity, n_ids):
+    """(ids int32[n_ids], frequency int64[n_ids], doc_frequency int64[n_ids]) of a statistics table, in slot order."""
+    dev = table.device
+    ids = torch.empty(n_ids, dtype=torch.int32, device=dev)
+    frequency = torch.empty(n_ids, dtype=torch.int64, device=dev)
+    doc_frequency = torch.empty(n_ids, dtype=torch.int64, device=dev)
+    counter = _ws(256, dev)
+    check(_lib.load().esr_terms_stats(_p(table), int(capacity), int(n_ids), _p(ids), _p(frequency), _p(doc_frequency),
+                                      _p(counter), _stream()), "esr_terms_stats")
+    return ids, frequency, doc_frequency
+
+
+def terms_lookup_table(keys, values, capacity):
+    """A pair table of `capacity` >= 2 len(keys) slots with key = keys[i] (distinct raw ids), sum = values[i]."""
+    _req(keys, torch.int32, "keys"), _req(values, torch.int32, "values")
+    table = cooccur_table(capacity, keys.device)
+    check(_lib.load().esr_terms_lookup_build(_p(keys), _p(values), keys.numel(), _p(table), int(capacity), _stream()),
+          "esr_terms_lookup_build")
+    return table
+
+
+def terms_lookup(tokens, lookup, lookup_capacity, mode, size, oov_bucket=None):
+    """(out int32[N], fail int64[1]): mode 0 the value of each token or -1; mode 1 the embedding index (1 + value, or
+    1 + size + bucket).  fail holds bit 2 (a negative token) / bit 32 (a bucket outside [0, 65536)); reading it syncs."""
+    _req(tokens, torch.int32, "tokens")
+    if oov_bucket is not None:
+        _req(oov_bucket, torch.int32, "oov_bucket")
+    out = torch.empty(tokens.numel(), dtype=torch.int32, device=tokens.device)
+    fail = torch.zeros(1, dtype=torch.int64, device=tokens.device)
+    check(_lib.load().esr_terms_lookup(_p(tokens), tokens.numel(), _p(lookup), int(lookup_capacity), int(mode), int(size),
+                                       _p(oov_bucket), _p(out), _p(fail), _stream()), "esr_terms_lookup")
+    return out, fail
+
+
+def terms_tfidf_rows(scratch, capacity, index, row_off, idf):
+    """float32[nnz]: the L2-normalised tf * idf of the rows row_off (int32 [nrows + 1]) of `index`, tf read from scratch."""
+    _req(index, torch.int32, "index"), _req(row_off, torch.int32, "row_off"), _req(idf, torch.float64, "idf")
+    out = torch.empty(index.numel(), dtype=torch.float32, device=index.device)
+    check(_lib.load().esr_terms_tfidf_rows(_p(scratch), int(capacity), _p(index), _p(row_off), row_off.numel() - 1,
+                                           index.numel(), _p(idf), idf.numel(), _p(out), _stream()),
+          "esr_terms_tfidf_rows")
+    return out

@@ -1,8 +1,10 @@
 """Makes the co-occurrence matrix -- the step in front of the GloVe trainer (the reference's
 ``wikipedia/make_cooccurrence.py``, a PySpark job there) on the GPU, from token-id streams.
 
-Tokenising and the token -> embedding-index dictionary are host string work and stay outside: the input is
-``tokens int32[N]`` with ``doc_offsets int64[ndocs + 1]`` (CSR; document d is ``tokens[doc_offsets[d]:doc_offsets[d + 1]]``).
+Tokenising is host string work and stays outside; the token -> embedding-index dictionary is made on the GPU from
+provisional ids by ``make_dictionary`` (``TermStatsBuilder``, ``make_token_dictionary``, ``Dictionary.embedding_indices``),
+whose output is this module's input: ``tokens int32[N]`` with ``doc_offsets int64[ndocs + 1]`` (CSR; document d is
+``tokens[doc_offsets[d]:doc_offsets[d + 1]]``).
 
     builder = CooccurrenceBuilder(context_window=10)
     builder.add(tokens, doc_offsets)            # any number of times: the reduce-by-key over the corpus

@@ -900,6 +900,42 @@ int esr_dice_accumulate(const int32_t* indices, int64_t N, const int64_t* doc_of
                         int64_t doc_begin, int64_t doc_end, void* table, int64_t capacity, void* workspace,
                         size_t workspace_bytes, esr_stream_t stream);
 
+/* ---- Term statistics, dictionary lookup and tf-idf documents from token-id streams (esr_terms.hip; the reference's
+ * wikipedia/make_dictionary.py:67-117, token_dictionary.py:58-64, count_terms.py:32-74) ----
+ * All tables are esr_cooccur_* pair tables (same header, same failure bits, grown by esr_cooccur_rehash); all counts uint64.
+ *   accumulate   the tokens [tok_begin, tok_end) = the whole documents [doc_begin, doc_end) of doc_offsets int64[ndocs + 1]
+ *                (both ranges given: the device's offsets must agree with the host's plan, else failure bit 4) add 1 to
+ *                the SCRATCH key (document - doc_begin) << 32 | id, so its sum is the term frequency.  id = the raw token
+ *                id, or with `lookup` (a table made by lookup_build) the value stored for it -- a raw id the lookup does
+ *                not hold adds nothing.  The caller keeps scratch capacity >= 2 (tok_end - tok_begin).  A negative id
+ *                raises failure bit 2.
+ *   fold         every occupied scratch slot (document, id, tf) adds tf to key id << 32 | 0 and 1 to key id << 32 | 1 of
+ *                `table`: frequency and document frequency.  The scratch table's failure bits are carried over.  The
+ *                caller keeps capacity >= occupied + 2 x the scratch table's occupied count.
+ *   stats        n_ids = occupied / 2: the ids of `table` with both sums, in slot order (sort with esr_segment_sort_ids).
+ *                counter: 8 bytes of device memory, zeroed by the call.
+ *   lookup_build table (initialised by esr_cooccur_table_init, capacity >= 2 K) receives key = keys[i], sum = values[i];
+ *                the keys are distinct.
+ *   lookup       mode 0: out[i] = the value of tokens[i], -1 when absent.  mode 1: out[i] = 1 + value, and when absent
+ *                1 + size + bucket with bucket = oov_bucket[i] (or tokens[i] & 0xFFFF when oov_bucket is NULL).  fail: a
+ *                uint64 device word the CALLER zeroes; bit 2 = a negative token, bit 32 = a bucket outside [0, 65536).
+ *   tfidf_rows   index int32[nnz] = the dictionary indices of the scratch keys in (document, index) order (esr_cooccur_finalize
+ *                with context_window = 1), row_off int32[nrows + 1] their rows (esr_run_offsets): tfidf[i] =
+ *                float(tf idf[index] / sqrt(sum over the row of (tf idf)^2)), 0 where that sum is 0; tf is read back from
+ *                the scratch table as uint64, the arithmetic is fp64, the row sum one wave's fixed-order reduction. */
+int esr_terms_accumulate(const int32_t* tokens, int64_t N, const int64_t* doc_offsets, int64_t ndocs, int64_t doc_begin,
+                         int64_t doc_end, int64_t tok_begin, int64_t tok_end, const void* lookup,
+                         int64_t lookup_capacity, void* scratch, int64_t capacity, esr_stream_t stream);
+int esr_terms_fold(const void* scratch, int64_t scratch_capacity, void* table, int64_t capacity, esr_stream_t stream);
+int esr_terms_stats(void* table, int64_t capacity, int64_t n_ids, int32_t* ids, int64_t* frequency,
+                    int64_t* doc_frequency, void* counter, esr_stream_t stream);
+int esr_terms_lookup_build(const int32_t* keys, const int32_t* values, int64_t K, void* table, int64_t capacity,
+                           esr_stream_t stream);
+int esr_terms_lookup(const int32_t* tokens, int64_t N, const void* lookup, int64_t lookup_capacity, int mode,
+                     int32_t size, const int32_t* oov_bucket, int32_t* out, void* fail, esr_stream_t stream);
+int esr_terms_tfidf_rows(const void* scratch, int64_t capacity, const int32_t* index, const int32_t* row_off,
+                         int64_t nrows, int64_t nnz, const double* idf, int64_t K, float* tfidf, esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
