@@ -860,11 +860,12 @@ __global__ __launch_bounds__(kBlock) void glove_step_kernel(
 }
 
 // the versioned read-modify-write of one row with its summed gradient g: the row was read where `code` says it lives
-// (`own`), its new value goes to the OTHER buffer and the byte flips (nobody reads `loc` during this launch: the plan
-// kernel resolved every address).  `a` = the row's accumulator, loaded by the caller next to `own`.
+// (`own`), its new value goes to the OTHER buffer and the byte flips and takes this step's stamp, as on every other path
+// (nobody reads `loc` during this launch: the resolve kernel resolved every address).  `a` = the row's accumulator,
+// loaded by the caller next to `own`.
 template <int VEC, int NCH, class TR>
 __device__ __forceinline__ void step_apply_resolved(TR* __restrict__ emb0, TR* __restrict__ emb1, uint8_t* __restrict__ loc,
-                                           float* __restrict__ accum, uint32_t code, const RowRegs<VEC, NCH>& own,
+                                           float* __restrict__ accum, uint32_t code, uint32_t T, const RowRegs<VEC, NCH>& own,
                                            RowRegs<VEC, NCH>& a, const RowRegs<VEC, NCH>& g, int D, int lig, int G,
                                            int nvec, float lr, float eps) {
   const int64_t id = code & kIdMask;
@@ -872,7 +873,7 @@ __device__ __forceinline__ void step_apply_resolved(TR* __restrict__ emb0, TR* _
   row_adagrad(w, a, g, lr, eps);
   row_store(a, accum + id * D, lig, G, nvec);
   row_store(w, ((code & kLocBit) ? emb0 : emb1) + id * D, lig, G, nvec);
-  if (lig == 0) loc[id] = (code & kLocBit) ? 0 : 1;
+  if (lig == 0) loc[id] = loc_written((code & kLocBit) ? 0u : 1u, T);
 }
 
 // update, RESOLVED records (long lists; round 2's kernel as it was: the templated in-kernel-resolution variant below
@@ -887,7 +888,7 @@ template <int VEC, int NCH, class TR>
 __global__ __launch_bounds__(kBlock) void glove_step_resolved_kernel(
     TR* __restrict__ emb0, TR* __restrict__ emb1, uint8_t* __restrict__ loc, float* __restrict__ accum, int D,
     int G, const uint32_t* __restrict__ own_code, const float4* __restrict__ meta, int64_t n, int64_t B, int mode,
-    int nstat, const double* __restrict__ stat_part, float lr, float eps, float* __restrict__ chunk_rows,
+    uint32_t T, int nstat, const double* __restrict__ stat_part, float lr, float eps, float* __restrict__ chunk_rows,
     double2* __restrict__ bias_info, double* __restrict__ pair_part, int* __restrict__ long_flag,
     uint32_t* __restrict__ start_flag, uint32_t start_value) {
   __shared__ double sm[16];
@@ -1009,7 +1010,7 @@ __global__ __launch_bounds__(kBlock) void glove_step_resolved_kernel(
     const bool ends = q == n || ((q == p + 1 ? code_n : own_code[q]) & kIdMask) != id;
     if (lig == 0) bias_info[p] = make_double2(bsum, (double)(e_run - p));
     if (head && ends) {
-      step_apply_resolved<VEC, NCH, TR>(emb0, emb1, loc, accum, code, own, a, g, D, lig, G, nvec, lr, eps);
+      step_apply_resolved<VEC, NCH, TR>(emb0, emb1, loc, accum, code, T, own, a, g, D, lig, G, nvec, lr, eps);
     } else {  // a chunk of a long run: park the partial sum for glove_step_long_kernel
       const int64_t slot = 2 * (p / kStepChunk) + (head ? 1 : 0);
       row_store(g, chunk_rows + slot * D, lig, G, nvec);
@@ -1379,7 +1380,7 @@ static void launch_glove_step_t(const GloveTables& t, const int32_t* inputs, con
       grid = std::min(grid, resident);
       ESR_KT("glove_step_resolved_kernel", st, hipLaunchKernelGGL((glove_step_resolved_kernel<VEC, NCH, T>), dim3(grid), dim3(kBlock), 0, st, (T*)t.emb, (T*)t.emb_shadow,
                          t.emb_loc, t.emb_accum, D, g.G, (const uint32_t*)ws.own_code, (const float4*)ws.meta_res, n, B,
-                         mode, nstat, (const double*)ws.stat_part, lr, eps, ws.chunk_rows, ws.bias_info, ws.pair_part,
+                         mode, stamp, nstat, (const double*)ws.stat_part, lr, eps, ws.chunk_rows, ws.bias_info, ws.pair_part,
                          ws.res_flags, start_flag, start_value));
       // (its last workgroup also reduces the loss partials for the finalize kernel; when the caller knows that no run
       // outgrows its head chunk -- long_runs == 0 -- it is skipped and every finalize workgroup reduces them itself,
