@@ -43,11 +43,7 @@ struct WindowWeights {
 };
 
 // One lane per position q of [tok_begin, tok_end); it walks the W positions behind q inside q's document.  For one
-// distance d every lane of a wave adds the same weight, so equal keys in the wave are merged first: the lowest live lane
-// broadcasts its key, the lanes that hold the same key are counted by a ballot and that lane makes ONE table access
-// for all of them.  A few such rounds take the frequent pairs (a frequent token repeats inside any window); what is
-// left goes lane by lane.
-constexpr int kMergeRounds = 4;
+// distance d every lane of a wave adds the same weight, so equal keys in the wave are merged first (wave_merge_add).
 __global__ __launch_bounds__(kBlock) void cooccur_accumulate_kernel(const int32_t* __restrict__ tokens, int64_t N,
                                                                    const int64_t* __restrict__ doc_offsets,
                                                                    int64_t ndocs, int64_t tok_begin, int64_t tok_end,
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(kBlock) void cooccur_accumulate_kernel(const int32_
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t first = doc_offsets[0], last = doc_offsets[ndocs];
   if (blockIdx.x == 0 && threadIdx.x == 0 && (first < 0 || last > N || first > last)) atomicOr(t.fail, kFailBadOffsets);
-  // (whole waves stay in the loop together: the ballots below need every lane of the wave)
+  // (whole waves stay in the loop together: wave_merge_add needs every lane of the wave)
   const int64_t span = tok_end - tok_begin;
   const int64_t rounds = (span + (int64_t)gridDim.x * kBlock - 1) / ((int64_t)gridDim.x * kBlock);
   for (int64_t r = 0; r < rounds; ++r) {
@@ -64,13 +60,7 @@ __global__ __launch_bounds__(kBlock) void cooccur_accumulate_kernel(const int32_
     int64_t start = q;
     int32_t tq = 0;
     if (in_doc) {
-      // the document of q: the first k in [1, ndocs] with doc_offsets[k] > q (empty documents repeat an offset)
-      int64_t lo = 1, hi = ndocs;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (doc_offsets[mid] > q) hi = mid; else lo = mid + 1;
-      }
-      start = doc_offsets[lo - 1];
+      start = doc_offsets[doc_of(doc_offsets, 1, ndocs, q) - 1];
       start = start < 0 ? 0 : (start > q ? q : start);        // whatever the offsets hold, every read stays in [0, q]
       tq = tokens[q];
       if (tq < 0) atomicOr(t.fail, kFailNegativeId);
@@ -87,25 +77,14 @@ __global__ __launch_bounds__(kBlock) void cooccur_accumulate_kernel(const int32_
         const uint32_t hi = (uint32_t)(tq > tp ? tq : tp), lo = (uint32_t)(tq > tp ? tp : tq);
         key = ((unsigned long long)hi << 32) | lo;
       }
-      const unsigned long long w = ww.w[d];
-      for (int m = 0; m < kMergeRounds; ++m) {
-        const unsigned long long alive = __ballot(live);
-        if (!alive) break;
-        const int leader = __ffsll((long long)alive) - 1;
-        const unsigned long long lk = __shfl(key, leader, kWave);
-        const bool same = live && key == lk;
-        const int cnt = __popcll(__ballot(same));
-        if (lane == leader) table_add(t, lk, w * (unsigned long long)cnt);
-        if (same) live = false;
-      }
-      if (live) table_add(t, key, w);
+      wave_merge_add(t, live, key, ww.w[d], lane);
     }
   }
 }
 
 __global__ __launch_bounds__(kBlock) void cooccur_rehash_kernel(CooccurTable src, CooccurTable dst) {
   const int64_t cap = (int64_t)src.mask + 1;
-  if (blockIdx.x == 0 && threadIdx.x == 0 && *src.fail) atomicOr(dst.fail, *src.fail);
+  carry_fail(src, dst);
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < cap; i += (int64_t)gridDim.x * kBlock) {
     const unsigned long long k = src.keys[i];
     if (k != kEmptyKey) table_add(dst, k, src.sums[i]);
@@ -120,11 +99,8 @@ __global__ __launch_bounds__(kBlock) void cooccur_compact_kernel(CooccurTable t,
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < cap; i += (int64_t)gridDim.x * kBlock) {
     const unsigned long long k = t.keys[i];
     if (k == kEmptyKey) continue;
-    const unsigned long long pos = atomicAdd(counter, 1ull);
-    if (pos >= (unsigned long long)nnz) {  // the caller's nnz is not the table's: nothing is written out of bounds
-      atomicOr(t.fail, kFailCompactOverflow);
-      continue;
-    }
+    unsigned long long pos;
+    if (!compact_claim(t, counter, nnz, pos)) continue;
     index[pos] = (int32_t)(k >> 32);
     other[pos] = (int32_t)(uint32_t)k;
     sum[pos] = t.sums[i];
@@ -194,8 +170,7 @@ size_t esr_cooccur_table_bytes(int64_t capacity) {
 }
 
 int esr_cooccur_table_init(void* table, int64_t capacity, esr_stream_t stream) {
-  ESR_REQUIRE(pow2(capacity) && capacity >= 2, "esr_cooccur_table_init: capacity=%lld is not a power of two >= 2",
-              (long long)capacity);
+  ESR_REQUIRE_TABLE("esr_cooccur_table_init", "capacity", capacity);
   ESR_REQUIRE(table && ((uintptr_t)table & 15) == 0, "esr_cooccur_table_init: null (or misaligned) table");
   hipStream_t st = as_stream(stream);
   ESR_KT("cooccur_init", st,
@@ -211,8 +186,7 @@ int esr_cooccur_accumulate(const int32_t* tokens, int64_t N, const int64_t* doc_
   ESR_REQUIRE(context_window >= 1 && context_window <= kCooccurMaxW,
               "esr_cooccur_accumulate: context_window=%d not in [1, %d] (lcm(1..W) must leave room in a uint64 sum)",
               context_window, kCooccurMaxW);
-  ESR_REQUIRE(pow2(capacity) && capacity >= 2, "esr_cooccur_accumulate: capacity=%lld is not a power of two >= 2",
-              (long long)capacity);
+  ESR_REQUIRE_TABLE("esr_cooccur_accumulate", "capacity", capacity);
   ESR_REQUIRE(N >= 0 && ndocs >= 0, "esr_cooccur_accumulate: negative size N=%lld ndocs=%lld", (long long)N,
               (long long)ndocs);
   ESR_REQUIRE(0 <= tok_begin && tok_begin <= tok_end && tok_end <= N,
@@ -235,7 +209,7 @@ int esr_cooccur_accumulate(const int32_t* tokens, int64_t N, const int64_t* doc_
 int esr_cooccur_rehash(const void* table, int64_t capacity, void* new_table, int64_t new_capacity,
                        esr_stream_t stream) {
   TraceScope trace_scope_("esr_cooccur_rehash");
-  ESR_REQUIRE(pow2(capacity) && capacity >= 2 && pow2(new_capacity) && new_capacity >= capacity,
+  ESR_REQUIRE(table_capacity_ok(capacity) && table_capacity_ok(new_capacity) && new_capacity >= capacity,
               "esr_cooccur_rehash: capacities %lld -> %lld must be powers of two >= 2 that do not shrink",
               (long long)capacity, (long long)new_capacity);
   ESR_REQUIRE(table && new_table && table != new_table && ((uintptr_t)new_table & 15) == 0,
@@ -257,8 +231,7 @@ int esr_cooccur_finalize(void* table, int64_t capacity, int64_t nnz, int64_t num
   TraceScope trace_scope_("esr_cooccur_finalize");
   ESR_REQUIRE(context_window >= 1 && context_window <= kCooccurMaxW,
               "esr_cooccur_finalize: context_window=%d not in [1, %d]", context_window, kCooccurMaxW);
-  ESR_REQUIRE(pow2(capacity) && capacity >= 2, "esr_cooccur_finalize: capacity=%lld is not a power of two >= 2",
-              (long long)capacity);
+  ESR_REQUIRE_TABLE("esr_cooccur_finalize", "capacity", capacity);
   ESR_REQUIRE(nnz >= 0 && nnz <= capacity && nnz < ((int64_t)1 << 30) && num_ids > 0 &&
                   num_ids <= ((int64_t)1 << 31),
               "esr_cooccur_finalize: bad sizes nnz=%lld (capacity %lld) num_ids=%lld", (long long)nnz,

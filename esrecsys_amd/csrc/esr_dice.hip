@@ -249,8 +249,7 @@ int esr_dice_accumulate(const int32_t* indices, int64_t N, const int64_t* doc_of
                         int64_t doc_begin, int64_t doc_end, void* table, int64_t capacity, void* workspace,
                         size_t workspace_bytes, esr_stream_t stream) {
   TraceScope trace_scope_("esr_dice_accumulate");
-  ESR_REQUIRE(pow2(capacity) && capacity >= 2, "esr_dice_accumulate: capacity=%lld is not a power of two >= 2",
-              (long long)capacity);
+  ESR_REQUIRE_TABLE("esr_dice_accumulate", "capacity", capacity);
   ESR_REQUIRE(N >= 0 && ndocs >= 0, "esr_dice_accumulate: negative size N=%lld ndocs=%lld", (long long)N,
               (long long)ndocs);
   ESR_REQUIRE(0 <= doc_begin && doc_begin <= doc_end && doc_end <= ndocs,

@@ -25,21 +25,6 @@
 namespace esr {
 
 constexpr unsigned long long kFailBadBucket = 32;  // esr_terms_lookup's own word: an oov bucket outside [0, 65536)
-constexpr int kTermsMergeRounds = 4;
-
-// the sum of `key`, or false when the table does not hold it.  Read-only: the table is complete when this runs.
-__device__ __forceinline__ bool table_find(const CooccurTable& t, unsigned long long key, unsigned long long& sum) {
-  unsigned long long slot = mix64(key) & t.mask;
-  for (unsigned long long probes = 0; probes <= t.mask; ++probes, slot = (slot + 1) & t.mask) {
-    const unsigned long long k = t.keys[slot];
-    if (k == key) {
-      sum = t.sums[slot];
-      return true;
-    }
-    if (k == kEmptyKey) return false;
-  }
-  return false;
-}
 
 __global__ __launch_bounds__(kBlock) void terms_accumulate_kernel(const int32_t* __restrict__ tokens,
                                                                  const int64_t* __restrict__ doc_offsets,
@@ -52,7 +37,7 @@ __global__ __launch_bounds__(kBlock) void terms_accumulate_kernel(const int32_t*
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(t.fail, kFailBadOffsets);
     return;
   }
-  // (whole waves stay in the loop together: the ballots below need every lane of the wave)
+  // (whole waves stay in the loop together: wave_merge_add needs every lane of the wave)
   const int64_t span = tok_end - tok_begin;
   const int64_t rounds = (span + (int64_t)gridDim.x * kBlock - 1) / ((int64_t)gridDim.x * kBlock);
   for (int64_t r = 0; r < rounds; ++r) {
@@ -60,12 +45,7 @@ __global__ __launch_bounds__(kBlock) void terms_accumulate_kernel(const int32_t*
     bool live = q < tok_end;
     unsigned long long key = 0;
     if (live) {
-      // the document of q: the first k in (doc_begin, doc_end] with doc_offsets[k] > q (empty documents repeat an offset)
-      int64_t lo = doc_begin + 1, hi = doc_end;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (doc_offsets[mid] > q) hi = mid; else lo = mid + 1;
-      }
+      const int64_t doc = doc_of(doc_offsets, doc_begin + 1, doc_end, q) - 1 - doc_begin;  // in the launch
       const int32_t tok = tokens[q];
       unsigned long long id = (unsigned long long)(uint32_t)tok;
       if (tok < 0) {
@@ -74,25 +54,15 @@ __global__ __launch_bounds__(kBlock) void terms_accumulate_kernel(const int32_t*
       } else if (use_lookup) {
         live = table_find(lookup, id, id);
       }
-      key = ((unsigned long long)(lo - 1 - doc_begin) << 32) | id;
+      key = ((unsigned long long)doc << 32) | id;
     }
-    for (int m = 0; m < kTermsMergeRounds; ++m) {
-      const unsigned long long alive = __ballot(live);
-      if (!alive) break;
-      const int leader = __ffsll((long long)alive) - 1;
-      const unsigned long long lk = __shfl(key, leader, kWave);
-      const bool same = live && key == lk;
-      const int cnt = __popcll(__ballot(same));
-      if (lane == leader) table_add(t, lk, (unsigned long long)cnt);
-      if (same) live = false;
-    }
-    if (live) table_add(t, key, 1ull);
+    wave_merge_add(t, live, key, 1ull, lane);
   }
 }
 
 __global__ __launch_bounds__(kBlock) void terms_fold_kernel(CooccurTable scratch, CooccurTable t) {
   const int64_t cap = (int64_t)scratch.mask + 1;
-  if (blockIdx.x == 0 && threadIdx.x == 0 && *scratch.fail) atomicOr(t.fail, *scratch.fail);
+  carry_fail(scratch, t);
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < cap; i += (int64_t)gridDim.x * kBlock) {
     const unsigned long long k = scratch.keys[i];
     if (k == kEmptyKey) continue;
@@ -110,11 +80,8 @@ __global__ __launch_bounds__(kBlock) void terms_stats_kernel(CooccurTable t, int
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < cap; i += (int64_t)gridDim.x * kBlock) {
     const unsigned long long k = t.keys[i];
     if (k == kEmptyKey || (uint32_t)k != 0u) continue;
-    const unsigned long long pos = atomicAdd(counter, 1ull);
-    if (pos >= (unsigned long long)n_ids) {  // the caller's count is not the table's: nothing is written out of bounds
-      atomicOr(t.fail, kFailCompactOverflow);
-      continue;
-    }
+    unsigned long long pos;
+    if (!compact_claim(t, counter, n_ids, pos)) continue;
     unsigned long long df = 0;
     table_find(t, k | 1ull, df);
     ids[pos] = (int32_t)(k >> 32);
@@ -216,10 +183,8 @@ int esr_terms_accumulate(const int32_t* tokens, int64_t N, const int64_t* doc_of
                          int64_t doc_end, int64_t tok_begin, int64_t tok_end, const void* lookup,
                          int64_t lookup_capacity, void* scratch, int64_t capacity, esr_stream_t stream) {
   TraceScope trace_scope_("esr_terms_accumulate");
-  ESR_REQUIRE(pow2(capacity) && capacity >= 2, "esr_terms_accumulate: capacity=%lld is not a power of two >= 2",
-              (long long)capacity);
-  ESR_REQUIRE(!lookup || (pow2(lookup_capacity) && lookup_capacity >= 2),
-              "esr_terms_accumulate: lookup_capacity=%lld is not a power of two >= 2", (long long)lookup_capacity);
+  ESR_REQUIRE_TABLE("esr_terms_accumulate", "capacity", capacity);
+  if (lookup) ESR_REQUIRE_TABLE("esr_terms_accumulate", "lookup_capacity", lookup_capacity);
   ESR_REQUIRE(N >= 0 && ndocs >= 0, "esr_terms_accumulate: negative size N=%lld ndocs=%lld", (long long)N,
               (long long)ndocs);
   ESR_REQUIRE(0 <= doc_begin && doc_begin <= doc_end && doc_end <= ndocs,
@@ -244,7 +209,7 @@ int esr_terms_accumulate(const int32_t* tokens, int64_t N, const int64_t* doc_of
 
 int esr_terms_fold(const void* scratch, int64_t scratch_capacity, void* table, int64_t capacity, esr_stream_t stream) {
   TraceScope trace_scope_("esr_terms_fold");
-  ESR_REQUIRE(pow2(scratch_capacity) && scratch_capacity >= 2 && pow2(capacity) && capacity >= 2,
+  ESR_REQUIRE(table_capacity_ok(scratch_capacity) && table_capacity_ok(capacity),
               "esr_terms_fold: capacities %lld, %lld must be powers of two >= 2", (long long)scratch_capacity,
               (long long)capacity);
   ESR_REQUIRE(scratch && table && scratch != table, "esr_terms_fold: null or aliased table");
@@ -258,8 +223,7 @@ int esr_terms_fold(const void* scratch, int64_t scratch_capacity, void* table, i
 int esr_terms_stats(void* table, int64_t capacity, int64_t n_ids, int32_t* ids, int64_t* frequency,
                     int64_t* doc_frequency, void* counter, esr_stream_t stream) {
   TraceScope trace_scope_("esr_terms_stats");
-  ESR_REQUIRE(pow2(capacity) && capacity >= 2, "esr_terms_stats: capacity=%lld is not a power of two >= 2",
-              (long long)capacity);
+  ESR_REQUIRE_TABLE("esr_terms_stats", "capacity", capacity);
   ESR_REQUIRE(n_ids >= 0 && 2 * n_ids <= capacity, "esr_terms_stats: n_ids=%lld needs two slots each of capacity %lld",
               (long long)n_ids, (long long)capacity);
   ESR_REQUIRE(table, "esr_terms_stats: null pointer");
@@ -278,7 +242,7 @@ int esr_terms_stats(void* table, int64_t capacity, int64_t n_ids, int32_t* ids, 
 int esr_terms_lookup_build(const int32_t* keys, const int32_t* values, int64_t K, void* table, int64_t capacity,
                            esr_stream_t stream) {
   TraceScope trace_scope_("esr_terms_lookup_build");
-  ESR_REQUIRE(pow2(capacity) && capacity >= 2 && K >= 0 && 2 * K <= capacity,
+  ESR_REQUIRE(table_capacity_ok(capacity) && K >= 0 && 2 * K <= capacity,
               "esr_terms_lookup_build: capacity=%lld must be a power of two >= max(2, 2 K), K=%lld", (long long)capacity,
               (long long)K);
   ESR_REQUIRE(table, "esr_terms_lookup_build: null pointer");
@@ -294,8 +258,7 @@ int esr_terms_lookup_build(const int32_t* keys, const int32_t* values, int64_t K
 int esr_terms_lookup(const int32_t* tokens, int64_t N, const void* lookup, int64_t lookup_capacity, int mode,
                      int32_t size, const int32_t* oov_bucket, int32_t* out, void* fail, esr_stream_t stream) {
   TraceScope trace_scope_("esr_terms_lookup");
-  ESR_REQUIRE(pow2(lookup_capacity) && lookup_capacity >= 2,
-              "esr_terms_lookup: lookup_capacity=%lld is not a power of two >= 2", (long long)lookup_capacity);
+  ESR_REQUIRE_TABLE("esr_terms_lookup", "lookup_capacity", lookup_capacity);
   ESR_REQUIRE(mode == 0 || mode == 1, "esr_terms_lookup: mode=%d not 0 (index) or 1 (embedding index)", mode);
   ESR_REQUIRE(N >= 0 && size >= 0 && size <= INT32_MAX - 65537, "esr_terms_lookup: bad sizes N=%lld size=%d",
               (long long)N, (int)size);
@@ -313,8 +276,7 @@ int esr_terms_lookup(const int32_t* tokens, int64_t N, const void* lookup, int64
 int esr_terms_tfidf_rows(const void* scratch, int64_t capacity, const int32_t* index, const int32_t* row_off,
                          int64_t nrows, int64_t nnz, const double* idf, int64_t K, float* tfidf, esr_stream_t stream) {
   TraceScope trace_scope_("esr_terms_tfidf_rows");
-  ESR_REQUIRE(pow2(capacity) && capacity >= 2, "esr_terms_tfidf_rows: capacity=%lld is not a power of two >= 2",
-              (long long)capacity);
+  ESR_REQUIRE_TABLE("esr_terms_tfidf_rows", "capacity", capacity);
   ESR_REQUIRE(nrows >= 0 && nrows <= (int64_t)INT32_MAX && nnz >= 0 && nnz <= (int64_t)INT32_MAX && K >= 0,
               "esr_terms_tfidf_rows: bad sizes nrows=%lld nnz=%lld K=%lld", (long long)nrows, (long long)nnz,
               (long long)K);

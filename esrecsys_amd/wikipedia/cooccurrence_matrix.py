@@ -22,6 +22,8 @@ import threading
 
 import numpy as np
 
+from .wire import read_varint
+
 _IO_LIB = None
 
 
@@ -62,37 +64,26 @@ def decode_lines(text, cap=None):
     return t1[:got], t2[:got], cnt[:got], consumed.value
 
 
-def _varint(buf, pos):
-    result, shift = 0, 0
-    while True:
-        b = buf[pos]
-        pos += 1
-        result |= (b & 0x7F) << shift
-        if b < 0x80:
-            return result, pos
-        shift += 7
-
-
 def parse_cooccurrence_row(serialized):
     """Decode one CooccurrenceRow.  Returns (index, other_index list, count list)."""
     buf = memoryview(serialized)
     n, pos = len(buf), 0
     index, others, counts = 0, [], []
     while pos < n:
-        key, pos = _varint(buf, pos)
+        key, pos = read_varint(buf, pos)
         field, wire = key >> 3, key & 7
         if wire == 0:  # varint
-            val, pos = _varint(buf, pos)
+            val, pos = read_varint(buf, pos)
             if field == 1:
                 index = val
             elif field == 2:
                 others.append(val)
         elif wire == 2:  # length-delimited: packed repeated field
-            ln, pos = _varint(buf, pos)
+            ln, pos = read_varint(buf, pos)
             end = pos + ln
             if field == 2:
                 while pos < end:
-                    val, pos = _varint(buf, pos)
+                    val, pos = read_varint(buf, pos)
                     others.append(val)
             elif field == 3:
                 counts.extend(struct.unpack_from("<%df" % (ln // 4), buf, pos))

@@ -20,15 +20,13 @@ squares differs by at most about n 2^-53 relative, which can move the float32 ro
 Only the token part of ``SparseDocument`` is made here: ``primary_index`` is the caller's (a title-dictionary lookup,
 ``Dictionary.index_of`` of the title ids), the secondary titles and the url are left out.
 """
-import base64
-import bz2
-
 import numpy as np
 import torch
 
 from .. import ops
-from .make_cooccurrence import CooccurrenceError, _packed_varints, _pow2_at_least, _varint
-from .make_dictionary import _device_inputs, _failure_text, plan_launches
+from .make_dictionary import FAILURES, plan_launches, token_inputs
+from .pair_table import PairTable
+from .wire import packed_varints, varint, write_lines
 
 
 def idf_table(doc_frequency, max_doc_frequency):
@@ -55,9 +53,12 @@ class TfidfBuilder:
         self.stopwords = frozenset(int(s) for s in stopwords) if stopwords else frozenset()
         self.max_tokens_per_launch = max(int(max_tokens_per_launch), 1)
         self.launches = 0
-        self._failed = None
+        self._scratch = self._new_scratch()   # the last launch's: it holds the failed state
         self._lookup = None     # made at the first launch: a refused transform touches no device
         self._idf = None
+
+    def _new_scratch(self):
+        return PairTable(2, self.device, FAILURES, "tf-idf scratch table")
 
     def _prepare(self):
         if self._lookup is None:
@@ -68,10 +69,9 @@ class TfidfBuilder:
     def transform(self, tokens, doc_offsets):
         """(out_offsets int64[ndocs + 1], token_index int32[nnz], token_tfidf float32[nnz]) on the device: row d is
         ``[out_offsets[d], out_offsets[d + 1])``, ascending by index."""
-        if self._failed is not None:
-            raise CooccurrenceError("this builder is unusable: " + self._failed)
+        self._scratch.check_usable()
+        tokens, off_host, off_dev = token_inputs(tokens, doc_offsets, self.device)
         with torch.cuda.device(self.device):
-            tokens, off_host, off_dev = _device_inputs(tokens, doc_offsets, self.device)
             ndocs = off_host.size - 1
             K = self.dictionary.size
             pieces_off = [torch.zeros(1, dtype=torch.int64, device=self.device)]
@@ -83,15 +83,12 @@ class TfidfBuilder:
                 if n:
                     self._prepare()
                     lookup, lookup_capacity = self._lookup
-                    capacity = _pow2_at_least(2 * n)
-                    scratch = ops.cooccur_table(capacity, self.device)
+                    self._scratch = self._new_scratch().reserve(2 * n)
+                    scratch, capacity = self._scratch.tensor, self._scratch.capacity
                     ops.terms_accumulate(scratch, capacity, tokens, off_dev, a, b, int(off_host[a]), int(off_host[b]),
                                          lookup, lookup_capacity)
                     self.launches += 1
-                    used, fail = ops.cooccur_header(scratch)
-                    if fail:
-                        self._failed = _failure_text(fail)
-                        raise CooccurrenceError("tf-idf scratch table failure (bits %d): %s" % (fail, self._failed))
+                    used = self._scratch.sync()
                 if used == 0:
                     pieces_off.append(torch.full((rows,), base, dtype=torch.int64, device=self.device))
                     continue
@@ -117,13 +114,13 @@ def encode_sparse_document(primary_index, token_index, token_tfidf):
     and 5 packed (left out when empty)."""
     out = bytearray()
     if primary_index:
-        out += b"\x10" + _varint(int(primary_index))
+        out += b"\x10" + varint(int(primary_index))
     if len(token_index):
-        body = _packed_varints(token_index)
-        out += b"\x22" + _varint(len(body)) + body
+        body = packed_varints(token_index)
+        out += b"\x22" + varint(len(body)) + body
     if len(token_tfidf):
         body = np.asarray(token_tfidf, dtype="<f4").tobytes()
-        out += b"\x2a" + _varint(len(body)) + body
+        out += b"\x2a" + varint(len(body)) + body
     return bytes(out)
 
 
@@ -139,8 +136,5 @@ def write_sparse_docs(path, primary_index, out_offsets, token_index, token_tfidf
     primary_index = primary_index.cpu().numpy() if isinstance(primary_index, torch.Tensor) else np.asarray(primary_index)
     if primary_index.size != ndocs:
         raise ValueError("primary_index must hold one index per document: %d for %d" % (primary_index.size, ndocs))
-    with bz2.open(path, "wb") as f:
-        for d in range(ndocs):
-            a, b = int(out_offsets[d]), int(out_offsets[d + 1])
-            f.write(base64.b64encode(encode_sparse_document(primary_index[d], token_index[a:b], token_tfidf[a:b])) + b"\n")
-    return ndocs
+    return write_lines(path, (encode_sparse_document(primary_index[d], token_index[out_offsets[d]:out_offsets[d + 1]],
+                                                     token_tfidf[out_offsets[d]:out_offsets[d + 1]]) for d in range(ndocs)))

@@ -17,121 +17,67 @@ forward -- and adds ``1 / |i - j|`` to entry (t[i], t[j]) when t[i] > t[j].  The
 1 / lcm(1..W), uint64: esr_cooccur.hip), so the result does not depend on atomic order or on how the corpus is cut into
 ``add`` calls; ``count = float32(float64(sum) / lcm)``.
 """
-import base64
-import bz2
 import types
 
 import numpy as np
 import torch
 
 from .. import ops
+from .pair_table import CooccurrenceError, PairTable, csr_inputs, pow2_at_least  # noqa: F401 (CooccurrenceError: re-exported)
+from .wire import packed_varints, varint, write_lines
 
 # Flags with the reference's names and defaults (make_cooccurrence.py:23-27; token_dictionary has no part here: ids come
 # in).  input_file is an .npz of `tokens` / `doc_offsets`.
 FLAGS = types.SimpleNamespace(input_file=None, output_file=None, context_window=10, max_row_size=1000)
 
 MAX_CONTEXT_WINDOW = 22   # lcm(1..22) < 2^28: 2^36 window hits fit a uint64 sum
-_FAILURES = {1: "a probe wrapped the whole table (capacity below occupied + emitted pairs)", 2: "a negative token id",
-             4: "doc_offsets outside [0, N]", 8: "finalize: nnz below the table's occupied count"}
-
-
-class CooccurrenceError(RuntimeError):
-    """The device raised the table's failure word; the builder that saw it is unusable."""
-
-
-def _pow2_at_least(n):
-    c = 2
-    while c < n:
-        c <<= 1
-    return c
 
 
 class CooccurrenceBuilder:
     """Reduce-by-key of the window pairs of a corpus in a device hash table (open addressing, 64-bit keys
     ``index << 32 | other``, uint64 fixed-point sums).
 
-    Growth rule: before a launch ``capacity >= occupied + pairs the launch can emit`` (a launch covers a token range of at
-    most ``max_pairs_per_launch / context_window`` positions, each of which emits at most context_window pairs), so a probe
-    always finds its key or an empty slot; after a launch the table doubles until its load factor is at most 1/2.  Growing
-    re-inserts the occupied slots into a new table (esr_cooccur_rehash).  One host sync per launch: this is ETL."""
+    Growth rule (``PairTable``): a launch covers a token range of at most ``max_pairs_per_launch / context_window``
+    positions, each of which emits at most context_window pairs -- that many keys are reserved before it.  The table is
+    made at the first launch."""
 
     def __init__(self, context_window=10, capacity=1 << 20, device=None, max_pairs_per_launch=1 << 26):
         if not 1 <= int(context_window) <= MAX_CONTEXT_WINDOW:
             raise ValueError("context_window must be in [1, %d], got %r" % (MAX_CONTEXT_WINDOW, context_window))
         self.context_window = int(context_window)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.capacity = _pow2_at_least(int(capacity))
         self.max_pairs_per_launch = max(int(max_pairs_per_launch), self.context_window)
-        self.rehashes = 0
-        self._used = 0
         self._max_id = -1
-        self._failed = None
-        with torch.cuda.device(self.device):
-            self._table = ops.cooccur_table(self.capacity, self.device)
+        self._pairs = PairTable(capacity, self.device)
 
-    @property
-    def nnz(self):
-        """Distinct (index, other) pairs so far."""
-        return self._used
-
-    def _check_usable(self):
-        if self._failed is not None:
-            raise CooccurrenceError("this builder is unusable: " + self._failed)
-
-    def _grow_to(self, capacity):
-        if capacity > self.capacity:
-            self._table = ops.cooccur_rehash(self._table, self.capacity, capacity)
-            self.capacity = capacity
-            self.rehashes += 1
-
-    def _sync_header(self):
-        used, fail = ops.cooccur_header(self._table)
-        if fail:
-            self._failed = "; ".join(msg for bit, msg in _FAILURES.items() if fail & bit)
-            raise CooccurrenceError("co-occurrence table failure (bits %d): %s" % (fail, self._failed))
-        self._used = used
+    capacity = property(lambda self: self._pairs.capacity)
+    rehashes = property(lambda self: self._pairs.rehashes)
+    nnz = property(lambda self: self._pairs.used, doc="Distinct (index, other) pairs so far.")
 
     def add(self, tokens, doc_offsets):
         """Adds the documents ``tokens[doc_offsets[d]:doc_offsets[d + 1]]`` (numpy arrays or device tensors)."""
-        self._check_usable()
-        off_host = doc_offsets.cpu().numpy() if isinstance(doc_offsets, torch.Tensor) else np.asarray(doc_offsets)
-        off_host = np.ascontiguousarray(off_host, dtype=np.int64)
-        if off_host.ndim != 1 or off_host.size < 1:
-            raise ValueError("doc_offsets must be int64 [ndocs + 1]")
+        pairs, W = self._pairs, self.context_window
+        pairs.check_usable()
+        tokens, off_host, off_dev = csr_inputs(tokens, doc_offsets, self.device, "tokens")
+        N = tokens.numel()
+        if N == 0 or off_host.size == 1:
+            return self
         with torch.cuda.device(self.device):
-            tokens = ops.as_ids(tokens, self.device).reshape(-1)
-            N = tokens.numel()
-            if off_host[0] != 0 or off_host[-1] != N or (off_host.size > 1 and np.any(np.diff(off_host) < 0)):
-                raise ValueError("doc_offsets must rise from 0 to len(tokens) = %d" % N)
-            if N == 0 or off_host.size == 1:
-                return self
-            if isinstance(doc_offsets, torch.Tensor) and doc_offsets.is_cuda and doc_offsets.dtype == torch.int64 and \
-                    doc_offsets.is_contiguous():
-                off_dev = doc_offsets
-            else:
-                off_dev = torch.from_numpy(off_host).to(self.device)
-            W = self.context_window
             step = max(1, self.max_pairs_per_launch // W)
             for a in range(0, N, step):
                 b = min(N, a + step)
-                self._grow_to(_pow2_at_least(self._used + (b - a) * W))
-                ops.cooccur_accumulate(self._table, self.capacity, tokens, off_dev, a, b, W)
-                self._sync_header()
-                while 2 * self._used > self.capacity:
-                    self._grow_to(2 * self.capacity)
+                pairs.reserve((b - a) * W)
+                ops.cooccur_accumulate(pairs.tensor, pairs.capacity, tokens, off_dev, a, b, W)
+                pairs.sync()
+                pairs.settle()
             self._max_id = max(self._max_id, int(tokens.max()))
         return self
 
     def finalize(self):
         """(index int32[nnz], other int32[nnz], count float32[nnz]) on the device, ascending by (index, other).  The
         builder stays usable: more ``add`` calls may follow."""
-        self._check_usable()
         with torch.cuda.device(self.device):
-            out = ops.cooccur_finalize(self._table, self.capacity, self._used, self._max_id + 1 if self._used else 1,
-                                       self.context_window)
-            if self._used:
-                self._sync_header()
-        return out
+            return self._pairs.finalize(self._max_id + 1, self.context_window)
 
 
 def pack_docs(docs):
@@ -148,31 +94,9 @@ def process_docs(docs, context_window=10, device=None):
     """``process_doc`` over every document plus the reduce (make_cooccurrence.py:33-55, 95-96): an iterable of embedding
     index lists -> (index, other, count) device tensors ascending by (index, other)."""
     tokens, offsets = pack_docs(docs)
-    builder = CooccurrenceBuilder(context_window, capacity=_pow2_at_least(min(1 << 20, 2 * max(1, tokens.size))),
+    builder = CooccurrenceBuilder(context_window, capacity=pow2_at_least(min(1 << 20, 2 * max(1, tokens.size))),
                                   device=device)
     return builder.add(tokens, offsets).finalize()
-
-
-def _varint(value):
-    out = bytearray()
-    while value > 0x7F:
-        out.append((value & 0x7F) | 0x80)
-        value >>= 7
-    out.append(value)
-    return bytes(out)
-
-
-def _packed_varints(values):
-    """The varints of a uint array back to back (vectorised: an id is at most five bytes here)."""
-    v = np.asarray(values, dtype=np.uint64)
-    nbytes = np.ones(v.shape, np.int64)
-    for k in range(1, 10):
-        nbytes += v >= np.uint64(1 << (7 * k))
-    groups = (v[:, None] >> (np.arange(10, dtype=np.uint64) * np.uint64(7))[None, :]) & np.uint64(0x7F)
-    pos = np.arange(10)[None, :]
-    keep = pos < nbytes[:, None]
-    more = pos < (nbytes[:, None] - 1)
-    return (groups.astype(np.uint8) | (more.astype(np.uint8) << 7))[keep].tobytes()
 
 
 def encode_cooccurrence_row(index, others, counts):
@@ -181,13 +105,13 @@ def encode_cooccurrence_row(index, others, counts):
     (left out when empty)."""
     out = bytearray()
     if index:
-        out += b"\x08" + _varint(int(index))
+        out += b"\x08" + varint(int(index))
     if len(others):
-        body = _packed_varints(others)
-        out += b"\x12" + _varint(len(body)) + body
+        body = packed_varints(others)
+        out += b"\x12" + varint(len(body)) + body
     if len(counts):
         body = np.asarray(counts, dtype="<f4").tobytes()
-        out += b"\x1a" + _varint(len(body)) + body
+        out += b"\x1a" + varint(len(body)) + body
     return bytes(out)
 
 
@@ -212,12 +136,8 @@ def write_cooccurrence(path, index, other, count, max_row_size=1000):
     """Writes (index, other, count) -- grouped by index, as ``finalize`` returns them -- as a ``*.cooccur.pb.b64.bz2``
     line file: one base64 ``CooccurrenceRow`` per line, bz2 (make_cooccurrence.py:80-100).  Returns the line count."""
     index, other, count = (x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x) for x in (index, other, count))
-    lines = 0
-    with bz2.open(path, "wb") as f:
-        for a, b in split_rows(index, max_row_size):
-            f.write(base64.b64encode(encode_cooccurrence_row(index[a], other[a:b], count[a:b])) + b"\n")
-            lines += 1
-    return lines
+    return write_lines(path, (encode_cooccurrence_row(index[a], other[a:b], count[a:b])
+                              for a, b in split_rows(index, max_row_size)))
 
 
 def device_batches(index, other, count, batch_size, generator=None):

@@ -29,30 +29,23 @@ import numpy as np
 import torch
 
 from .. import ops
-from .make_cooccurrence import (CooccurrenceError, _FAILURES as _TABLE_FAILURES, _pow2_at_least, device_batches,  # noqa: F401
-                                pack_docs, split_rows, write_cooccurrence)
+from .make_cooccurrence import device_batches, pack_docs, split_rows, write_cooccurrence  # noqa: F401 (re-exported)
+from .pair_table import (FAILURES as TABLE_FAILURES, CooccurrenceError, PairTable, csr_inputs, host_offsets,  # noqa: F401
+                         plan_ranges, pow2_at_least)
 
 # Flags with the reference's names and defaults (make_dice.py:19-22).  input_file is an .npz of `indices` / `doc_offsets`.
 FLAGS = types.SimpleNamespace(input_file=None, output_file=None, max_row_size=1000)
 
 MAX_DOC = 4096   # esr_dice_max_doc(): ids per document, repeats counted
-_FAILURES = dict(_TABLE_FAILURES)
-_FAILURES[2] = "a negative id"
-_FAILURES[4] = "doc_offsets outside [0, N] (or overlapping documents)"
-_FAILURES[16] = "a document above %d ids" % MAX_DOC
-
-
-def _host_offsets(doc_offsets):
-    off = doc_offsets.cpu().numpy() if isinstance(doc_offsets, torch.Tensor) else np.asarray(doc_offsets)
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("doc_offsets must be int64 [ndocs + 1]")
-    return off
+FAILURES = dict(TABLE_FAILURES)
+FAILURES[2] = "a negative id"
+FAILURES[4] = "doc_offsets outside [0, N] (or overlapping documents)"
+FAILURES[16] = "a document above %d ids" % MAX_DOC
 
 
 def check_doc_sizes(doc_offsets, max_doc=MAX_DOC):
     """Raises ValueError naming the first document of more than max_doc ids.  Host work on doc_offsets alone."""
-    n = np.diff(_host_offsets(doc_offsets))
+    n = np.diff(host_offsets(doc_offsets))
     long_ = np.flatnonzero(n > max_doc)
     if long_.size:
         d = int(long_[0])
@@ -62,7 +55,7 @@ def check_doc_sizes(doc_offsets, max_doc=MAX_DOC):
 
 def pair_bounds(doc_offsets):
     """Per document, what it can add to the table at most: n (n - 1) / 2 pair keys + n diagonal keys (n = its length)."""
-    n = np.diff(_host_offsets(doc_offsets))
+    n = np.diff(host_offsets(doc_offsets))
     return n * (n - 1) // 2 + n
 
 
@@ -70,18 +63,7 @@ def plan_launches(doc_offsets, max_pairs_per_launch):
     """[(doc_begin, doc_end, bound), ...]: consecutive document ranges that cover every document exactly once, each with
     bound = the sum of its documents' pair_bounds <= max_pairs_per_launch -- or holding ONE document, when that document's
     own bound is above the limit (a document is never cut)."""
-    bounds = pair_bounds(doc_offsets)
-    limit = max(int(max_pairs_per_launch), 1)
-    cum = np.concatenate([[0], np.cumsum(bounds)])
-    ndocs = bounds.size
-    plan = []
-    a = 0
-    while a < ndocs:
-        b = int(np.searchsorted(cum, cum[a] + limit, side="right")) - 1   # the last b with cum[b] - cum[a] <= limit
-        b = min(max(b, a + 1), ndocs)
-        plan.append((a, b, int(cum[b] - cum[a])))
-        a = b
-    return plan
+    return plan_ranges(np.concatenate([[0], np.cumsum(pair_bounds(doc_offsets))]), max_pairs_per_launch)
 
 
 class DiceBuilder:
@@ -89,88 +71,52 @@ class DiceBuilder:
     64-bit keys ``index << 32 | other``, uint64 counts).  The document frequencies live in the same table on the diagonal
     keys ``id << 32 | id``, which no pair can make; ``finalize`` and ``doc_frequency`` split them off.
 
-    Growth rule: the host computes ``sum of n (n - 1) / 2 + n`` per document range from ``doc_offsets`` and cuts an ``add``
-    into ranges whose bound is at most ``max_pairs_per_launch`` (``plan_launches``); before a launch
-    ``capacity >= occupied + bound``, so a probe always finds its key or an empty slot; after a launch the table doubles
-    until its load factor is at most 1/2.  One host sync per launch: this is ETL.
+    Growth rule (``PairTable``): the host computes ``sum of n (n - 1) / 2 + n`` per document range from ``doc_offsets``
+    and cuts an ``add`` into ranges whose bound is at most ``max_pairs_per_launch`` (``plan_launches``); that bound is
+    reserved before the launch.
 
     A failure word raised by the device (a negative id in a device tensor, broken offsets) becomes a ``CooccurrenceError``
     and leaves the builder unusable, as in ``CooccurrenceBuilder``."""
 
     def __init__(self, capacity=1 << 20, device=None, max_pairs_per_launch=1 << 26):
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.capacity = _pow2_at_least(int(capacity))
         self.max_pairs_per_launch = max(int(max_pairs_per_launch), 1)
-        self.rehashes = 0
         self.launches = 0
-        self._used = 0
         self._max_id = -1
-        self._failed = None
-        self._table = None      # made at the first launch: a refused add touches no device
+        self._pairs = PairTable(capacity, self.device, FAILURES)
         self._result = None     # (index, other, count, ids, df) of the table as it stands
 
-    def _check_usable(self):
-        if self._failed is not None:
-            raise CooccurrenceError("this builder is unusable: " + self._failed)
-
-    def _grow_to(self, capacity):
-        if self._table is None:
-            self.capacity = max(self.capacity, capacity)
-            self._table = ops.cooccur_table(self.capacity, self.device)
-        elif capacity > self.capacity:
-            self._table = ops.cooccur_rehash(self._table, self.capacity, capacity)
-            self.capacity = capacity
-            self.rehashes += 1
-
-    def _sync_header(self):
-        used, fail = ops.cooccur_header(self._table)
-        if fail:
-            self._failed = "; ".join(msg for bit, msg in _FAILURES.items() if fail & bit)
-            raise CooccurrenceError("co-occurrence table failure (bits %d): %s" % (fail, self._failed))
-        self._used = used
+    capacity = property(lambda self: self._pairs.capacity)
+    rehashes = property(lambda self: self._pairs.rehashes)
 
     def add(self, indices, doc_offsets):
         """Adds the documents ``indices[doc_offsets[d]:doc_offsets[d + 1]]`` (numpy arrays or device tensors)."""
-        self._check_usable()
-        off_host = _host_offsets(doc_offsets)
+        pairs = self._pairs
+        pairs.check_usable()
+        off_host = host_offsets(doc_offsets)
         check_doc_sizes(off_host)
-        n_host = indices.numel() if isinstance(indices, torch.Tensor) else np.asarray(indices).size
-        if off_host[0] != 0 or off_host[-1] != n_host or (off_host.size > 1 and np.any(np.diff(off_host) < 0)):
-            raise ValueError("doc_offsets must rise from 0 to len(indices) = %d" % n_host)
-        if n_host == 0 or off_host.size == 1:
+        indices, off_host, off_dev = csr_inputs(indices, doc_offsets, self.device, "indices", off_host)
+        if indices.numel() == 0 or off_host.size == 1:
             return self
         with torch.cuda.device(self.device):
-            indices = ops.as_ids(indices, self.device).reshape(-1)
-            if isinstance(doc_offsets, torch.Tensor) and doc_offsets.is_cuda and doc_offsets.dtype == torch.int64 and \
-                    doc_offsets.is_contiguous():
-                off_dev = doc_offsets
-            else:
-                off_dev = torch.from_numpy(off_host).to(self.device)
-            ws = ops.dice_workspace(n_host, self.device)
+            ws = ops.dice_workspace(indices.numel(), self.device)
             self._result = None
             for a, b, bound in plan_launches(off_host, self.max_pairs_per_launch):
                 if bound == 0:
                     continue
-                self._grow_to(_pow2_at_least(self._used + bound))
-                ops.dice_accumulate(self._table, self.capacity, indices, off_dev, a, b, ws)
+                pairs.reserve(bound)
+                ops.dice_accumulate(pairs.tensor, pairs.capacity, indices, off_dev, a, b, ws)
                 self.launches += 1
-                self._sync_header()
-                while 2 * self._used > self.capacity:
-                    self._grow_to(2 * self.capacity)
+                pairs.sync()
+                pairs.settle()
             self._max_id = max(self._max_id, int(indices.max()))
         return self
 
     def _finalized(self):
-        self._check_usable()
+        self._pairs.check_usable()
         if self._result is None:
             with torch.cuda.device(self.device):
-                if self._used:
-                    index, other, count = ops.cooccur_finalize(self._table, self.capacity, self._used,
-                                                               self._max_id + 1, 1)
-                    self._sync_header()
-                else:
-                    index = other = torch.empty(0, dtype=torch.int32, device=self.device)
-                    count = torch.empty(0, dtype=torch.float32, device=self.device)
+                index, other, count = self._pairs.finalize(self._max_id + 1)
                 diag = index == other
                 pair = ~diag
                 self._result = (index[pair], other[pair], count[pair], index[diag], count[diag])
@@ -197,7 +143,7 @@ def process_sdocs(docs, device=None):
     index first, then the secondary indices) -> (index, other, count) device tensors ascending by (index, other)."""
     indices, offsets = pack_docs(docs)
     bound = int(pair_bounds(offsets).sum())
-    builder = DiceBuilder(capacity=_pow2_at_least(min(1 << 20, 2 * max(1, bound))), device=device)
+    builder = DiceBuilder(capacity=pow2_at_least(min(1 << 20, 2 * max(1, bound))), device=device)
     return builder.add(indices, offsets).finalize()
 
 

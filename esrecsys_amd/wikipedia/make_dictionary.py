@@ -34,8 +34,9 @@ import numpy as np
 import torch
 
 from .. import ops
-from .make_cooccurrence import CooccurrenceError, _FAILURES as _TABLE_FAILURES, _pow2_at_least, _varint
-from .cooccurrence_matrix import _varint as _read_varint
+from . import pair_table
+from .pair_table import FAILURES as TABLE_FAILURES, PairTable, csr_inputs, failure_text, plan_ranges, pow2_at_least
+from .wire import read_varint, varint, write_lines
 
 # Flags with the reference's names and defaults (make_dictionary.py:19-31; the title dictionary is the same job over the
 # titles: call the same functions with the title flags).  input_file is an .npz of `tokens` / `doc_offsets`.
@@ -43,23 +44,17 @@ FLAGS = types.SimpleNamespace(input_file=None, token_output=None, title_output=N
                               max_token_dictionary_size=500000, max_title_dictionary_size=500000, min_title_frequency=5)
 
 OOV_BUCKETS = 65536
-_FAILURES = dict(_TABLE_FAILURES)
-_FAILURES[2] = "a negative id"
-_FAILURES[4] = "doc_offsets on the device differ from the host's plan"
-_FAILURES[32] = "an oov_bucket outside [0, %d)" % OOV_BUCKETS
+FAILURES = dict(TABLE_FAILURES)
+FAILURES[2] = "a negative id"
+FAILURES[4] = "doc_offsets on the device differ from the host's plan"
+FAILURES[32] = "an oov_bucket outside [0, %d)" % OOV_BUCKETS
 
 
 # ---- host-side argument checks and launch planning (no device) ----
 def host_offsets(doc_offsets, n_tokens):
     """doc_offsets as a host int64 array, checked: one dimension, rising from 0 to n_tokens.  ValueError otherwise --
     before any launch."""
-    off = doc_offsets.cpu().numpy() if isinstance(doc_offsets, torch.Tensor) else np.asarray(doc_offsets)
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("doc_offsets must be int64 [ndocs + 1]")
-    if off[0] != 0 or off[-1] != n_tokens or (off.size > 1 and np.any(np.diff(off) < 0)):
-        raise ValueError("doc_offsets must rise from 0 to len(tokens) = %d" % n_tokens)
-    return off
+    return pair_table.host_offsets(doc_offsets, n_tokens)
 
 
 def check_host_tokens(tokens):
@@ -85,39 +80,13 @@ def plan_launches(doc_offsets, max_tokens_per_launch):
     """[(doc_begin, doc_end, tokens), ...]: consecutive document ranges that cover every document exactly once, each of
     at most max_tokens_per_launch tokens -- or holding ONE document, when that document alone is longer (a document is
     never cut, and there is no cap on its length)."""
-    off = np.asarray(doc_offsets, dtype=np.int64)
-    limit = max(int(max_tokens_per_launch), 1)
-    ndocs = off.size - 1
-    plan = []
-    a = 0
-    while a < ndocs:
-        b = int(np.searchsorted(off, off[a] + limit, side="right")) - 1   # the last b with off[b] - off[a] <= limit
-        b = min(max(b, a + 1), ndocs)
-        plan.append((a, b, int(off[b] - off[a])))
-        a = b
-    return plan
+    return plan_ranges(doc_offsets, max_tokens_per_launch)
 
 
-def _device_inputs(tokens, doc_offsets, device):
-    """(tokens int32 device, offsets host, offsets device) with every host-side check done before the device is touched."""
-    if isinstance(tokens, torch.Tensor):
-        n = tokens.numel()
-        off_host = host_offsets(doc_offsets, n)
-        tokens = ops.as_ids(tokens.to(device), device).reshape(-1)
-    else:
-        host = check_host_tokens(tokens)
-        off_host = host_offsets(doc_offsets, host.size)
-        tokens = torch.from_numpy(host).to(device)
-    if isinstance(doc_offsets, torch.Tensor) and doc_offsets.is_cuda and doc_offsets.dtype == torch.int64 and \
-            doc_offsets.is_contiguous() and doc_offsets.device == tokens.device:
-        off_dev = doc_offsets
-    else:
-        off_dev = torch.from_numpy(off_host).to(device)
-    return tokens, off_host, off_dev
-
-
-def _failure_text(fail):
-    return "; ".join(msg for bit, msg in _FAILURES.items() if fail & bit)
+def token_inputs(tokens, doc_offsets, device):
+    """``csr_inputs`` behind the terms builders' host screen: a host token array goes through ``check_host_tokens``."""
+    return csr_inputs(tokens if isinstance(tokens, torch.Tensor) else check_host_tokens(tokens), doc_offsets, device,
+                      "tokens")
 
 
 class TermStatsBuilder:
@@ -129,80 +98,55 @@ class TermStatsBuilder:
     ``id << 32 | 0`` += tf, ``id << 32 | 1`` += 1.  Contention on a hot id is per document, not per occurrence, and
     nothing persistent grows with the number of documents.
 
-    Growth rule: before a launch the scratch table holds >= 2 x the launch's tokens and the persistent one >= occupied
-    + 2 x the launch's tokens; after it the persistent table doubles until its load factor is at most 1/2
-    (esr_cooccur_rehash).  One host sync per launch: this is ETL.
+    Growth rule (``PairTable``): a launch of n tokens reserves 2 n keys in its scratch table and 2 n more in the
+    persistent one.
 
     A failure word raised by the device (a negative id in a device tensor, offsets that differ) becomes a
     ``CooccurrenceError`` and leaves the builder unusable, as in ``CooccurrenceBuilder``."""
 
     def __init__(self, capacity=1 << 20, device=None, max_tokens_per_launch=1 << 21):
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.capacity = _pow2_at_least(int(capacity))
         self.max_tokens_per_launch = max(int(max_tokens_per_launch), 1)
-        self.rehashes = 0
         self.launches = 0
-        self._used = 0
-        self._failed = None
-        self._table = None      # made at the first launch: a refused add touches no device
+        self._pairs = PairTable(capacity, self.device, FAILURES, "term statistics table")
         self._result = None
 
-    def _check_usable(self):
-        if self._failed is not None:
-            raise CooccurrenceError("this builder is unusable: " + self._failed)
-
-    def _grow_to(self, capacity):
-        if self._table is None:
-            self.capacity = max(self.capacity, capacity)
-            self._table = ops.cooccur_table(self.capacity, self.device)
-        elif capacity > self.capacity:
-            self._table = ops.cooccur_rehash(self._table, self.capacity, capacity)
-            self.capacity = capacity
-            self.rehashes += 1
-
-    def _sync_header(self):
-        used, fail = ops.cooccur_header(self._table)
-        if fail:
-            self._failed = _failure_text(fail)
-            raise CooccurrenceError("term statistics table failure (bits %d): %s" % (fail, self._failed))
-        self._used = used
-
-    @property
-    def num_ids(self):
-        """Distinct ids so far (every id holds two slots of the table)."""
-        return self._used // 2
+    capacity = property(lambda self: self._pairs.capacity)
+    rehashes = property(lambda self: self._pairs.rehashes)
+    num_ids = property(lambda self: self._pairs.used // 2, doc="Distinct ids so far (every id holds two slots of the table).")
 
     def add(self, tokens, doc_offsets):
         """Adds the documents ``tokens[doc_offsets[d]:doc_offsets[d + 1]]`` (numpy arrays or device tensors)."""
-        self._check_usable()
+        pairs = self._pairs
+        pairs.check_usable()
+        tokens, off_host, off_dev = token_inputs(tokens, doc_offsets, self.device)
+        if tokens.numel() == 0 or off_host.size == 1:
+            return self
         with torch.cuda.device(self.device):
-            tokens, off_host, off_dev = _device_inputs(tokens, doc_offsets, self.device)
-            if tokens.numel() == 0 or off_host.size == 1:
-                return self
             self._result = None
             for a, b, n in plan_launches(off_host, self.max_tokens_per_launch):
                 if n == 0:
                     continue
-                scratch_capacity = _pow2_at_least(2 * n)
-                scratch = ops.cooccur_table(scratch_capacity, self.device)
-                self._grow_to(_pow2_at_least(self._used + 2 * n))
-                ops.terms_accumulate(scratch, scratch_capacity, tokens, off_dev, a, b, int(off_host[a]), int(off_host[b]))
-                ops.terms_fold(scratch, scratch_capacity, self._table, self.capacity)
+                scratch = PairTable(2, self.device).reserve(2 * n)   # (its failure word goes into `pairs` with its entries)
+                pairs.reserve(2 * n)
+                ops.terms_accumulate(scratch.tensor, scratch.capacity, tokens, off_dev, a, b, int(off_host[a]),
+                                     int(off_host[b]))
+                ops.terms_fold(scratch.tensor, scratch.capacity, pairs.tensor, pairs.capacity)
                 self.launches += 1
-                self._sync_header()
-                while 2 * self._used > self.capacity:
-                    self._grow_to(2 * self.capacity)
+                pairs.sync()
+                pairs.settle()
         return self
 
     def finalize(self):
         """(ids int32[K], frequency int64[K], doc_frequency int64[K]) on the device, ascending by id.  The builder stays
         usable: more ``add`` calls may follow."""
-        self._check_usable()
+        pairs = self._pairs
+        pairs.check_usable()
         if self._result is None:
             with torch.cuda.device(self.device):
-                if self._used:
-                    ids, frequency, doc_frequency = ops.terms_stats(self._table, self.capacity, self._used // 2)
-                    self._sync_header()
+                if pairs.used:
+                    ids, frequency, doc_frequency = ops.terms_stats(pairs.tensor, pairs.capacity, pairs.used // 2)
+                    pairs.sync()
                     ids, perm = ops.segment_sort(ids, int(ids.max()) + 1)
                     perm = perm.to(torch.int64)
                     self._result = (ids, frequency[perm], doc_frequency[perm])
@@ -251,15 +195,15 @@ class Dictionary:
             if skip is not None and len(skip):
                 keep = ~torch.isin(keys, torch.as_tensor(sorted(int(s) for s in skip), dtype=torch.int32, device=device))
                 keys, values = keys[keep].contiguous(), values[keep].contiguous()
-            capacity = _pow2_at_least(2 * max(1, keys.numel()))
-            table = ops.terms_lookup_table(keys, values, capacity)
-            used, fail = ops.cooccur_header(table)
+            capacity = pow2_at_least(2 * max(1, keys.numel()))
+            lookup = PairTable(capacity, device, tensor=ops.terms_lookup_table(keys, values, capacity))
+            used, fail = lookup.header()
             if fail or used != keys.numel():
                 raise ValueError("dictionary ids must be distinct and >= 0 (%d ids, %d distinct, failure bits %d)"
                                  % (keys.numel(), used, fail))
         if skip is None:
-            self._lookups[device] = (table, capacity)
-        return table, capacity
+            self._lookups[device] = (lookup.tensor, capacity)
+        return lookup.tensor, capacity
 
     def _lookup(self, tokens, mode, oov_bucket, device):
         if isinstance(tokens, torch.Tensor) and tokens.is_cuda:
@@ -284,7 +228,7 @@ class Dictionary:
             out, fail = ops.terms_lookup(tokens, table, capacity, mode, self.size, oov_bucket)
             fail = int(fail)
         if fail:
-            raise ValueError("dictionary lookup refused (bits %d): %s" % (fail, _failure_text(fail)))
+            raise ValueError("dictionary lookup refused (bits %d): %s" % (fail, failure_text(fail, FAILURES)))
         return out
 
     def index_of(self, tokens, device=None):
@@ -326,10 +270,10 @@ def encode_token_stat(token, frequency, doc_frequency, index):
     out = bytearray()
     text = token.encode("utf-8") if isinstance(token, str) else bytes(token)
     if text:
-        out += b"\x0a" + _varint(len(text)) + text
+        out += b"\x0a" + varint(len(text)) + text
     for tag, value in ((b"\x18", frequency), (b"\x20", doc_frequency), (b"\x28", index)):
         if value:
-            out += tag + _varint(int(value))
+            out += tag + varint(int(value))
     return bytes(out)
 
 
@@ -340,14 +284,14 @@ def parse_token_stat(serialized):
     n, pos = len(buf), 0
     token, values = "", {3: 0, 4: 0, 5: 0}
     while pos < n:
-        key, pos = _read_varint(buf, pos)
+        key, pos = read_varint(buf, pos)
         field, wire = key >> 3, key & 7
         if wire == 0:
-            val, pos = _read_varint(buf, pos)
+            val, pos = read_varint(buf, pos)
             if field in values:
                 values[field] = val
         elif wire == 2:
-            ln, pos = _read_varint(buf, pos)
+            ln, pos = read_varint(buf, pos)
             if field == 1:
                 token = bytes(buf[pos:pos + ln]).decode("utf-8")
             pos += ln
@@ -367,10 +311,8 @@ def write_dictionary(path, dictionary, token_of):
     get = token_of if callable(token_of) else token_of.__getitem__
     ids, frequency, doc_frequency = (x.cpu().tolist() for x in (dictionary.ids, dictionary.frequency,
                                                                 dictionary.doc_frequency))
-    with bz2.open(path, "wb") as f:
-        for index, (raw, fr, df) in enumerate(zip(ids, frequency, doc_frequency)):
-            f.write(base64.b64encode(encode_token_stat(get(raw), fr, df, index)) + b"\n")
-    return len(ids)
+    return write_lines(path, (encode_token_stat(get(raw), fr, df, index)
+                              for index, (raw, fr, df) in enumerate(zip(ids, frequency, doc_frequency))))
 
 
 def read_dictionary(path):

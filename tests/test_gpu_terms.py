@@ -121,7 +121,7 @@ def test_bad_input_is_refused_on_the_host_before_any_launch(dev):
             b.add(torch.from_numpy(tokens).to(dev), torch.tensor(off, dtype=torch.int64, device=dev))
     with pytest.raises(ValueError, match="token ids"):
         b.add(np.array([1, -2, 3], np.int32), np.array([0, 3], np.int64))
-    assert b.launches == 0 and b._table is None
+    assert b.launches == 0 and b.rehashes == 0 and b.capacity == 64 and b._pairs.tensor is None
     b.add(tokens, np.array([0, 3], np.int64))                     # a refusal on the host leaves the builder usable
     assert b.finalize()[0].tolist() == [1, 2, 3]
 

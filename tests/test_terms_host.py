@@ -107,6 +107,69 @@ def test_plan_with_empty_documents_and_none():
     assert _check_plan(np.array([0, 4, 8], np.int64), 4) == [(0, 1, 4), (1, 2, 4)]
 
 
+# ---- the shared planner (wikipedia/pair_table.py), on the inputs of the two plan_launches tests ----
+def _dice_plan_offsets(limit):
+    """test_dice_host.py's input for `limit`: lengths 0..11, empty documents, 300, 1, the cap, 0..69."""
+    from _dice_ref import MAX_DOC
+    rng = np.random.default_rng(limit)
+    lens = np.concatenate([rng.integers(0, 12, 400), [0, 0, 300, 1, MAX_DOC, 0], rng.integers(0, 70, 100), [0]])
+    return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+
+
+# What both public plan_launches returned before plan_ranges existed: (ranges, crc32 of the int64 [ranges, 3] array) for
+# every limit of the two existing tests, and the lists themselves where they are short.
+DICE_PLANS = {1: (498, 1447092877), 7: (472, 967786916), 100: (234, 567998729), 5000: (23, 517427679),
+              1 << 26: (1, 128799818)}
+DICE_PLAN_5000 = [(0, 202, 4956), (202, 402, 4901), (402, 403, 45150), (403, 404, 1), (404, 405, 8390656), (405, 411, 4969),
+                  (411, 419, 4831), (419, 424, 2957), (424, 432, 4931), (432, 439, 4531), (439, 446, 4979), (446, 451, 4127),
+                  (451, 453, 3975), (453, 458, 4374), (458, 466, 4479), (466, 470, 4603), (470, 475, 4823), (475, 479, 4642),
+                  (479, 484, 4833), (484, 494, 4960), (494, 498, 4674), (498, 502, 4857), (502, 507, 2524)]
+TERMS_PLANS = {1: (150, 2274331956), 100: (54, 1619156526), 257: (20, 2812722372), 5000: (3, 1310867510),
+               1 << 30: (1, 1960462011)}
+TERMS_PLAN_257 = [(0, 7, 209), (7, 13, 240), (13, 22, 253), (22, 30, 225), (30, 38, 227), (38, 46, 256), (46, 54, 235),
+                  (54, 62, 254), (62, 69, 237), (69, 70, 53), (70, 71, 5000), (71, 81, 229), (81, 90, 241), (90, 98, 226),
+                  (98, 106, 245), (106, 117, 240), (117, 123, 253), (123, 135, 254), (135, 144, 257), (144, 151, 230)]
+TERMS_PLAN_5000 = [(0, 70, 2189), (70, 71, 5000), (71, 151, 2175)]
+
+
+def _check_ranges(cum, limit):
+    from esrecsys_amd.wikipedia.pair_table import plan_ranges
+    plan = plan_ranges(cum, limit)
+    n = len(cum) - 1
+    covered = np.zeros(n, np.int64)
+    for (a, b, cost), nxt in zip(plan, plan[1:] + [None]):
+        assert 0 <= a < b <= n and cost == cum[b] - cum[a]
+        assert cost <= limit or b == a + 1                              # above the limit only as ONE document
+        assert nxt is None or nxt[0] == b                               # consecutive
+        covered[a:b] += 1
+    assert np.all(covered == 1) and (not n or (plan[0][0] == 0 and plan[-1][1] == n))     # [0, ndocs) exactly once
+    return plan
+
+
+def _digest(plan):
+    import zlib
+    return len(plan), zlib.crc32(np.array(plan, np.int64).tobytes())
+
+
+def test_plan_ranges_is_what_both_plan_launches_were():
+    from esrecsys_amd.wikipedia import make_dice as md
+    from esrecsys_amd.wikipedia.pair_table import plan_ranges
+    for limit, want in DICE_PLANS.items():
+        off = _dice_plan_offsets(limit)
+        cum = np.concatenate([[0], np.cumsum(md.pair_bounds(off))])
+        plan = _check_ranges(cum, limit)
+        assert md.plan_launches(off, limit) == plan and _digest(plan) == want
+    assert md.plan_launches(_dice_plan_offsets(5000), 5000) == DICE_PLAN_5000
+    off = tr.pack(tr.case_docs("cut_corpus"))[1]
+    for limit, want in TERMS_PLANS.items():
+        plan = _check_ranges(off, limit)
+        assert mk.plan_launches(off, limit) == plan and _digest(plan) == want
+    assert mk.plan_launches(off, 257) == TERMS_PLAN_257 and mk.plan_launches(off, 5000) == TERMS_PLAN_5000
+    for limit in (0, 1, 10):                                            # no documents: no range
+        assert plan_ranges(np.zeros(1, np.int64), limit) == []
+    assert _digest(DICE_PLAN_5000) == DICE_PLANS[5000] and _digest(TERMS_PLAN_257) == TERMS_PLANS[257]
+
+
 # ---- ranking ----
 def test_ranking_ties_go_by_ascending_id():
     ids = np.array([50, 7, 9, 3, 100, 8])
