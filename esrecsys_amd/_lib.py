@@ -28,6 +28,7 @@ c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
 c_int32 = ctypes.c_int32
 c_uint32 = ctypes.c_uint32
+c_uint64 = ctypes.c_uint64
 c_f32 = ctypes.c_float
 c_size = ctypes.c_size_t
 
@@ -74,6 +75,11 @@ SIGNATURES = {
     "esr_spotify_train_step_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int]),
     "esr_spotify_train_step": (c_int, [c_f32p, c_f32p, c_i32p, c_i64, c_f32p, c_f32p, c_i32p, c_i64, c_int, c_i32p, c_i32p,
                                        c_int, c_int, c_int, c_f32, c_int, c_f32, c_f32, c_f32p, c_vp, c_size, c_vp]),
+    "esr_spotify_sample_negatives": (c_int, [c_i32p, c_i32p, c_i64, c_uint64, c_int, c_int, c_i32p, c_i32p, c_i32p, c_vp]),
+    "esr_spotify_train_steps_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int, c_int, c_i64]),
+    "esr_spotify_train_steps": (c_int, [c_f32p, c_f32p, c_i32p, c_i64, c_f32p, c_f32p, c_i32p, c_i64, c_int, c_int, c_int,
+                                        c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_vp, c_vp, c_i32p, c_i32p, c_i64, c_uint64,
+                                        c_int, c_f32, c_f32, c_f32, c_f32p, c_i32p, c_vp, c_size, c_vp]),
     "esr_ivf_search_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_int]),
     "esr_ivf_search": (c_int, [c_f32p, c_i64, c_int, c_f32p, c_i32p, c_i32p, c_int, c_int, c_i32p, c_int, c_int, c_f32p,
                                c_i32p, c_vp, c_size, c_vp]),

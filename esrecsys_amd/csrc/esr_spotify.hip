@@ -13,6 +13,7 @@
 //              affinity terms through d raw and the norm term; writes the per-occurrence gradient rows
 //   finalize   fixed-order fp64 sum of the loss partials
 #include "esr_common.h"
+#include "esr_philox.h"
 #include "esr_segment.h"
 
 #include <algorithm>
@@ -579,6 +580,57 @@ __global__ __launch_bounds__(kBlock) void spotify_affinity_all_kernel(const floa
   }
 }
 
+// The id lists of a GROUP of K steps in one launch (esr_spotify_train_steps), and the stand-alone sampler
+// (esr_spotify_sample_negatives: K = 1, n = 0, no next lists, lists == null).  One thread per (step j, position r):
+// blocks_per_step workgroups per step, position r of step j = [context n | next m_j | neg o].  Context and next ids are
+// copied, a negative is drawn -- sp_negative_index (esr_philox.h): a pure function of (seed, first_step + j, i); every
+// thread runs the ten Philox rounds for its own word (four threads share a block of four words: 64 negatives are 640
+// multiplies more than sharing would cost, and no lane waits on another).  Integer arithmetic, plain loads and stores,
+// no atomics, no workgroup waits on another.
+struct SpAssemble {
+  const int32_t *ctx_album, *ctx_artist;    // [K, n]
+  const int32_t *next_album, *next_artist;  // packed
+  const int64_t* next_offsets;              // device [K + 1]; null: no next lists (the sampler)
+  const int32_t *all_albums, *all_artists;  // [T]
+  uint64_t seed;
+  uint32_t tm1, first_step;
+  int n, o, K, blocks_per_step;
+  int32_t* lists;      // the group call's list region (sp_list_start); null: the sampler's three outputs below
+  int32_t* neg_index;  // [K, o], optional
+  int32_t *neg_album, *neg_artist;  // [o], sampler only, optional
+};
+__global__ __launch_bounds__(kBlock) void spotify_assemble_kernel(SpAssemble a) {
+  const int j = (int)(blockIdx.x / (unsigned)a.blocks_per_step);
+  const int r = (int)(blockIdx.x % (unsigned)a.blocks_per_step) * kBlock + (int)threadIdx.x;
+  if (j >= a.K) return;
+  const int64_t off0 = a.next_offsets ? a.next_offsets[j] : 0, off1 = a.next_offsets ? a.next_offsets[j + 1] : 0;
+  const int m = (int)(off1 - off0), R = a.n + m + a.o;
+  if (r >= R) return;
+  int32_t al, ar;
+  if (r < a.n) {
+    al = a.ctx_album[(int64_t)j * a.n + r];
+    ar = a.ctx_artist[(int64_t)j * a.n + r];
+  } else if (r < a.n + m) {
+    al = a.next_album[off0 + (r - a.n)];
+    ar = a.next_artist[off0 + (r - a.n)];
+  } else {
+    const int i = r - a.n - m;
+    const uint32_t idx = sp_negative_index(a.seed, a.first_step + (uint32_t)j, (uint32_t)i, a.tm1);
+    al = a.all_albums[idx];
+    ar = a.all_artists[idx];
+    if (a.neg_index) a.neg_index[(int64_t)j * a.o + i] = (int32_t)idx;
+    if (!a.lists) {
+      if (a.neg_album) a.neg_album[i] = al;
+      if (a.neg_artist) a.neg_artist[i] = ar;
+    }
+  }
+  if (a.lists) {
+    int32_t* blk = a.lists + sp_list_start(j, a.n, a.o, off0);
+    blk[r] = al;
+    blk[R + r] = ar;
+  }
+}
+
 struct SpWs {
   float *E, *l2, *raw, *aff, *W;
   double* partial;  // [R] row partials then [1] head
@@ -770,19 +822,19 @@ size_t esr_spotify_train_step_workspace_bytes(int n, int m, int o, int F) {
 // six-term loss and its per-occurrence gradient rows, one sort of the virtual rows [album mod rows ; n_album_rows + artist]
 // and the whole momentum step on the touched rows of both tables -- eight launches, one foreign call (the step is
 // launch-bound: fourteen launches from Python took ~100 us of host time for ~60 us of kernels).
-int esr_spotify_train_step(float* album_table, float* album_trace, int32_t* album_last, int64_t n_album_rows,
-                           float* artist_table, float* artist_trace, int32_t* artist_last, int64_t n_artists, int F,
-                           const int32_t* album_ids, const int32_t* artist_ids, int n, int m, int o, float regularization,
-                           int step, float lr, float momentum, float* loss, void* workspace, size_t workspace_bytes,
-                           esr_stream_t stream) {
-  TraceScope trace_scope_("esr_spotify_train_step");
-  if (int rc = sp_check("esr_spotify_train_step", n, m, o, F, n_album_rows, n_artists)) return rc;
+// (the one step both esr_spotify_train_step and esr_spotify_train_steps issue: `who` names the entry point in messages)
+static int sp_train_step(const char* who, float* album_table, float* album_trace, int32_t* album_last, int64_t n_album_rows,
+                         float* artist_table, float* artist_trace, int32_t* artist_last, int64_t n_artists, int F,
+                         const int32_t* album_ids, const int32_t* artist_ids, int n, int m, int o, float regularization,
+                         int step, float lr, float momentum, float* loss, void* workspace, size_t workspace_bytes,
+                         esr_stream_t stream) {
+  if (int rc = sp_check(who, n, m, o, F, n_album_rows, n_artists)) return rc;
   ESR_REQUIRE(album_table && album_trace && album_last && artist_table && artist_trace && artist_last && album_ids &&
                   artist_ids && loss && workspace && step >= 1,
-              "esr_spotify_train_step: null pointer or step < 1");
-  ESR_REQUIRE(n_album_rows < ((int64_t)1 << 30) && n_artists < ((int64_t)1 << 30), "esr_spotify_train_step: tables too large");
+              "%s: null pointer or step < 1", who);
+  ESR_REQUIRE(n_album_rows < ((int64_t)1 << 30) && n_artists < ((int64_t)1 << 30), "%s: tables too large", who);
   if (workspace_bytes < esr_spotify_train_step_workspace_bytes(n, m, o, F) || ((uintptr_t)workspace & 15)) {
-    set_error("esr_spotify_train_step: workspace %zu bytes < %zu required (or misaligned)", workspace_bytes,
+    set_error("%s: workspace %zu bytes < %zu required (or misaligned)", who, workspace_bytes,
               esr_spotify_train_step_workspace_bytes(n, m, o, F));
     return ESR_EWORKSPACE;
   }
@@ -826,6 +878,138 @@ int esr_spotify_train_step(float* album_table, float* album_trace, int32_t* albu
     return sparse_momentum_step_lazy2(tables, traces, lasts, row_offsets, 2, F, sorted, perm, 2 * R, grads, lr, momentum, step,
                                       as_stream(stream));
   return esr_sparse_momentum_step_multi(tables, traces, row_offsets, 2, F, sorted, perm, 2 * R, grads, lr, momentum, stream);
+}
+
+int esr_spotify_train_step(float* album_table, float* album_trace, int32_t* album_last, int64_t n_album_rows,
+                           float* artist_table, float* artist_trace, int32_t* artist_last, int64_t n_artists, int F,
+                           const int32_t* album_ids, const int32_t* artist_ids, int n, int m, int o, float regularization,
+                           int step, float lr, float momentum, float* loss, void* workspace, size_t workspace_bytes,
+                           esr_stream_t stream) {
+  TraceScope trace_scope_("esr_spotify_train_step");
+  return sp_train_step("esr_spotify_train_step", album_table, album_trace, album_last, n_album_rows, artist_table,
+                       artist_trace, artist_last, n_artists, F, album_ids, artist_ids, n, m, o, regularization, step, lr,
+                       momentum, loss, workspace, workspace_bytes, stream);
+}
+
+constexpr int64_t kSpMaxGroupIds = (int64_t)1 << 24;  // ids of one group / negatives of one sampler call
+
+// T and the count of one draw: the multiply-high takes T - 1 as a 32-bit factor below 2^31
+static int sp_check_corpus(const char* who, int64_t T) {
+  ESR_REQUIRE(T >= 2 && T - 1 <= (int64_t)INT32_MAX, "%s: T=%lld (2 <= T, T - 1 <= 2^31 - 1: the last track is never drawn)",
+              who, (long long)T);
+  return ESR_OK;
+}
+
+int esr_spotify_sample_negatives(const int32_t* all_albums, const int32_t* all_artists, int64_t T, uint64_t seed, int step,
+                                 int o, int32_t* neg_index, int32_t* neg_album, int32_t* neg_artist, esr_stream_t stream) {
+  const char* who = "esr_spotify_sample_negatives";
+  if (int rc = sp_check_corpus(who, T)) return rc;
+  ESR_REQUIRE(o >= 1 && o <= kSpMaxGroupIds && step >= 1, "%s: bad sizes o=%d step=%d (1 <= o <= 2^24, step >= 1)", who, o,
+              step);
+  ESR_REQUIRE(all_albums && all_artists && (neg_index || neg_album || neg_artist), "%s: null pointer", who);
+  SpAssemble a{};
+  a.all_albums = all_albums;
+  a.all_artists = all_artists;
+  a.seed = seed;
+  a.tm1 = (uint32_t)(T - 1);
+  a.first_step = (uint32_t)step;
+  a.o = o;
+  a.K = 1;
+  a.blocks_per_step = (int)cdiv(o, kBlock);
+  a.neg_index = neg_index;
+  a.neg_album = neg_album;
+  a.neg_artist = neg_artist;
+  hipStream_t st = as_stream(stream);
+  ESR_KT("spotify_assemble_kernel", st,
+         hipLaunchKernelGGL(spotify_assemble_kernel, dim3(a.blocks_per_step), dim3(kBlock), 0, st, a));
+  return check_launch(who);
+}
+
+size_t esr_spotify_train_steps_workspace_bytes(int n, int max_m, int o, int F, int K, int64_t total_next) {
+  if (n <= 0 || max_m <= 0 || o <= 0 || F <= 0 || K <= 0 || total_next < K) return 256;
+  return align_up((size_t)sp_list_region(K, n, o, total_next) * 4, 256) + esr_spotify_train_step_workspace_bytes(n, max_m, o, F);
+}
+
+int esr_spotify_train_steps(float* album_table, float* album_trace, int32_t* album_last, int64_t n_album_rows,
+                            float* artist_table, float* artist_trace, int32_t* artist_last, int64_t n_artists, int F,
+                            int n, int o, int K, const int32_t* ctx_album, const int32_t* ctx_artist,
+                            const int32_t* next_album, const int32_t* next_artist, const int64_t* next_offsets,
+                            const int64_t* next_offsets_dev, const int32_t* all_albums, const int32_t* all_artists,
+                            int64_t T, uint64_t seed, int first_step, float regularization, float lr, float momentum,
+                            float* losses, int32_t* neg_index, void* workspace, size_t workspace_bytes,
+                            esr_stream_t stream) {
+  const char* who = "esr_spotify_train_steps";
+  TraceScope trace_scope_(who);
+  // ---- everything is checked here, before the first launch: the steps below cannot fail on their arguments
+  if (int rc = sp_check(who, n, 1, o, F, n_album_rows, n_artists)) return rc;
+  ESR_REQUIRE(K >= 1 && first_step >= 1 && (int64_t)first_step + K - 1 <= (int64_t)INT32_MAX,
+              "%s: bad sizes K=%d first_step=%d (K >= 1, first_step >= 1, the last step an int)", who, K, first_step);
+  if (int rc = sp_check_corpus(who, T)) return rc;
+  ESR_REQUIRE(album_table && album_trace && album_last && artist_table && artist_trace && artist_last && ctx_album &&
+                  ctx_artist && next_album && next_artist && next_offsets && next_offsets_dev && all_albums &&
+                  all_artists && losses && workspace,
+              "%s: null pointer", who);
+  ESR_REQUIRE(n_album_rows < ((int64_t)1 << 30) && n_artists < ((int64_t)1 << 30), "%s: tables too large", who);
+  int64_t max_m = 0;
+  if (const int64_t bad = sp_check_offsets(next_offsets, K, &max_m)) {
+    set_error("%s: next_offsets[%lld] = %lld: the offsets start at 0 and every next list holds at least one id (m >= 1)",
+              who, (long long)(bad - 1), (long long)next_offsets[bad - 1]);
+    return ESR_EINVAL;
+  }
+  const int64_t total_next = next_offsets[K], total_ids = (int64_t)K * (n + o) + total_next;
+  ESR_REQUIRE(total_ids <= kSpMaxGroupIds, "%s: %lld ids in one group exceed 2^24", who, (long long)total_ids);
+  const size_t need = esr_spotify_train_steps_workspace_bytes(n, (int)max_m, o, F, K, total_next);
+  if (workspace_bytes < need || ((uintptr_t)workspace & 15)) {
+    set_error("%s: workspace %zu bytes < %zu required (or misaligned)", who, workspace_bytes, need);
+    return ESR_EWORKSPACE;
+  }
+  int32_t* lists = (int32_t*)workspace;
+  const size_t lists_bytes = align_up((size_t)sp_list_region(K, n, o, total_next) * 4, 256);
+  char* step_ws = (char*)workspace + lists_bytes;
+  const size_t step_ws_bytes = workspace_bytes - lists_bytes;
+  const int64_t blocks_per_step = cdiv((int64_t)n + max_m + o, kBlock);
+  ESR_REQUIRE(K * blocks_per_step <= (int64_t)INT32_MAX, "%s: K=%d steps of up to %lld ids exceed one launch", who, K,
+              (long long)(n + max_m + o));
+  for (int j = 0, seen = 0; j < K; ++j) {  // (the steps share the region sized for the longest list: every shorter one fits)
+    const int m = (int)(next_offsets[j + 1] - next_offsets[j]);
+    if (m == seen) continue;
+    seen = m;
+    if (esr_spotify_train_step_workspace_bytes(n, m, o, F) > step_ws_bytes) {
+      set_error("%s: workspace %zu bytes: step %d (m = %d) needs %zu after the %zu bytes of id lists", who, workspace_bytes, j,
+                m, esr_spotify_train_step_workspace_bytes(n, m, o, F), lists_bytes);
+      return ESR_EWORKSPACE;
+    }
+  }
+  hipStream_t st = as_stream(stream);
+  SpAssemble a{};
+  a.ctx_album = ctx_album;
+  a.ctx_artist = ctx_artist;
+  a.next_album = next_album;
+  a.next_artist = next_artist;
+  a.next_offsets = next_offsets_dev;
+  a.all_albums = all_albums;
+  a.all_artists = all_artists;
+  a.seed = seed;
+  a.tm1 = (uint32_t)(T - 1);
+  a.first_step = (uint32_t)first_step;
+  a.n = n;
+  a.o = o;
+  a.K = K;
+  a.blocks_per_step = (int)blocks_per_step;
+  a.lists = lists;
+  a.neg_index = neg_index;
+  ESR_KT("spotify_assemble_kernel", st,
+         hipLaunchKernelGGL(spotify_assemble_kernel, dim3((unsigned)((int64_t)K * a.blocks_per_step)), dim3(kBlock), 0, st, a));
+  if (int rc = check_launch(who)) return rc;
+  for (int j = 0; j < K; ++j) {
+    const int m = (int)(next_offsets[j + 1] - next_offsets[j]), R = n + m + o;
+    const int32_t* blk = lists + sp_list_start(j, n, o, next_offsets[j]);
+    if (int rc = sp_train_step(who, album_table, album_trace, album_last, n_album_rows, artist_table, artist_trace,
+                               artist_last, n_artists, F, blk, blk + R, n, m, o, regularization, first_step + j, lr,
+                               momentum, losses + j, step_ws, step_ws_bytes, stream))
+      return rc;
+  }
+  return ESR_OK;
 }
 
 int esr_spotify_affinity_all(const float* album_table, int64_t n_album_rows, const float* artist_table,

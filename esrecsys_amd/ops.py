@@ -855,6 +855,87 @@ def spotify_train_step(album_table, album_trace, album_last, artist_table, artis
     return loss
 
 
+def spotify_sample_negatives(all_albums, all_artists, seed, step, num_negatives):
+    """The negatives of global step `step` (>= 1) drawn on the device (esr_spotify_sample_negatives): Philox4x32-10 keyed by
+    the 64-bit `seed`, counter (i >> 2, step, 0, 0), index = (word * (T - 1)) >> 32 -- the last track is never drawn, as in
+    train_spotify.py:146; multiply-high is biased by at most (T - 1) / 2^32 relative (5.3e-4 at the reference's corpus).
+    all_albums / all_artists: device int32 [T].  Returns (index, album, artist), int32 [num_negatives] each."""
+    lib = _lib.load()
+    _req(all_albums, torch.int32, "all_albums"), _req(all_artists, torch.int32, "all_artists")
+    T, o = all_albums.numel(), int(num_negatives)
+    if all_artists.numel() != T:
+        raise ValueError("all_albums and all_artists differ in length (%d vs %d)" % (T, all_artists.numel()))
+    if T < 2 or o < 1 or int(step) < 1:
+        raise ValueError("spotify_sample_negatives: T=%d num_negatives=%d step=%d (T >= 2, num_negatives >= 1, step >= 1)"
+                         % (T, o, step))
+    out = torch.empty((3, o), dtype=torch.int32, device=all_albums.device)
+    check(lib.esr_spotify_sample_negatives(_p(all_albums), _p(all_artists), T, int(seed) & (2 ** 64 - 1), int(step), o,
+                                           _p(out[0]), _p(out[1]), _p(out[2]), _stream()), "esr_spotify_sample_negatives")
+    return out[0], out[1], out[2]
+
+
+def spotify_list_starts(n, next_offsets, o):
+    """Where esr_spotify_train_steps puts step j's id lists in its workspace (include/esr_hip.h), in int32 units: block j
+    = [album ids R_j][artist ids R_j], R_j = n + m_j + o.  next_offsets: the K + 1 host offsets."""
+    off = np.asarray(next_offsets, dtype=np.int64)
+    j = np.arange(off.size - 1, dtype=np.int64)
+    return (2 * (j * (n + o) + off[:-1]) + 63) // 64 * 64 + 64 * j
+
+
+def spotify_train_steps(album_table, album_trace, album_last, artist_table, artist_trace, artist_last, ctx_album, ctx_artist,
+                        next_album, next_artist, next_offsets, next_offsets_dev, all_albums, all_artists, seed, first_step,
+                        num_negatives, regularization, lr, momentum, losses=None, neg_index=None, workspace=None):
+    """K Spotify train steps under lazy optax.sgd(lr, momentum) by ONE library call (esr_spotify_train_steps): one launch
+    draws the negatives of steps first_step .. first_step + K - 1 and assembles every step's id lists, then each step is
+    the launch sequence of spotify_train_step.  ctx_album / ctx_artist: device int32 [K, n]; next_album / next_artist:
+    device int32, the K next lists packed; next_offsets: host int64 [K + 1] (numpy), next_offsets_dev: its device copy.
+    losses (float32 [K]), neg_index (int32 [K, num_negatives]) and workspace (uint8) are outputs the caller may provide.
+    Returns losses."""
+    lib = _lib.load()
+    for t, name in ((album_table, "album_table"), (album_trace, "album_trace"), (artist_table, "artist_table"),
+                    (artist_trace, "artist_trace")):
+        _req(t, torch.float32, name)
+    for t, name in ((album_last, "album_last"), (artist_last, "artist_last"), (ctx_album, "ctx_album"),
+                    (ctx_artist, "ctx_artist"), (next_album, "next_album"), (next_artist, "next_artist"),
+                    (all_albums, "all_albums"), (all_artists, "all_artists")):
+        _req(t, torch.int32, name)
+    _req(next_offsets_dev, torch.int64, "next_offsets_dev")
+    if ctx_album.dim() != 2 or ctx_album.shape != ctx_artist.shape:
+        raise ValueError("ctx_album / ctx_artist must both be [K, n], got %s and %s"
+                         % (tuple(ctx_album.shape), tuple(ctx_artist.shape)))
+    K, n = ctx_album.shape
+    off = np.ascontiguousarray(next_offsets, dtype=np.int64)
+    if off.ndim != 1 or off.size != K + 1 or next_offsets_dev.numel() != K + 1:
+        raise ValueError("next_offsets / next_offsets_dev must hold K + 1 = %d entries" % (K + 1))
+    if K < 1 or off[0] != 0 or (np.diff(off) < 1).any():
+        raise ValueError("spotify_train_steps: K >= 1 playlists, next_offsets from 0, every next list non-empty")
+    total = int(off[-1])
+    if next_album.numel() != total or next_artist.numel() != total:
+        raise ValueError("next_album / next_artist hold %d / %d ids, next_offsets[K] = %d"
+                         % (next_album.numel(), next_artist.numel(), total))
+    T, o = all_albums.numel(), int(num_negatives)
+    if all_artists.numel() != T:
+        raise ValueError("all_albums and all_artists differ in length (%d vs %d)" % (T, all_artists.numel()))
+    if T < 2:
+        raise ValueError("spotify_train_steps: a corpus of T=%d tracks (T >= 2: the last track is never drawn)" % T)
+    F, dev = album_table.shape[1], album_table.device
+    if losses is None:
+        losses = torch.empty(K, dtype=torch.float32, device=dev)
+    elif _req(losses, torch.float32, "losses").numel() != K:
+        raise ValueError("losses must hold K = %d entries" % K)
+    if neg_index is not None and _req(neg_index, torch.int32, "neg_index").numel() != K * o:
+        raise ValueError("neg_index must hold K * num_negatives = %d entries" % (K * o))
+    nbytes = _ws_bytes("esr_spotify_train_steps_workspace_bytes", n, int(np.diff(off).max()), o, F, K, total)
+    ws = _ws(nbytes, dev) if workspace is None else _req(workspace, torch.uint8, "workspace")
+    check(lib.esr_spotify_train_steps(_p(album_table), _p(album_trace), _p(album_last), album_table.shape[0],
+                                      _p(artist_table), _p(artist_trace), _p(artist_last), artist_table.shape[0], F, n, o, K,
+                                      _p(ctx_album), _p(ctx_artist), _p(next_album), _p(next_artist), off.ctypes.data,
+                                      _p(next_offsets_dev), _p(all_albums), _p(all_artists), T, int(seed) & (2 ** 64 - 1),
+                                      int(first_step), float(regularization), float(lr), float(momentum), _p(losses),
+                                      _p(neg_index), _p(ws), ws.numel(), _stream()), "esr_spotify_train_steps")
+    return losses
+
+
 def spotify_affinity_all(album_table, artist_table, ctx_album, ctx_artist, all_albums, all_artists):
     """Affinity [T] of every track to the context (train_spotify.py:113-119, result[1])."""
     lib = _lib.load()

@@ -190,3 +190,140 @@ def sample_negative(x, rng, num_negatives, all_tracks, all_albums, all_artists):
     x["neg_album"] = np.asarray(all_albums)[idx]
     x["neg_artist"] = np.asarray(all_artists)[idx]
     return rng
+
+
+def _host_ids(v):
+    return (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).reshape(-1)
+
+
+class NegativeSampler:
+    """sample_negative (train_spotify.py:139-150) on the device: the corpus is uploaded and validated ONCE, and the
+    negatives of a step are a pure function of (seed, step) -- never of the model -- so a loop can draw them for many
+    steps ahead (train_steps) and a restored run continues the same stream.
+
+    Negative i of step s: word i & 3 of Philox4x32-10 (Random123) with counter (i >> 2, s, 0, 0) and key (seed & 0xffffffff,
+    seed >> 32); track index = (word * (T - 1)) >> 32.  Like the reference the last track is never drawn; multiply-high is
+    biased by at most (T - 1) / 2^32 relative (5.3e-4 at the reference's 2 262 292 tracks).  This is not JAX's threefry
+    stream (which is not reproducible without JAX) and not sample_negative's NumPy stream.
+
+    Raises ValueError for arrays of different lengths or fewer than two tracks, IndexError for an artist id outside
+    [0, n_artists)."""
+
+    def __init__(self, all_tracks, all_albums, all_artists, num_negatives, seed, n_artists, device):
+        sizes = {int(v.numel()) if isinstance(v, torch.Tensor) else int(np.size(v))
+                 for v in (all_tracks, all_albums, all_artists)}
+        if len(sizes) != 1:
+            raise ValueError("all_tracks, all_albums and all_artists differ in length: %s" % sorted(sizes))
+        self.T = sizes.pop()
+        if self.T < 2:
+            raise ValueError("a corpus of %d track(s): negatives are drawn from all but the last, T >= 2 is required" % self.T)
+        if int(num_negatives) < 1:
+            raise ValueError("num_negatives must be >= 1, got %d" % num_negatives)
+        self.num_negatives, self.seed, self.n_artists = int(num_negatives), int(seed) & (2 ** 64 - 1), int(n_artists)
+        self.tracks = ops.as_ids(all_tracks, device).reshape(-1)
+        self.albums = ops.as_ids(all_albums, device).reshape(-1)
+        self.artists = ops.as_ids(all_artists, device).reshape(-1)
+        lo, hi = int(self.artists.min()), int(self.artists.max())
+        if lo < 0 or hi >= self.n_artists:
+            raise IndexError("artist id out of range [0, %d) in the corpus: min %d max %d" % (self.n_artists, lo, hi))
+
+    def sample(self, step):
+        """(index, album, artist) of the step's negatives: device int32 [num_negatives] each."""
+        return ops.spotify_sample_negatives(self.albums, self.artists, self.seed, step, self.num_negatives)
+
+    def indices(self, step):
+        return self.sample(step)[0]
+
+    def fill(self, x, step):
+        """The per-step counterpart of sample_negative: x's neg_track / neg_album / neg_artist as device tensors."""
+        idx, x["neg_album"], x["neg_artist"] = self.sample(step)
+        x["neg_track"] = self.tracks[idx.long()]
+        return x
+
+
+def _fused(state):
+    """(album table, artist table) when train_step would take its one-call path for this state, else None."""
+    p = state.raw_params["params"]
+    at, rt = p["album_embed"]["embedding"], p["artist_embed"]["embedding"]
+    tx = state.tx
+    if getattr(tx, "lazy", False) and hasattr(tx, "_lazy_state") and at.is_cuda and at.shape[1] == rt.shape[1]:
+        return at, rt
+    return None
+
+
+def _pack_group(xs, n, n_artists):
+    """One int32 host buffer for a group of playlists: [next_offsets as int64 (K + 1) | ctx_album K n | ctx_artist K n |
+    next_album | next_artist], and the int64 offsets.  Artist ids are range-checked (album ids are hashed: any int32)."""
+    K = len(xs)
+    nexts_a = [_host_ids(x["next_album"]) for x in xs]
+    nexts_r = [_host_ids(x["next_artist"]) for x in xs]
+    lens = np.array([a.size for a in nexts_a], dtype=np.int64)
+    if (lens < 1).any() or any(a.size != r.size for a, r in zip(nexts_a, nexts_r)):
+        raise ValueError("every playlist needs a non-empty next list with one artist per album (lengths %s)"
+                         % [(a.size, r.size) for a, r in zip(nexts_a, nexts_r)])
+    off = np.zeros(K + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    total = int(off[-1])
+    buf = np.empty(2 * (K + 1) + 2 * K * n + 2 * total, dtype=np.int32)
+    buf[:2 * (K + 1)] = off.view(np.int32)
+    p = 2 * (K + 1)
+    buf[p:p + K * n] = np.concatenate([_host_ids(x["album_context"]) for x in xs])
+    buf[p + K * n:p + 2 * K * n] = np.concatenate([_host_ids(x["artist_context"]) for x in xs])
+    q = p + 2 * K * n
+    buf[q:q + total] = np.concatenate(nexts_a)
+    buf[q + total:q + 2 * total] = np.concatenate(nexts_r)
+    art = np.concatenate([buf[p + K * n:q], buf[q + total:]])
+    if art.min() < 0 or art.max() >= n_artists:
+        raise IndexError("artist id out of range [0, %d)" % n_artists)
+    return buf, off
+
+
+def train_steps(state, train_it, num_steps, regularization, sampler, group=64):
+    """The training loop of train_spotify.py:255-259 for `num_steps` playlists drawn from `train_it` (the reference's
+    feature dicts, without negatives): per playlist what ``sampler.fill(x, step)`` + ``train_step(state, x, regularization)``
+    compute, bit for bit, issued `group` playlists per library call -- one upload of the group's contexts and next lists,
+    one launch that draws every step's negatives and assembles its id lists, then the steps' own launches
+    (esr_spotify_train_steps).  The step number of a playlist is the lazy optimizer's step counter for that step, so a
+    restored run continues the same negative stream.  Returns (state, losses): float32 [num_steps] on the tables' device.
+
+    ValueError for mixed context lengths within a call or an empty next list, IndexError for an artist id outside the
+    artist table.  A state that is not on train_step's one-call path (optimizer not lazy, tables of unequal width) runs
+    the per-playlist loop."""
+    if num_steps < 1 or group < 1:
+        raise ValueError("num_steps and group must be >= 1, got %d and %d" % (num_steps, group))
+    xs = [next(train_it) for _ in range(num_steps)]
+    n = _context_length(xs)
+    tables = _fused(state)
+    if tables is None:
+        losses = []
+        for x in xs:
+            lz = state.opt_state.get("_lazy") if isinstance(state.opt_state, dict) else None
+            step = (lz["step"] if lz else int(state.step)) + 1
+            state, loss = train_step(state, sampler.fill(dict(x), step), regularization)
+            losses.append(loss)
+        return state, torch.stack(losses).float()
+    at, rt = tables
+    dev, tx = at.device, state.tx
+    lz = tx._lazy_state(state.raw_params, state.opt_state)
+    tr = state.opt_state["trace"]["params"]
+    last_a, last_r = lz["last"][("params", "album_embed", "embedding")], lz["last"][("params", "artist_embed", "embedding")]
+    if sampler.n_artists > rt.shape[0]:
+        raise IndexError("the sampler's corpus may name artists up to %d, the artist table has %d rows"
+                         % (sampler.n_artists, rt.shape[0]))
+    losses = torch.empty(num_steps, dtype=torch.float32, device=dev)
+    for g0 in range(0, num_steps, group):
+        chunk = xs[g0:g0 + group]
+        K = len(chunk)
+        buf, off = _pack_group(chunk, n, rt.shape[0])
+        total = int(off[-1])
+        d = torch.from_numpy(buf).to(dev, non_blocking=True)
+        p = 2 * (K + 1)
+        q = p + 2 * K * n
+        ops.spotify_train_steps(at, tr["album_embed"]["embedding"], last_a, rt, tr["artist_embed"]["embedding"], last_r,
+                                d[p:p + K * n].view(K, n), d[p + K * n:q].view(K, n), d[q:q + total], d[q + total:],
+                                off, d[:p].view(torch.int64), sampler.albums, sampler.artists, sampler.seed, lz["step"] + 1,
+                                sampler.num_negatives, regularization, tx.lr, tx.momentum, losses=losses[g0:g0 + K])
+        lz["step"] += K
+        lz["dirty"] = True
+        state = state.replace(step=state.step + K)
+    return state, losses

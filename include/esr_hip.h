@@ -640,6 +640,34 @@ int esr_spotify_train_step(float* album_table, float* album_trace, int32_t* albu
                            const int32_t* album_ids, const int32_t* artist_ids, int n, int m, int o, float regularization,
                            int step, float lr, float momentum, float* loss, void* workspace, size_t workspace_bytes,
                            esr_stream_t stream);
+/* sample_negative (train_spotify.py:139-150) on the device: the o negatives of global step `step` >= 1 are a function
+ * of (seed, step) alone.  Negative i takes word i & 3 of Philox4x32-10 (Random123) with counter (i >> 2, step, 0, 0) and
+ * key (seed & 0xffffffff, seed >> 32); its track index is (word * (T - 1)) >> 32 -- like the reference, the last track is
+ * never drawn; multiply-high is biased by at most (T - 1) / 2^32 relative (5.3e-4 at the reference's 2 262 292 tracks).
+ * neg_index / neg_album / neg_artist [o] (each may be NULL, not all): the index, all_albums[index], all_artists[index].
+ * 2 <= T <= 2^31, 1 <= o <= 2^24.  One launch, no workspace. */
+int esr_spotify_sample_negatives(const int32_t* all_albums, const int32_t* all_artists, int64_t T, uint64_t seed, int step,
+                                 int o, int32_t* neg_index, int32_t* neg_album, int32_t* neg_artist, esr_stream_t stream);
+/* K train steps in ONE call (the loop of train_spotify.py:255-259 over a group of playlists): one launch draws the
+ * negatives of steps first_step .. first_step + K - 1 (as esr_spotify_sample_negatives) and assembles every step's id
+ * lists, then each step j runs exactly the launch sequence of esr_spotify_train_step with shape (n, m_j, o) and
+ * step = first_step + j, and writes losses[j].  Never synchronises, never allocates.
+ * ctx_album / ctx_artist: device int32 [K * n]; next_album / next_artist: device int32, the K next lists packed;
+ * next_offsets: HOST int64 [K + 1] (next_offsets[0] = 0, list j = [next_offsets[j], next_offsets[j + 1]), m_j >= 1) and
+ * next_offsets_dev: the same K + 1 values in device memory (the caller uploads them, e.g. with the id lists: the call
+ * copies nothing from the host); neg_index: device int32 [K * o] or NULL.  K (n + o) + next_offsets[K] <= 2^24.
+ * The workspace begins with the assembled lists, int32: step j's block [album ids R_j][artist ids R_j] (context, next,
+ * neg; R_j = n + m_j + o) starts at int  roundup(2 (j (n + o) + next_offsets[j]), 64) + 64 j,  i.e. 256-byte aligned.
+ * Workspace query: max_m = the longest next list, total_next = next_offsets[K]. */
+size_t esr_spotify_train_steps_workspace_bytes(int n, int max_m, int o, int F, int K, int64_t total_next);
+int esr_spotify_train_steps(float* album_table, float* album_trace, int32_t* album_last, int64_t n_album_rows,
+                            float* artist_table, float* artist_trace, int32_t* artist_last, int64_t n_artists, int F,
+                            int n, int o, int K, const int32_t* ctx_album, const int32_t* ctx_artist,
+                            const int32_t* next_album, const int32_t* next_artist, const int64_t* next_offsets,
+                            const int64_t* next_offsets_dev, const int32_t* all_albums, const int32_t* all_artists,
+                            int64_t T, uint64_t seed, int first_step, float regularization, float lr, float momentum,
+                            float* losses, int32_t* neg_index, void* workspace, size_t workspace_bytes,
+                            esr_stream_t stream);
 
 /* ---- 8e: row-shard routing (owner = id mod world, local row = id div world) ---------------
  * Stable bucket of ids by owner: local_rows[k] = ids[perm[k]] / world, counts[g] = #ids owned by g
