@@ -226,6 +226,13 @@ SIGNATURES = {
     "esr_terms_lookup_build": (c_int, [c_i32p, c_i32p, c_i64, c_vp, c_i64, c_vp]),
     "esr_terms_lookup": (c_int, [c_i32p, c_i64, c_vp, c_i64, c_int, c_int32, c_i32p, c_i32p, c_vp, c_vp]),
     "esr_terms_tfidf_rows": (c_int, [c_vp, c_i64, c_i32p, c_i32p, c_i64, c_i64, c_vp, c_i64, c_f32p, c_vp]),
+    "esr_neighbours_workspace_bytes": (c_size, [c_i64, c_i64, c_int]),
+    "esr_neighbours_plan_bounds": (c_int, [c_i32p, c_int]),
+    "esr_neighbours_topk": (c_int, [c_i32p, c_i32p, c_f32p, c_i64, c_i32p, c_f32p, c_i64, c_int, c_int, c_int, c_i32p,
+                                    c_f32p, c_f32p, c_i32p, c_vp, c_size, c_vp]),
+    "esr_itemknn_max_entries": (c_int, []),
+    "esr_itemknn_recommend": (c_int, [c_i32p, c_i32p, c_f32p, c_i32p, c_i64, c_int, c_i32p, c_i64, c_vp, c_i64, c_int,
+                                      c_int, c_i32p, c_f32p, c_i32p, c_vp]),
 }
 
 

@@ -1701,3 +1701,57 @@ def terms_tfidf_rows(scratch, capacity, index, row_off, idf):
                                            index.numel(), _p(idf), idf.numel(), _p(out), _stream()),
           "esr_terms_tfidf_rows")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# item-to-item neighbours and the item-kNN recommender (esr_neighbours.hip)
+def neighbours_plan_bounds():
+    """The row lengths at which the neighbour select changes class, ascending (esr_neighbours_plan_bounds)."""
+    lib = _lib.load()
+    n = int(lib.esr_neighbours_plan_bounds(None, 0))
+    buf = (ctypes.c_int32 * n)()
+    lib.esr_neighbours_plan_bounds(ctypes.addressof(buf), n)
+    return list(buf)
+
+
+def neighbours_topk(index, other, count, ids, df, k, both, dice):
+    """(neighbours int32[u, k], scores float32[u, k], counts float32[u, k], lengths int32[u], fail int) of the rows of
+    `ids`; fail = the failure word of the call (bit 64: an entry with an id that `ids` lacks).  Reading it syncs."""
+    lib = _lib.load()
+    _req(index, torch.int32, "index"), _req(other, torch.int32, "other"), _req(count, torch.float32, "count")
+    _req(ids, torch.int32, "ids")
+    if df is not None:
+        _req(df, torch.float32, "df")
+    dev, nnz, u = ids.device, index.numel(), ids.numel()
+    nb = torch.empty((u, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((u, k), dtype=torch.float32, device=dev)
+    counts = torch.empty((u, k), dtype=torch.float32, device=dev)
+    lengths = torch.empty(u, dtype=torch.int32, device=dev)
+    ws = _ws(int(lib.esr_neighbours_workspace_bytes(nnz, u, int(both))), dev)
+    check(lib.esr_neighbours_topk(_p(index), _p(other), _p(count), nnz, _p(ids), _p(df), u, int(k), int(both), int(dice),
+                                  _p(nb), _p(scores), _p(counts), _p(lengths), _p(ws), ws.numel(), _stream()),
+          "esr_neighbours_topk")
+    fail = int(ws[:8].view(torch.int64).item()) if u and nnz else 0
+    return nb, scores, counts, lengths, fail
+
+
+def itemknn_max_entries():
+    """History length x table width one query of itemknn_recommend may gather (one workgroup sorts them in LDS)."""
+    return int(_lib.load().esr_itemknn_max_entries())
+
+
+def itemknn_recommend(table_ids, table_neighbours, table_scores, table_lengths, history, offsets, k, exclude_history):
+    """(ids int32[nq, k], scores float32[nq, k], lengths int32[nq]) of the queries history[offsets[q]:offsets[q + 1]]."""
+    lib = _lib.load()
+    _req(table_ids, torch.int32, "table.ids"), _req(table_neighbours, torch.int32, "table.neighbours")
+    _req(table_scores, torch.float32, "table.scores"), _req(table_lengths, torch.int32, "table.lengths")
+    _req(history, torch.int32, "history"), _req(offsets, torch.int64, "offsets")
+    dev, nq = history.device, offsets.numel() - 1
+    out_ids = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    out_scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    out_lengths = torch.empty(nq, dtype=torch.int32, device=dev)
+    check(lib.esr_itemknn_recommend(_p(table_ids), _p(table_neighbours), _p(table_scores), _p(table_lengths),
+                                    table_ids.numel(), int(table_neighbours.shape[1]), _p(history), history.numel(),
+                                    _p(offsets), nq, int(k), int(bool(exclude_history)), _p(out_ids), _p(out_scores),
+                                    _p(out_lengths), _stream()), "esr_itemknn_recommend")
+    return out_ids, out_scores, out_lengths

@@ -964,6 +964,40 @@ int esr_terms_lookup(const int32_t* tokens, int64_t N, const void* lookup, int64
 int esr_terms_tfidf_rows(const void* scratch, int64_t capacity, const int32_t* index, const int32_t* row_off,
                          int64_t nrows, int64_t nnz, const double* idf, int64_t K, float* tfidf, esr_stream_t stream);
 
+/* ---- Item-to-item neighbours and the item-kNN recommender (esr_neighbours.hip; the reference's wikipedia/dump_dice.py:33-51
+ * ranks a row's partners by Dice score) ----
+ * Entries index / other int32[nnz], count float[nnz] as esr_cooccur_finalize returns them without the diagonal (either
+ * orientation, any order); ids int32[u] ascending and distinct, df float[u] their document frequencies (score 1 only).
+ * Row r = item ids[r]: both = 0 the entries with index == ids[r] (partner = other), both = 1 those with index == ids[r] or
+ * other == ids[r] (partner = the other end).  score 0: the joint count; score 1: count / (df[other] + df[index]), f32, no
+ * factor 2.  Per row the k best by (score descending, partner id ascending) -- a total order, so the result does not depend
+ * on atomic order or on the grid: out_neighbours int32[u, k] (-1 behind the row's end), out_scores / out_counts float[u, k]
+ * (0 there), out_lengths int32[u] = min(k, row length).  1 <= k <= 1024, nnz < 2^30.  An entry with an end that ids lacks is
+ * left out and raises bit 64 of the failure word = the first uint64 of the workspace (the caller reads it after the call).
+ * workspace: esr_neighbours_workspace_bytes(nnz, u, both) bytes, 16-byte aligned.
+ * esr_neighbours_plan_bounds: the row lengths at which the select changes class, ascending, into bounds[0 .. capacity);
+ * returns their number (3): rows of at most bounds[0] entries share a wave four at a time, at most bounds[1] take a wave,
+ * at most bounds[2] a workgroup's LDS, longer ones a radix select over global memory.
+ *   recommend   the table is what esr_neighbours_topk wrote (table_ids = ids, width = its k).  Query q has the history
+ *               history[offsets[q] .. offsets[q + 1]) (offsets int64[nq + 1] over history int32[N], device memory).  The score
+ *               of candidate c = the f32 sum of table_scores[row(h_p), j] over the (p, j) with table_neighbours[row(h_p), j]
+ *               == c, added left to right in ascending history position p; ids the table lacks add nothing; with
+ *               exclude_history candidates that occur in the history are dropped.  out_ids int32[nq, k] (-1 padded),
+ *               out_scores float[nq, k] (0 padded), out_lengths int32[nq]: the k best by (score descending, id ascending).
+ *               A query may gather at most esr_itemknn_max_entries() = history length x width entries (one workgroup sorts
+ *               them in LDS): the caller checks that; the kernel answers such a query with length -1, never truncated. */
+size_t esr_neighbours_workspace_bytes(int64_t nnz, int64_t u, int both);
+int esr_neighbours_plan_bounds(int32_t* bounds, int capacity);
+int esr_neighbours_topk(const int32_t* index, const int32_t* other, const float* count, int64_t nnz, const int32_t* ids,
+                        const float* df, int64_t u, int k, int both, int score, int32_t* out_neighbours,
+                        float* out_scores, float* out_counts, int32_t* out_lengths, void* workspace,
+                        size_t workspace_bytes, esr_stream_t stream);
+int esr_itemknn_max_entries(void);
+int esr_itemknn_recommend(const int32_t* table_ids, const int32_t* table_neighbours, const float* table_scores,
+                          const int32_t* table_lengths, int64_t u, int width, const int32_t* history, int64_t N,
+                          const int64_t* offsets, int64_t nq, int k, int exclude_history, int32_t* out_ids,
+                          float* out_scores, int32_t* out_lengths, esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
