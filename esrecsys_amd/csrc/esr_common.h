@@ -410,7 +410,7 @@ __device__ __forceinline__ void row_add4(RowRegs<VEC, NCH>& acc, const RowRegs<V
 }
 
 // optax.adagrad [upstream]: acc += g^2 ; p -= lr * g * rsqrt(acc + eps)  (0 where acc == 0).  ONE definition for every
-// kernel that applies it (esr_optim.hip, esr_glove_step.hip), so their results are bit-identical.
+// kernel that applies it (esr_optim.hip, esr_glove.hip), so their results are bit-identical.
 __device__ __forceinline__ void adagrad_elem(float& w, float& a, float gv, float lr, float eps) {
   // explicit roundings: no fused multiply-add may be formed here, whatever kernel this is inlined into
   const float acc = __fmaf_rn(gv, gv, a);

@@ -27,41 +27,60 @@ struct GloveWs {
   float* s;           // [B]
 };
 
-static size_t glove_ws_layout(int64_t B, char* base, GloveWs* ws) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
+// the unit's buffers are carved into 256-byte-aligned pieces (base null: only the size, `off`, is wanted)
+struct Carve {
+  char* base;
+  size_t off;
+  template <class T>
+  __host__ __device__ T* take(size_t count) {
     char* p = base ? base + off : nullptr;
-    off += align_up(bytes, 256);
-    return p;
-  };
-  double* a = (double*)take(sizeof(double) * 2 * kStatBlocks);
-  double* b = (double*)take(sizeof(double) * 3 * kPairBlocks);
-  float* s = (float*)take(sizeof(float) * (size_t)B);
+    off += align_up(sizeof(T) * count, 256);
+    return (T*)p;
+  }
+};
+
+static size_t glove_ws_layout(int64_t B, char* base, GloveWs* ws) {
+  Carve c{base, 0};
+  double* a = c.take<double>(2 * kStatBlocks);
+  double* b = c.take<double>(3 * kPairBlocks);
+  float* s = c.take<float>((size_t)B);
   if (ws) *ws = GloveWs{a, b, s};
-  return off;
+  return c.off;
 }
 
-// K_A: s_i = Bias[t1_i] + Bias[t2_i]; per-block partial (sum s, sum s^2) in fp64.
+// weight = min(1, c/100)^0.75 ; log_target = log10(1 + c)   (train_cooccurence.py:79-82)
+__device__ __forceinline__ float glove_weight(float c) { return powf(fminf(1.0f, c / 100.0f), 0.75f); }
+__device__ __forceinline__ float glove_log_target(float c) { return log10f(1.0f + c); }
+
+// K_A's work for workgroup blockIdx.x of `nblocks`: s_i = Bias[t1_i] + Bias[t2_i] (to s_out, if given) and the workgroup's
+// partial (sum s, sum s^2) in fp64 (to part, if given).  ONE definition: the grid and the per-thread order fix the bits
+// of the statistics, hence of sbar and every gdot.
+__device__ __forceinline__ void bias_stats_block(const float* __restrict__ bias, const int32_t* __restrict__ inputs,
+                                                 int64_t B, int nblocks, float* __restrict__ s_out,
+                                                 double* __restrict__ part, double* sm /* >= 8 doubles */) {
+  double a = 0.0, a2 = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < B; i += (int64_t)nblocks * kBlock) {
+    const float s = bias[inputs[i]] + bias[inputs[B + i]];
+    if (s_out) s_out[i] = s;
+    a += (double)s;
+    a2 += (double)s * (double)s;
+  }
+  if (!part) return;
+  const double t = block_sum_d(a, sm);
+  const double t2 = block_sum_d(a2, sm + 4);
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = t;
+    part[2 * blockIdx.x + 1] = t2;
+  }
+}
+
+// K_A: s_i and the per-block partials.
 __global__ __launch_bounds__(kBlock) void glove_bias_stats_kernel(const float* __restrict__ bias,
                                                                  const int32_t* __restrict__ inputs,
                                                                  int64_t B, float* __restrict__ s_out,
                                                                  double* __restrict__ part) {
   __shared__ double sm[8];
-  double a = 0.0, a2 = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < B; i += (int64_t)gridDim.x * kBlock) {
-    const float s = bias[inputs[i]] + bias[inputs[B + i]];
-    s_out[i] = s;
-    a += (double)s;
-    a2 += (double)s * (double)s;
-  }
-  if (part) {
-    const double t = block_sum_d(a, sm);
-    const double t2 = block_sum_d(a2, sm + 4);
-    if (threadIdx.x == 0) {
-      part[2 * blockIdx.x] = t;
-      part[2 * blockIdx.x + 1] = t2;
-    }
-  }
+  bias_stats_block(bias, inputs, B, gridDim.x, s_out, part, sm);
 }
 
 // Every block re-reduces the <= 256 K_A partials in the same fixed order (4 KB from L2): this
@@ -84,6 +103,43 @@ __device__ __forceinline__ void reduce_stat_parts(const double* __restrict__ par
   *sum_s = sm[8];
   *sum_s2 = sm[9];
   __syncthreads();
+}
+
+// The [npair][3] loss partials (sum w, sum w r, sum w (r - center)^2) of a pairs / update launch, summed in THE fixed
+// order every path shares: the loss is bit-identical whichever launch reduces them.  ALL = false: the totals are valid
+// in thread 0 only (sm >= 12 doubles); true: broadcast to every thread (sm >= 15 doubles).
+template <bool ALL>
+__device__ __forceinline__ void reduce_pair_parts(const double* __restrict__ pair_part, int npair, double* sm, double* Sw,
+                                                  double* Swr, double* Swq) {
+  double a = 0.0, b = 0.0, c = 0.0;
+  for (int i = threadIdx.x; i < npair; i += kBlock) {
+    a += pair_part[3 * i];
+    b += pair_part[3 * i + 1];
+    c += pair_part[3 * i + 2];
+  }
+  *Sw = block_sum_d(a, sm);
+  *Swr = block_sum_d(b, sm + 4);
+  *Swq = block_sum_d(c, sm + 8);
+  if (!ALL) return;
+  if (threadIdx.x == 0) {
+    sm[12] = *Sw;
+    sm[13] = *Swr;
+    sm[14] = *Swq;
+  }
+  __syncthreads();
+  *Sw = sm[12];
+  *Swr = sm[13];
+  *Swq = sm[14];
+}
+
+// the loss scalar from the batch sums -- the ONE place its formula is written.  Reference mode:
+// L = (B sum w (r - sbar)^2 + sum w SS) / B^2 with SS = sum_i (s_i - sbar)^2 in fp64; diagonal mode: sum w (r - s)^2 / B.
+__device__ __forceinline__ float glove_loss_value(int mode, double Bd, double Sw, double Swq, double sum_s, double sum_s2,
+                                                  bool poisoned) {
+  if (mode != ESR_GLOVE_REFERENCE) return (float)(poisoned ? __builtin_nan("") : Swq / Bd);
+  double SS = sum_s2 - sum_s * sum_s / Bd;
+  if (SS < 0.0) SS = 0.0;
+  return (float)(poisoned ? __builtin_nan("") : (Bd * Swq + Sw * SS) / (Bd * Bd));
 }
 
 // K_B: one row group (G lanes) per pair.  LOSS=false is the forward-only path (dot only).
@@ -119,10 +175,8 @@ __global__ __launch_bounds__(kBlock) void glove_pairs_kernel(
       continue;
     }
     const float c_j = target[j];
-    // weight = min(1, c/100)^0.75 ; log_target = log10(1 + c)   (train_cooccurence.py:79-82)
-    const float w = powf(fminf(1.0f, c_j / 100.0f), 0.75f);
-    const float lt = log10f(1.0f + c_j);
-    const float r = lt - dot;
+    const float w = glove_weight(c_j);
+    const float r = glove_log_target(c_j) - dot;
     const float center = (mode == ESR_GLOVE_REFERENCE) ? sbar : s_in[j];
     const float gdot = -(two_over_B * w) * (r - center);
     if (lig == 0) {
@@ -171,34 +225,10 @@ __global__ __launch_bounds__(kBlock) void glove_finalize_kernel(
   mode &= ~ESR_GRADS_AT_IDS;
   double sum_s = 0.0, sum_s2 = 0.0;
   if (mode == ESR_GLOVE_REFERENCE) reduce_stat_parts(stat_part, nstat, sm, &sum_s, &sum_s2);
-  double a = 0.0, b = 0.0, c = 0.0;
-  for (int i = threadIdx.x; i < npair; i += kBlock) {
-    a += pair_part[3 * i];
-    b += pair_part[3 * i + 1];
-    c += pair_part[3 * i + 2];
-  }
-  const double tw = block_sum_d(a, sm);
-  const double twr = block_sum_d(b, sm + 4);
-  const double twq = block_sum_d(c, sm + 8);
-  if (threadIdx.x == 0) {
-    sm[12] = tw;
-    sm[13] = twr;
-    sm[14] = twq;
-  }
-  __syncthreads();
-  const double Sw = sm[12], Swr = sm[13], Swq = sm[14];
+  double Sw, Swr, Swq;
+  reduce_pair_parts<true>(pair_part, npair, sm, &Sw, &Swr, &Swq);
   const double Bd = (double)B;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    double L;
-    if (mode == ESR_GLOVE_REFERENCE) {
-      double SS = sum_s2 - sum_s * sum_s / Bd;  // sum_i (s_i - sbar)^2, fp64
-      if (SS < 0.0) SS = 0.0;
-      L = (Bd * Swq + Sw * SS) / (Bd * Bd);
-    } else {
-      L = Swq / Bd;
-    }
-    loss[0] = (float)L;
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) loss[0] = glove_loss_value(mode, Bd, Sw, Swq, sum_s, sum_s2, false);
   if (mode == ESR_GLOVE_REFERENCE && grad_bias) {
     const float k = (float)(2.0 / (Bd * Bd));
     const float fSw = (float)Sw, fSwr = (float)Swr;
@@ -259,21 +289,16 @@ constexpr int kStatWords = 96;
 constexpr int kFinAccs = 6;                                // (sum w, sum w r, sum w q^2) x (hi, lo)
 constexpr int kFinWords = kFinAccs * kFixAccWords + 32;    // + [0] arrivals of finished accumulators, [16] poison
 constexpr int64_t kFinFuseMaxIds = 8192;  // lists up to this long: the update kernel's last workgroup is the finalize step
-static size_t glove_plan_layout(int64_t B, char* base, GlovePlan* out) {
-  const int64_t n = 2 * B;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align_up(bytes, 256);
-    return p;
-  };
+// (host and device: glove_plan_kernel finds a plan's parts through it too -- the layout is written here only)
+__host__ __device__ static size_t glove_plan_layout(int64_t B, char* base, GlovePlan* out) {
+  Carve c{base, 0};
   GlovePlan pl;
-  pl.flags = (int*)take(sizeof(int) * 64);
-  pl.stat = (unsigned long long*)take(sizeof(unsigned long long) * kStatWords);
-  pl.fin = (unsigned long long*)take(sizeof(unsigned long long) * kFinWords);
-  pl.meta = (float4*)take(sizeof(float4) * (size_t)n);
+  pl.flags = c.take<int>(64);
+  pl.stat = c.take<unsigned long long>(kStatWords);
+  pl.fin = c.take<unsigned long long>(kFinWords);
+  pl.meta = c.take<float4>((size_t)(2 * B));
   if (out) *out = pl;
-  return off;
+  return c.off;
 }
 
 struct StepWs {
@@ -294,31 +319,26 @@ struct StepWs {
 };
 
 static size_t step_ws_layout(int64_t B, int D, char* base, StepWs* ws) {
-  const int64_t n = 2 * B;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align_up(bytes, 256);
-    return p;
-  };
+  const size_t n = (size_t)(2 * B);
+  Carve c{base, 0};
   StepWs w;
-  w.sorted_ids = (int32_t*)take(sizeof(int32_t) * (size_t)n);
-  w.perm = (int32_t*)take(sizeof(int32_t) * (size_t)n);
-  w.bias_info = (double2*)take(sizeof(double2) * (size_t)n);
-  w.pair_part = (double*)take(sizeof(double) * 3 * kPairBlocks);
+  w.sorted_ids = c.take<int32_t>(n);
+  w.perm = c.take<int32_t>(n);
+  w.bias_info = c.take<double2>(n);
+  w.pair_part = c.take<double>(3 * kPairBlocks);
   // the resolved mode's records exist for long lists only (kResolveMinIds); short ones resolve inside the update kernel
-  const bool res = n > kResolveMinIds;
-  w.own_code = (uint32_t*)take(res ? sizeof(uint32_t) * (size_t)n : 0);
-  w.meta_res = (float4*)take(res ? sizeof(float4) * (size_t)n : 0);
-  w.stat_part = (double*)take(sizeof(double) * 2 * kStatBlocks);
-  w.res_flags = (int*)take(sizeof(int) * 64);
-  w.pair_tot = (double*)take(sizeof(double) * 4);
-  w.chunk_rows = (float*)take(sizeof(float) * 2 * (size_t)cdiv(n, kStepChunk) * (size_t)D);
-  w.plan = take(glove_plan_layout(B, nullptr, nullptr));
-  w.sort_ws_bytes = esr_segment_sort_workspace_bytes(n);
-  w.sort_ws = take(w.sort_ws_bytes);
+  const bool res = 2 * B > kResolveMinIds;
+  w.own_code = c.take<uint32_t>(res ? n : 0);
+  w.meta_res = c.take<float4>(res ? n : 0);
+  w.stat_part = c.take<double>(2 * kStatBlocks);
+  w.res_flags = c.take<int>(64);
+  w.pair_tot = c.take<double>(4);
+  w.chunk_rows = c.take<float>(2 * (size_t)cdiv(2 * B, kStepChunk) * (size_t)D);
+  w.plan = c.take<char>(glove_plan_layout(B, nullptr, nullptr));
+  w.sort_ws_bytes = esr_segment_sort_workspace_bytes(2 * B);
+  w.sort_ws = c.take<char>(w.sort_ws_bytes);
   if (ws) *ws = w;
-  return off;
+  return c.off;
 }
 
 constexpr int kMaxGlovePlanBatch = 8;
@@ -326,6 +346,29 @@ struct GlovePlanBatch {
   const int32_t* inputs[kMaxGlovePlanBatch];
   const float* target[kMaxGlovePlanBatch];
 };
+
+// What a sorted position brings from the pair lists (no table is read): occurrence o = perm[p] is side o >= B of pair
+// j = o mod B.  ONE definition for the plan made ahead and the records resolved per step.
+struct GloveOcc {
+  int32_t own, partner;  // the id at this position (= sorted[p]) and the pair's other id
+  bool side;             // own is the pair's second id
+  float w, lt;           // glove_weight, glove_log_target of the pair's count
+  __device__ int32_t t1() const { return side ? partner : own; }
+  __device__ int32_t t2() const { return side ? own : partner; }
+  __device__ uint32_t partner_code() const { return (uint32_t)partner | (side ? kSideBit : 0u); }
+};
+__device__ __forceinline__ GloveOcc glove_occ(int64_t o, const int32_t* __restrict__ inputs,
+                                              const float* __restrict__ target, int64_t B) {
+  GloveOcc oc;
+  oc.side = o >= B;
+  const int64_t j = oc.side ? o - B : o;
+  oc.own = inputs[o];
+  oc.partner = inputs[oc.side ? j : B + j];
+  const float c_j = target[j];
+  oc.w = glove_weight(c_j);
+  oc.lt = glove_log_target(c_j);
+  return oc;
+}
 
 // plan: one thread per sorted position of list blockIdx.y; nothing here reads a table.  hints[list] = gen when some run
 // of equal ids is longer than kStepChunk positions (only then can the update kernel park a chunk partial).
@@ -339,30 +382,17 @@ __global__ __launch_bounds__(kBlock) void glove_plan_kernel(GlovePlanBatch pb, c
   const int32_t* __restrict__ perm = perm_all + (int64_t)list * n;
   const int32_t* __restrict__ inputs = pb.inputs[list];
   const float* __restrict__ target = pb.target[list];
-  char* base = plans + (size_t)list * plan_stride;
-  int* flags = (int*)base;
-  unsigned long long* stat = (unsigned long long*)(base + 256);
-  const size_t kFinOff = 256 + align_up(sizeof(unsigned long long) * kStatWords, 256);
-  unsigned long long* fin = (unsigned long long*)(base + kFinOff);
-  float4* meta = (float4*)(base + kFinOff + align_up(sizeof(unsigned long long) * kFinWords, 256));
+  GlovePlan pl;
+  glove_plan_layout(B, plans + (size_t)list * plan_stride, &pl);
   if (blockIdx.x == 0) {
-    if (threadIdx.x < 64) flags[threadIdx.x] = 0;
-    if (threadIdx.x < kStatWords) stat[threadIdx.x] = 0ull;
-    for (int i = threadIdx.x; i < kFinWords; i += kBlock) fin[i] = 0ull;
+    if (threadIdx.x < 64) pl.flags[threadIdx.x] = 0;
+    if (threadIdx.x < kStatWords) pl.stat[threadIdx.x] = 0ull;
+    for (int i = threadIdx.x; i < kFinWords; i += kBlock) pl.fin[i] = 0ull;
   }
   bool long_run = false;
   for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kBlock) {
-    const int64_t o = perm[p];
-    const bool side = o >= B;
-    const int64_t j = side ? o - B : o;
-    const int32_t partner = side ? inputs[j] : inputs[B + j];
-    const float c_j = target[j];
-    float4 m;
-    m.x = __uint_as_float((uint32_t)partner | (side ? kSideBit : 0u));
-    m.y = powf(fminf(1.0f, c_j / 100.0f), 0.75f);  // weight = min(1, c/100)^0.75   (train_cooccurence.py:79-81)
-    m.z = log10f(1.0f + c_j);                      // log10(1 + c)                  (train_cooccurence.py:82)
-    m.w = 0.f;
-    meta[p] = m;
+    const GloveOcc oc = glove_occ(perm[p], inputs, target, B);
+    pl.meta[p] = make_float4(__uint_as_float(oc.partner_code()), oc.w, oc.lt, 0.f);
     if (p + kStepChunk < n && sorted[p] == sorted[p + kStepChunk]) long_run = true;
   }
   if (hints && __any(long_run) && (threadIdx.x & 63) == 0) hints[list] = gen;  // (every writer stores the same value)
@@ -382,35 +412,13 @@ __global__ __launch_bounds__(kBlock) void glove_resolve_kernel(const int32_t* __
                                                               double* __restrict__ stat_part, int* __restrict__ flags) {
   __shared__ double sm[8];
   if (blockIdx.x == 0 && threadIdx.x == 0) flags[0] = 0;  // parked: set by the update kernel
-  if ((int)blockIdx.x < nstat) {
-    double a = 0.0, a2 = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < B; i += (int64_t)nstat * kBlock) {
-      const float s = bias[inputs[i]] + bias[inputs[B + i]];
-      a += (double)s;
-      a2 += (double)s * (double)s;
-    }
-    const double t = block_sum_d(a, sm);
-    const double t2 = block_sum_d(a2, sm + 4);
-    if (threadIdx.x == 0) {
-      stat_part[2 * blockIdx.x] = t;
-      stat_part[2 * blockIdx.x + 1] = t2;
-    }
-  }
+  if ((int)blockIdx.x < nstat) bias_stats_block(bias, inputs, B, nstat, nullptr, stat_part, sm);
   const int64_t n = 2 * B;
   for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kBlock) {
     const int32_t id = sorted_ids[p];
-    const int64_t o = perm[p];
-    const bool side = o >= B;
-    const int64_t j = side ? o - B : o;
-    const int32_t t1 = inputs[j], t2 = inputs[B + j];
-    const int32_t partner = side ? t1 : t2;
-    const float c_j = target[j];
-    float4 m;
-    m.x = __uint_as_float((uint32_t)partner | ((loc[partner] & 1) ? kLocBit : 0u) | (side ? kSideBit : 0u));
-    m.y = powf(fminf(1.0f, c_j / 100.0f), 0.75f);  // weight = min(1, c/100)^0.75   (train_cooccurence.py:79-81)
-    m.z = log10f(1.0f + c_j);                      // log10(1 + c)                  (train_cooccurence.py:82)
-    m.w = bias[t1] + bias[t2];
-    meta[p] = m;
+    const GloveOcc oc = glove_occ(perm[p], inputs, target, B);
+    const uint32_t pcode = oc.partner_code() | ((loc[oc.partner] & 1) ? kLocBit : 0u);
+    meta[p] = make_float4(__uint_as_float(pcode), oc.w, oc.lt, bias[oc.t1()] + bias[oc.t2()]);
     own_code[p] = (uint32_t)id | ((loc[id] & 1) ? kLocBit : 0u);
   }
 }
@@ -510,14 +518,6 @@ __device__ __forceinline__ double glove_swq(int mode, double Bd, double Sw, doub
   const double sb = (double)(float)(sum_s / Bd);
   const double v = S3 - 2.0 * sb * Swr + sb * sb * Sw;
   return v < 0.0 ? 0.0 : v;
-}
-// the loss scalar from the batch sums (glove_finalize_kernel's formula)
-__device__ __forceinline__ float glove_loss_value(int mode, double Bd, double Sw, double Swq, double sum_s, double sum_s2,
-                                                  bool poisoned) {
-  if (mode != ESR_GLOVE_REFERENCE) return (float)(poisoned ? __builtin_nan("") : Swq / Bd);
-  double SS = sum_s2 - sum_s * sum_s / Bd;
-  if (SS < 0.0) SS = 0.0;
-  return (float)(poisoned ? __builtin_nan("") : (Bd * Swq + Sw * SS) / (Bd * Bd));
 }
 
 // update: the structure of segment_update_kernel (esr_optim.hip) with the gradient rows produced on the fly.
@@ -859,23 +859,6 @@ __global__ __launch_bounds__(kBlock) void glove_step_kernel(
   }
 }
 
-// the versioned read-modify-write of one row with its summed gradient g: the row was read where `code` says it lives
-// (`own`), its new value goes to the OTHER buffer and the byte flips and takes this step's stamp, as on every other path
-// (nobody reads `loc` during this launch: the resolve kernel resolved every address).  `a` = the row's accumulator,
-// loaded by the caller next to `own`.
-template <int VEC, int NCH, class TR>
-__device__ __forceinline__ void step_apply_resolved(TR* __restrict__ emb0, TR* __restrict__ emb1, uint8_t* __restrict__ loc,
-                                           float* __restrict__ accum, uint32_t code, uint32_t T, const RowRegs<VEC, NCH>& own,
-                                           RowRegs<VEC, NCH>& a, const RowRegs<VEC, NCH>& g, int D, int lig, int G,
-                                           int nvec, float lr, float eps) {
-  const int64_t id = code & kIdMask;
-  RowRegs<VEC, NCH> w = own;
-  row_adagrad(w, a, g, lr, eps);
-  row_store(a, accum + id * D, lig, G, nvec);
-  row_store(w, ((code & kLocBit) ? emb0 : emb1) + id * D, lig, G, nvec);
-  if (lig == 0) loc[id] = loc_written((code & kLocBit) ? 0u : 1u, T);
-}
-
 // update, RESOLVED records (long lists; round 2's kernel as it was: the templated in-kernel-resolution variant below
 // measured 0.169 ms per step at C3 against this one's 0.148 on the same box, alternating runs -- its third record in
 // flight and the in-kernel statistics make it more sensitive to the sort that runs beside it on the second stream):
@@ -1010,7 +993,8 @@ __global__ __launch_bounds__(kBlock) void glove_step_resolved_kernel(
     const bool ends = q == n || ((q == p + 1 ? code_n : own_code[q]) & kIdMask) != id;
     if (lig == 0) bias_info[p] = make_double2(bsum, (double)(e_run - p));
     if (head && ends) {
-      step_apply_resolved<VEC, NCH, TR>(emb0, emb1, loc, accum, code, T, own, a, g, D, lig, G, nvec, lr, eps);
+      // (nobody reads `loc` during this launch: the resolve kernel resolved every address)
+      step_apply<VEC, NCH, TR>(emb0, emb1, loc, accum, code, T, own, a, g, D, lig, G, nvec, lr, eps);
     } else {  // a chunk of a long run: park the partial sum for glove_step_long_kernel
       const int64_t slot = 2 * (p / kStepChunk) + (head ? 1 : 0);
       row_store(g, chunk_rows + slot * D, lig, G, nvec);
@@ -1040,15 +1024,8 @@ __global__ __launch_bounds__(kBlock) void glove_step_long_kernel(
   // a thousand partials each
   if (pair_tot && blockIdx.x == gridDim.x - 1) {
     __shared__ double smp[12];
-    double a = 0.0, b = 0.0, c = 0.0;
-    for (int i = threadIdx.x; i < npair; i += kBlock) {
-      a += pair_part[3 * i];
-      b += pair_part[3 * i + 1];
-      c += pair_part[3 * i + 2];
-    }
-    const double tw = block_sum_d(a, smp);
-    const double twr = block_sum_d(b, smp + 4);
-    const double twq = block_sum_d(c, smp + 8);
+    double tw, twr, twq;
+    reduce_pair_parts<false>(pair_part, npair, smp, &tw, &twr, &twq);
     if (threadIdx.x == 0) {
       pair_tot[0] = tw;
       pair_tot[1] = twr;
@@ -1087,18 +1064,34 @@ __global__ __launch_bounds__(kBlock) void glove_step_long_kernel(
       });
 }
 
-// finalize: the loss (same formula as glove_finalize_kernel) and the bias table's Adagrad step, one thread per sorted
-// position; a run head holds its run's sums.  Reference mode: sum over the run of dL/ds = -(2/B^2) (cnt * Swr - Sw *
-// sum s); diagonal mode: the sum of gdot itself.  Every workgroup re-reduces the update kernel's <= 2048 x 3 loss
-// partials in the same fixed order (48 KB out of L2), so it depends on no other launch.
+// where glove_step_finalize_kernel finds the batch's three loss sums and (reference mode) its bias statistics
+struct GloveSums {
+  enum Kind { kAccumulators, kTotals, kPartials } kind;
+  const unsigned long long *stat, *fin;  // kAccumulators
+  const double *stat_part, *pair;        // kTotals, kPartials: K_A's nstat partials (glove_resolve_kernel); the loss sums
+  int nstat, npair;
+  // short lists: the update kernel left the loss sums in the plan's integer accumulators (fin_arrive -- the totals its own
+  // last workgroup uses when it is the finalize step itself) and the statistics in the plan's words; both carry a poison word
+  static GloveSums accumulators(const unsigned long long* stat, const unsigned long long* fin) {
+    return GloveSums{kAccumulators, stat, fin, nullptr, nullptr, 0, 0};
+  }
+  // resolved mode, after the long-run launch: its last workgroup reduced the partials to pair_tot[3]
+  static GloveSums totals(const double* stat_part, int nstat, const double* pair_tot) {
+    return GloveSums{kTotals, nullptr, nullptr, stat_part, pair_tot, nstat, 0};
+  }
+  // resolved mode, no long-run launch: every workgroup reduces pair_part[npair][3] itself (<= 48 KB out of L2; the same
+  // sums in the same order), so it depends on no other launch
+  static GloveSums partials(const double* stat_part, int nstat, const double* pair_part, int npair) {
+    return GloveSums{kPartials, nullptr, nullptr, stat_part, pair_part, nstat, npair};
+  }
+};
+
+// finalize: the loss and the bias table's Adagrad step, one thread per sorted position; a run head holds its run's
+// sums.  Reference mode: sum over the run of dL/ds = -(2/B^2) (cnt * Swr - Sw * sum s); diagonal mode: the sum of gdot
+// itself.
 __global__ __launch_bounds__(kBlock) void glove_step_finalize_kernel(
-    int64_t B, int mode, const unsigned long long* __restrict__ stat, int nstat, const double* __restrict__ stat_part,
-    int npair, const double* __restrict__ pair_part, const double* __restrict__ pair_tot,
-    const unsigned long long* __restrict__ fin, const int32_t* __restrict__ sorted_ids,
-    const double2* __restrict__ bias_info, float* __restrict__ bias, float* __restrict__ bias_accum, float lr, float eps,
-    float* __restrict__ loss) {
-  // fin (short lists): the update kernel left the three loss sums in its integer accumulators (fin_arrive) -- the same
-  // totals its own last workgroup uses when it is the finalize step itself
+    int64_t B, int mode, GloveSums src, const int32_t* __restrict__ sorted_ids, const double2* __restrict__ bias_info,
+    float* __restrict__ bias, float* __restrict__ bias_accum, float lr, float eps, float* __restrict__ loss) {
   __shared__ double sm[16];
   // this thread's position: everything it needs from memory is requested before the reductions below
   const int64_t n = 2 * B;
@@ -1116,53 +1109,36 @@ __global__ __launch_bounds__(kBlock) void glove_step_finalize_kernel(
       acc = bias_accum[id];
     }
   }
+  const bool ref = mode == ESR_GLOVE_REFERENCE, words = src.kind == GloveSums::kAccumulators;
+  // (a by-value struct's pointers carry no __restrict__: without these the kernel takes two more registers)
+  const unsigned long long *__restrict__ stat = src.stat, *__restrict__ fin = src.fin;
+  const double *__restrict__ stat_part = src.stat_part, *__restrict__ pair = src.pair;
   double Sw, Swr, Swq;
-  if (fin) {
+  if (words) {
     Sw = fin_value(fin, 0);
     Swr = fin_value(fin, 1);
-    Swq = glove_swq(mode, (double)B, Sw, Swr, fin_value(fin, 2),
-                    mode == ESR_GLOVE_REFERENCE ? fixed2_value(stat[0], stat[16]) : 0.0);
-  } else if (pair_tot) {  // reduced by the long-run launch
-    Sw = pair_tot[0];
-    Swr = pair_tot[1];
-    Swq = pair_tot[2];
+    Swq = glove_swq(mode, (double)B, Sw, Swr, fin_value(fin, 2), ref ? fixed2_value(stat[0], stat[16]) : 0.0);
+  } else if (src.kind == GloveSums::kTotals) {
+    Sw = pair[0];
+    Swr = pair[1];
+    Swq = pair[2];
   } else {
-    double a = 0.0, b = 0.0, c = 0.0;
-    for (int i = threadIdx.x; i < npair; i += kBlock) {
-      a += pair_part[3 * i];
-      b += pair_part[3 * i + 1];
-      c += pair_part[3 * i + 2];
-    }
-    const double tw = block_sum_d(a, sm);
-    const double twr = block_sum_d(b, sm + 4);
-    const double twq = block_sum_d(c, sm + 8);
-    if (threadIdx.x == 0) {
-      sm[12] = tw;
-      sm[13] = twr;
-      sm[14] = twq;
-    }
-    __syncthreads();
-    Sw = sm[12];
-    Swr = sm[13];
-    Swq = sm[14];
+    reduce_pair_parts<true>(pair, src.npair, sm, &Sw, &Swr, &Swq);
   }
   const double Bd = (double)B;
-  double rs = 0.0, rs2 = 0.0;
-  if (blockIdx.x == 0 && stat_part && mode == ESR_GLOVE_REFERENCE)  // resolved mode: K_A's partials, K_A's order
-    reduce_stat_parts(stat_part, nstat, sm, &rs, &rs2);
+  double sum_s = 0.0, sum_s2 = 0.0;
+  if (blockIdx.x == 0 && !words && ref)  // resolved mode: K_A's partials, K_A's order
+    reduce_stat_parts(stat_part, src.nstat, sm, &sum_s, &sum_s2);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    double L;
-    if (mode == ESR_GLOVE_REFERENCE) {
-      const bool poisoned = (!stat_part && *reinterpret_cast<const unsigned*>(stat + 80) != 0u) || (fin && fin_poisoned(fin));
-      const double sum_s = stat_part ? rs : fixed2_value(stat[0], stat[16]);
-      const double sum_s2 = stat_part ? rs2 : fixed2_value(stat[32], stat[48]);
-      double SS = sum_s2 - sum_s * sum_s / Bd;
-      if (SS < 0.0) SS = 0.0;
-      L = poisoned ? __builtin_nan("") : (Bd * Swq + Sw * SS) / (Bd * Bd);
-    } else {
-      L = (fin && fin_poisoned(fin)) ? __builtin_nan("") : Swq / Bd;
+    bool poisoned = false;
+    if (words) {
+      if (ref) {
+        sum_s = fixed2_value(stat[0], stat[16]);
+        sum_s2 = fixed2_value(stat[32], stat[48]);
+      }
+      poisoned = (ref && *reinterpret_cast<const unsigned*>(stat + 80) != 0u) || fin_poisoned(fin);
     }
-    loss[0] = (float)L;
+    loss[0] = glove_loss_value(mode, Bd, Sw, Swq, sum_s, sum_s2, poisoned);
   }
   if (head) {
     const double k = 2.0 / (Bd * Bd);
@@ -1298,23 +1274,6 @@ static void launch_glove_plan(const int32_t* const* inputs, const float* const* 
                      hints, gen);
 }
 
-// hint[0] = gen when sorted_ids has a run of equal ids longer than `chunk` positions
-__global__ __launch_bounds__(kBlock) void long_run_hint_kernel(const int32_t* __restrict__ sorted_ids, int64_t n, int chunk,
-                                                              int* __restrict__ hint, int gen) {
-  bool long_run = false;
-  for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p + chunk < n; p += (int64_t)gridDim.x * kBlock)
-    if (sorted_ids[p] == sorted_ids[p + chunk]) long_run = true;
-  if (__any(long_run) && (threadIdx.x & 63) == 0) hint[0] = gen;
-}
-
-int esr_long_run_hint(const int32_t* sorted_ids, int64_t n, int chunk, int32_t* hint, int32_t gen, esr_stream_t stream) {
-  ESR_REQUIRE(n >= 0 && chunk > 0 && hint && (n == 0 || sorted_ids), "esr_long_run_hint: bad arguments");
-  if (n <= chunk) return ESR_OK;
-  const int grid = (int)std::min<int64_t>(kMaxGrid, cdiv(n, kBlock));
-  hipLaunchKernelGGL(long_run_hint_kernel, dim3(grid), dim3(kBlock), 0, as_stream(stream), sorted_ids, n, chunk, hint, gen);
-  return check_launch("esr_long_run_hint");
-}
-
 int esr_glove_plan(const int32_t* const* inputs, const float* const* targets, int nbatch, int64_t B,
                    const int32_t* sorted_ids, const int32_t* perm, void* plans, int32_t* hints, int32_t gen,
                    esr_stream_t stream) {
@@ -1331,137 +1290,180 @@ int esr_glove_plan(const int32_t* const* inputs, const float* const* targets, in
 
 }  // extern "C"
 
-struct GloveTables {
-  void* emb;         // f32 or bf16 rows (dtype)
-  void* emb_shadow;
-  uint8_t* emb_loc;
-  float* emb_accum;
-  float* bias;
-  float* bias_accum;
-  int D;
-  int dtype;
+// The unit's environment switches, read ONCE per entry-point call (not per process: a caller may change them between
+// two calls) and passed down.
+struct GloveMode {
+  bool vec8;       // ESR_BF16_VEC8=1: bf16 rows as 8 elements (16 bytes) per lane when the width allows (row_geom8) --
+                   // 150 registers, three waves per SIMD instead of four: see esr_triplet_step.hip
+  bool fin_fused;  // ESR_GLOVE_FIN_FUSED=0 keeps the finalize launch of short lists; default: the update kernel's last
+                   // workgroup is the finalize step
+};
+static GloveMode glove_mode() {
+  const char *v8 = getenv("ESR_BF16_VEC8"), *ff = getenv("ESR_GLOVE_FIN_FUSED");
+  return GloveMode{v8 && v8[0] == '1', !(ff && ff[0] == '0')};
+}
+
+// what both step entry points are given besides their batches, and what they check of it
+struct GloveStepArgs {
+  const char* who;
+  void* emb; void* emb_shadow; uint8_t* emb_loc; float* emb_accum; float* bias; float* bias_accum;  // emb: f32 or bf16 (dtype)
+  int64_t V;
+  int dtype, D;
+  int64_t B;
+  int mode;
+  float lr, eps;
+  void* workspace;
+  size_t workspace_bytes;
+};
+static int glove_step_checks(const GloveStepArgs& a) {
+  const char* who = a.who;
+  ESR_REQUIRE(a.B > 0 && a.V > 0 && a.D > 0, "%s: bad sizes V=%lld D=%d B=%lld", who, (long long)a.V, a.D, (long long)a.B);
+  ESR_REQUIRE(a.V <= (int64_t)kIdMask, "%s: V=%lld exceeds 2^30 - 1 rows", who, (long long)a.V);
+  ESR_REQUIRE(2 * a.B < ((int64_t)1 << 31), "%s: B=%lld too large", who, (long long)a.B);
+  ESR_REQUIRE(a.mode == ESR_GLOVE_REFERENCE || a.mode == ESR_GLOVE_DIAGONAL, "%s: bad mode %d", who, a.mode);
+  ESR_REQUIRE(a.emb && a.emb_shadow && a.emb_loc && a.emb_accum && a.bias && a.bias_accum, "%s: null table pointer", who);
+  ESR_REQUIRE(a.emb != a.emb_shadow, "%s: the shadow table must be a second buffer", who);
+  ESR_REQUIRE(a.dtype == ESR_F32 || a.dtype == ESR_BF16, "%s: bad dtype %d", who, a.dtype);
+  ESR_REQUIRE(a.dtype == ESR_F32 || a.D % 4 != 0 || !(((uintptr_t)a.emb | (uintptr_t)a.emb_shadow) & 7),
+              "%s: bf16 tables must be 8-byte aligned", who);
+  if (int rc = check_dim(who, a.D)) return rc;
+  const size_t need = esr_glove_step_workspace_bytes(a.B, a.D);
+  if (!a.workspace || a.workspace_bytes < need || ((uintptr_t)a.workspace & 15)) {
+    set_error("%s: workspace %zu bytes < %zu required (or misaligned)", who, a.workspace_bytes, need);
+    return ESR_EWORKSPACE;
+  }
+  return ESR_OK;
+}
+
+// one batch: its pair lists, sorted occurrence list and plan (null: made in line), what the caller knows about long
+// runs, and where its loss goes
+struct GloveBatch {
+  const int32_t* inputs;
+  const float* target;
+  const int32_t *sorted, *perm;
+  void* plan;
+  int long_runs;      // 0 = the caller knows (esr_glove_plan's hint) that no run outgrows its head chunk: no `long` launch
+  int blocks_per_cu;  // > 0: the update kernel's grid is what fits with so many workgroups per CU (default: all that fit)
+  // The update kernel's first workgroup stores start_value at start_flag as it starts.  A second stream gated on the
+  // word (esr_stream_gate) is released as the update kernel runs, so what it brings (the id sort of a coming batch)
+  // arrives after that kernel has taken its wave slots.  Arriving first, the sort's workgroups kept part of the update
+  // kernel's single resident wave-set waiting for a slot: 126 against 109 us for the same kernel.  (An event recorded
+  // in front of it did the same job, but the marker cost the main queue ~7 us between resolve and update.)
+  uint32_t* start_flag;
+  uint32_t start_value;
+  float* loss;
 };
 
-// one step's launches (arguments validated by the callers); T: the embedding rows' element type (GloveTables::dtype)
-template <class T>
-static void launch_glove_step_t(const GloveTables& t, const int32_t* inputs, const float* target, int64_t B, int mode,
-                              float lr, float eps, uint32_t stamp, const int32_t* sorted_ids, const int32_t* perm,
-                              void* plan, int long_runs, int blocks_per_cu, uint32_t* start_flag,
-                              uint32_t start_value, float* loss, const StepWs& ws, hipStream_t st) {
-  const int64_t n = 2 * B;
-  const int D = t.D;
-  // bf16 rows: 8 elements (16 bytes) per lane when the width allows (row_geom8)
-  // -- ESR_BF16_VEC8=1 only (150 registers, three waves per SIMD instead of four: see esr_triplet_step.hip)
-  const char* v8 = getenv("ESR_BF16_VEC8");
-  const bool vec8 = v8 && v8[0] == '1' && sizeof(T) == 2 && D % 8 == 0 && !(((uintptr_t)t.emb | (uintptr_t)t.emb_shadow) & 15);
-  const RowGeom g = vec8 ? row_geom8(D) : row_geom(D);
-  int grid = grid_for_groups(n, g.G);
+// the long-run launch of either path: `parked` = the path's flag word; resolved mode also has its last workgroup reduce
+// the update kernel's npair loss partials to pair_tot
+template <int VEC, int NCH, class T>
+static void launch_long(const GloveStepArgs& a, const RowGeom& g, const GloveBatch& b, uint32_t stamp, const StepWs& ws,
+                        const int* parked, int npair, const double* pair_part, double* pair_tot, hipStream_t st) {
+  const int64_t n = 2 * a.B;
   const int grid2 = (int)std::min<int64_t>(kMaxGrid, cdiv(cdiv(n, kStepChunk), 4));
-  const int nfin = (int)cdiv(n, kBlock);  // one thread per sorted position
-  if (n > kResolveMinIds) {
-    // long list: a resolve launch (round 2's plan kernel: row codes with the location bits, w, log10(1 + c), s and K_A's
-    // statistics) in front of the update kernel, which then walks resolved records -- see kResolveMinIds.  A plan made
-    // ahead is not used here (its records carry no locations).
-    const int nstat = (int)std::min<int64_t>(kStatBlocks, cdiv(B, kBlock));
-    const int nres = (int)std::max<int64_t>(nstat, std::min<int64_t>(kMaxGrid, cdiv(n, kBlock)));
-    ESR_KT("glove_resolve_kernel", st, hipLaunchKernelGGL(glove_resolve_kernel, dim3(nres), dim3(kBlock), 0, st, sorted_ids, perm, inputs, target,
-                       (const float*)t.bias, (const uint8_t*)t.emb_loc, B, nstat, ws.own_code, ws.meta_res, ws.stat_part,
-                       ws.res_flags));
-    // start_flag: the update kernel's first workgroup stores start_value there as it starts.  A second stream gated on
-    // the word (esr_stream_gate) is released as the update kernel runs, so what it brings (the id sort of a coming
-    // batch) arrives after that kernel has taken its wave slots.  Arriving first, the sort's workgroups kept part of
-    // the update kernel's single resident wave-set waiting for a slot: 126 against 109 us for the same kernel.  (An
-    // event recorded here did the same job, but the marker cost the main queue ~7 us between resolve and update.)
-    ESR_DISPATCH_ROW_ANY(g, { if constexpr (VEC != 8 || sizeof(T) == 2) {
-      static const int resident_all = resident_blocks((const void*)glove_step_resolved_kernel<VEC, NCH, T>, 0);
-      const int resident = blocks_per_cu > 0
-                               ? resident_blocks((const void*)glove_step_resolved_kernel<VEC, NCH, T>, blocks_per_cu)
-                               : resident_all;
-      grid = std::min(grid, resident);
-      ESR_KT("glove_step_resolved_kernel", st, hipLaunchKernelGGL((glove_step_resolved_kernel<VEC, NCH, T>), dim3(grid), dim3(kBlock), 0, st, (T*)t.emb, (T*)t.emb_shadow,
-                         t.emb_loc, t.emb_accum, D, g.G, (const uint32_t*)ws.own_code, (const float4*)ws.meta_res, n, B,
-                         mode, stamp, nstat, (const double*)ws.stat_part, lr, eps, ws.chunk_rows, ws.bias_info, ws.pair_part,
-                         ws.res_flags, start_flag, start_value));
-      // (its last workgroup also reduces the loss partials for the finalize kernel; when the caller knows that no run
-      // outgrows its head chunk -- long_runs == 0 -- it is skipped and every finalize workgroup reduces them itself,
-      // the same sums in the same order)
-      if (long_runs != 0)
-        ESR_KT("glove_step_long_kernel", st, hipLaunchKernelGGL((glove_step_long_kernel<VEC, NCH, T>), dim3(grid2), dim3(kBlock), 0, st, (T*)t.emb, (T*)t.emb_shadow,
-                           t.emb_loc, t.emb_accum, D, g.G, sorted_ids, n, stamp, lr, eps, (const float*)ws.chunk_rows,
-                           ws.bias_info, (const int*)ws.res_flags, grid, (const double*)ws.pair_part, ws.pair_tot));
-    }});
-    ESR_KT("glove_step_finalize_kernel", st, hipLaunchKernelGGL(glove_step_finalize_kernel, dim3(nfin), dim3(kBlock), 0, st, B, mode,
-                       (const unsigned long long*)nullptr, nstat, (const double*)ws.stat_part, grid,
-                       (const double*)ws.pair_part, long_runs != 0 ? (const double*)ws.pair_tot : (const double*)nullptr,
-                       (const unsigned long long*)nullptr, sorted_ids, (const double2*)ws.bias_info, t.bias, t.bias_accum,
-                       lr, eps, loss));
-    return;
-  }
-  if (!plan) {  // no plan made ahead: make it here (and nobody told us whether a run is long: screen for it)
-    launch_glove_plan(&inputs, &target, 1, sorted_ids, perm, B, ws.plan, 0, nullptr, 0, st);
-    plan = ws.plan;
-    long_runs = -1;
+  ESR_KT("glove_step_long_kernel", st,
+         hipLaunchKernelGGL((glove_step_long_kernel<VEC, NCH, T>), dim3(grid2), dim3(kBlock), 0, st, (T*)a.emb,
+                            (T*)a.emb_shadow, a.emb_loc, a.emb_accum, a.D, g.G, b.sorted, n, stamp, a.lr, a.eps,
+                            (const float*)ws.chunk_rows, ws.bias_info, parked, npair, pair_part, pair_tot));
+}
+
+// Long list (n > kResolveMinIds): a resolve launch (round 2's plan kernel: row codes with the location bits, w,
+// log10(1 + c), s and K_A's statistics) in front of the update kernel, which then walks resolved records.  A plan made
+// ahead is not used here (its records carry no locations).  T: the embedding rows' element type.
+template <int VEC, int NCH, class T>
+static void launch_resolved(const GloveStepArgs& a, const RowGeom& g, const GloveBatch& b, uint32_t stamp, const StepWs& ws,
+                            hipStream_t st) {
+  const int64_t B = a.B, n = 2 * B;
+  const int nstat = (int)std::min<int64_t>(kStatBlocks, cdiv(B, kBlock));
+  const int nres = (int)std::max<int64_t>(nstat, std::min<int64_t>(kMaxGrid, cdiv(n, kBlock)));
+  ESR_KT("glove_resolve_kernel", st,
+         hipLaunchKernelGGL(glove_resolve_kernel, dim3(nres), dim3(kBlock), 0, st, b.sorted, b.perm, b.inputs, b.target,
+                            (const float*)a.bias, (const uint8_t*)a.emb_loc, B, nstat, ws.own_code, ws.meta_res,
+                            ws.stat_part, ws.res_flags));
+  static const int resident_all = resident_blocks((const void*)glove_step_resolved_kernel<VEC, NCH, T>, 0);
+  const int resident = b.blocks_per_cu > 0
+                           ? resident_blocks((const void*)glove_step_resolved_kernel<VEC, NCH, T>, b.blocks_per_cu)
+                           : resident_all;
+  const int grid = std::min(grid_for_groups(n, g.G), resident);
+  ESR_KT("glove_step_resolved_kernel", st,
+         hipLaunchKernelGGL((glove_step_resolved_kernel<VEC, NCH, T>), dim3(grid), dim3(kBlock), 0, st, (T*)a.emb,
+                            (T*)a.emb_shadow, a.emb_loc, a.emb_accum, a.D, g.G, (const uint32_t*)ws.own_code,
+                            (const float4*)ws.meta_res, n, B, a.mode, stamp, nstat, (const double*)ws.stat_part, a.lr, a.eps,
+                            ws.chunk_rows, ws.bias_info, ws.pair_part, ws.res_flags, b.start_flag, b.start_value));
+  // (the long-run launch's last workgroup also reduces the loss partials for the finalize kernel; when the caller knows
+  // that no run outgrows its head chunk -- long_runs == 0 -- it is skipped and every finalize workgroup reduces them
+  // itself, the same sums in the same order)
+  if (b.long_runs != 0) launch_long<VEC, NCH, T>(a, g, b, stamp, ws, ws.res_flags, grid, ws.pair_part, ws.pair_tot, st);
+  const GloveSums sums = b.long_runs != 0 ? GloveSums::totals(ws.stat_part, nstat, ws.pair_tot)
+                                          : GloveSums::partials(ws.stat_part, nstat, ws.pair_part, grid);
+  ESR_KT("glove_step_finalize_kernel", st,
+         hipLaunchKernelGGL(glove_step_finalize_kernel, dim3((int)cdiv(n, kBlock)), dim3(kBlock), 0, st, B, a.mode, sums,
+                            b.sorted, (const double2*)ws.bias_info, a.bias, a.bias_accum, a.lr, a.eps, b.loss));
+}
+
+// Short list: the update kernel reads the stamped bytes and the bias values itself, on the plan made ahead (or here).
+template <int VEC, int NCH, class T>
+static void launch_planned(const GloveStepArgs& a, const GloveMode& gm, const RowGeom& g, GloveBatch b, uint32_t stamp,
+                           const StepWs& ws, hipStream_t st) {
+  const int64_t B = a.B, n = 2 * B;
+  if (!b.plan) {  // no plan made ahead: make it here (and nobody told us whether a run is long: screen for it)
+    launch_glove_plan(&b.inputs, &b.target, 1, b.sorted, b.perm, B, ws.plan, 0, nullptr, 0, st);
+    b.plan = ws.plan;
+    b.long_runs = -1;
   }
   GlovePlan pl;
-  glove_plan_layout(B, (char*)plan, &pl);
-  const int nstat = mode == ESR_GLOVE_REFERENCE ? (int)std::min<int64_t>(kStatBlocksStep, cdiv(B, kBlock)) : 0;
+  glove_plan_layout(B, (char*)b.plan, &pl);
+  const int nstat = a.mode == ESR_GLOVE_REFERENCE ? (int)std::min<int64_t>(kStatBlocksStep, cdiv(B, kBlock)) : 0;
   // no run outgrows its head chunk (the plan's hint) and the list is short: the update kernel's last workgroup is the
-  // finalize step (ESR_GLOVE_FIN_FUSED=0 keeps the launch)
-  const char* fin_env = getenv("ESR_GLOVE_FIN_FUSED");
-  const bool fin_fused_on = !(fin_env && fin_env[0] == '0');
-  const bool fuse_fin = fin_fused_on && long_runs == 0 && n <= kFinFuseMaxIds;
-  ESR_DISPATCH_ROW_ANY(g, { if constexpr (VEC != 8 || sizeof(T) == 2) {
-    // one resident wave-set: every group walks a contiguous slice, so a grid larger than what the chip holds at once
-    // only adds a second, partly filled round (94 VGPRs -> 5 blocks per CU: 2048 blocks ran as 1280 + 768); the
-    // prologue's wait also relies on the workgroups it waits for having been dispatched (they have: index order)
-    static const int resident_all = resident_blocks((const void*)glove_step_kernel<VEC, NCH, T>, 0);  // (one query)
-    const int resident = blocks_per_cu > 0 ? resident_blocks((const void*)glove_step_kernel<VEC, NCH, T>, blocks_per_cu)
+  // finalize step
+  const bool fuse_fin = gm.fin_fused && b.long_runs == 0 && n <= kFinFuseMaxIds;
+  // one resident wave-set: every group walks a contiguous slice, so a grid larger than what the chip holds at once
+  // only adds a second, partly filled round (94 VGPRs -> 5 blocks per CU: 2048 blocks ran as 1280 + 768); the
+  // prologue's wait also relies on the workgroups it waits for having been dispatched (they have: index order)
+  static const int resident_all = resident_blocks((const void*)glove_step_kernel<VEC, NCH, T>, 0);  // (one query)
+  const int resident = b.blocks_per_cu > 0 ? resident_blocks((const void*)glove_step_kernel<VEC, NCH, T>, b.blocks_per_cu)
                                            : resident_all;
-    grid = std::min(grid + nstat, std::max(resident, nstat + 1));  // nstat statistics-only workgroups in front
-    ESR_KT("glove_step_kernel", st, hipLaunchKernelGGL((glove_step_kernel<VEC, NCH, T>), dim3(grid), dim3(kBlock), 0, st, (T*)t.emb, (T*)t.emb_shadow, t.emb_loc,
-                       t.emb_accum, (const float*)t.bias, D, g.G, sorted_ids, (const float4*)pl.meta, inputs, n, B, mode,
-                       stamp, nstat, pl.stat, lr, eps, ws.chunk_rows, ws.bias_info, pl.fin, fuse_fin ? 1 : 0, t.bias,
-                       t.bias_accum, loss, pl.flags, start_flag, start_value));
-    if (long_runs != 0)  // 0 = the caller knows (esr_glove_plan's hint) that no run outgrows its head chunk
-      ESR_KT("glove_step_long_kernel", st, hipLaunchKernelGGL((glove_step_long_kernel<VEC, NCH, T>), dim3(grid2), dim3(kBlock), 0, st, (T*)t.emb, (T*)t.emb_shadow,
-                         t.emb_loc, t.emb_accum, D, g.G, sorted_ids, n, stamp, lr, eps, (const float*)ws.chunk_rows,
-                         ws.bias_info, (const int*)pl.flags, 0, (const double*)nullptr, (double*)nullptr));
-  }});
+  // nstat statistics-only workgroups in front
+  const int grid = std::min(grid_for_groups(n, g.G) + nstat, std::max(resident, nstat + 1));
+  ESR_KT("glove_step_kernel", st,
+         hipLaunchKernelGGL((glove_step_kernel<VEC, NCH, T>), dim3(grid), dim3(kBlock), 0, st, (T*)a.emb, (T*)a.emb_shadow,
+                            a.emb_loc, a.emb_accum, (const float*)a.bias, a.D, g.G, b.sorted, (const float4*)pl.meta,
+                            b.inputs, n, B, a.mode, stamp, nstat, pl.stat, a.lr, a.eps, ws.chunk_rows, ws.bias_info, pl.fin,
+                            fuse_fin ? 1 : 0, a.bias, a.bias_accum, b.loss, pl.flags, b.start_flag, b.start_value));
+  if (b.long_runs != 0) launch_long<VEC, NCH, T>(a, g, b, stamp, ws, pl.flags, 0, nullptr, nullptr, st);
   if (!fuse_fin)
-    ESR_KT("glove_step_finalize_kernel", st, hipLaunchKernelGGL(glove_step_finalize_kernel, dim3(nfin), dim3(kBlock), 0, st, B, mode,
-                       (const unsigned long long*)pl.stat, 0, (const double*)nullptr, grid, (const double*)nullptr,
-                       (const double*)nullptr, (const unsigned long long*)pl.fin, sorted_ids,
-                       (const double2*)ws.bias_info, t.bias, t.bias_accum, lr, eps, loss));
+    ESR_KT("glove_step_finalize_kernel", st,
+           hipLaunchKernelGGL(glove_step_finalize_kernel, dim3((int)cdiv(n, kBlock)), dim3(kBlock), 0, st, B, a.mode,
+                              GloveSums::accumulators(pl.stat, pl.fin), b.sorted, (const double2*)ws.bias_info, a.bias,
+                              a.bias_accum, a.lr, a.eps, b.loss));
 }
 
-static void launch_glove_step(const GloveTables& t, const int32_t* inputs, const float* target, int64_t B, int mode,
-                              float lr, float eps, uint32_t stamp, const int32_t* sorted_ids, const int32_t* perm,
-                              void* plan, int long_runs, int blocks_per_cu, uint32_t* start_flag,
-                              uint32_t start_value, float* loss, const StepWs& ws, hipStream_t st) {
-  if (t.dtype == ESR_BF16)
-    launch_glove_step_t<uint16_t>(t, inputs, target, B, mode, lr, eps, stamp, sorted_ids, perm, plan, long_runs,
-                                  blocks_per_cu, start_flag, start_value, loss, ws, st);
-  else
-    launch_glove_step_t<float>(t, inputs, target, B, mode, lr, eps, stamp, sorted_ids, perm, plan, long_runs,
-                               blocks_per_cu, start_flag, start_value, loss, ws, st);
+// nbatch steps with stamps first_stamp, first_stamp + 1, ...: batch(i) names step i's lists and plan.  One dispatch on
+// (dtype, vec8, row geometry) picks the kernels' instantiation; the list length picks the path (kResolveMinIds).
+template <int VEC, int NCH, class T>
+static void launch_glove_step(const GloveStepArgs& a, const GloveMode& gm, const RowGeom& g, const GloveBatch& b,
+                              uint32_t stamp, const StepWs& ws, hipStream_t st) {
+  if (2 * a.B > kResolveMinIds) launch_resolved<VEC, NCH, T>(a, g, b, stamp, ws, st);
+  else launch_planned<VEC, NCH, T>(a, gm, g, b, stamp, ws, st);
 }
-
-#define ESR_GLOVE_STEP_CHECKS(who)                                                                                    \
-  ESR_REQUIRE(B > 0 && V > 0 && D > 0, who ": bad sizes V=%lld D=%d B=%lld", (long long)V, D, (long long)B);          \
-  ESR_REQUIRE(V <= (int64_t)kIdMask, who ": V=%lld exceeds 2^30 - 1 rows", (long long)V);                             \
-  ESR_REQUIRE(2 * B < ((int64_t)1 << 31), who ": B=%lld too large", (long long)B);                                    \
-  ESR_REQUIRE(mode == ESR_GLOVE_REFERENCE || mode == ESR_GLOVE_DIAGONAL, who ": bad mode %d", mode);                  \
-  ESR_REQUIRE(emb && emb_shadow && emb_loc && emb_accum && bias && bias_accum, who ": null table pointer");           \
-  ESR_REQUIRE(emb != emb_shadow, who ": the shadow table must be a second buffer");                                   \
-  ESR_REQUIRE(dtype == ESR_F32 || dtype == ESR_BF16, who ": bad dtype %d", dtype);                                    \
-  ESR_REQUIRE(dtype == ESR_F32 || D % 4 != 0 || !(((uintptr_t)emb | (uintptr_t)emb_shadow) & 7),                      \
-              who ": bf16 tables must be 8-byte aligned");                                                            \
-  if (int rc = check_dim(who, D)) return rc;                                                                          \
-  if (!workspace || workspace_bytes < esr_glove_step_workspace_bytes(B, D) || ((uintptr_t)workspace & 15)) {          \
-    set_error(who ": workspace %zu bytes < %zu required (or misaligned)", workspace_bytes,                            \
-              esr_glove_step_workspace_bytes(B, D));                                                                  \
-    return ESR_EWORKSPACE;                                                                                            \
+template <class Batch>
+static int run_glove_steps(const GloveStepArgs& a, const GloveMode& gm, int nbatch, uint32_t first_stamp, Batch batch,
+                           const StepWs& ws, hipStream_t st) {
+  const bool bf16 = a.dtype == ESR_BF16;
+  const bool vec8 = gm.vec8 && bf16 && a.D % 8 == 0 && !(((uintptr_t)a.emb | (uintptr_t)a.emb_shadow) & 15);
+  const RowGeom g = vec8 ? row_geom8(a.D) : row_geom(a.D);
+  for (int i = 0; i < nbatch; ++i) {
+    const GloveBatch b = batch(i);
+    const uint32_t stamp = first_stamp + (uint32_t)i;
+    if (vec8)
+      ESR_DISPATCH_ROW8(g, (launch_glove_step<VEC, NCH, uint16_t>(a, gm, g, b, stamp, ws, st)));
+    else if (bf16)
+      ESR_DISPATCH_ROW(g, (launch_glove_step<VEC, NCH, uint16_t>(a, gm, g, b, stamp, ws, st)));
+    else
+      ESR_DISPATCH_ROW(g, (launch_glove_step<VEC, NCH, float>(a, gm, g, b, stamp, ws, st)));
   }
+  return check_launch(a.who);
+}
 
 extern "C" {
 
@@ -1472,28 +1474,26 @@ int esr_glove_train_step(void* emb, void* emb_shadow, uint8_t* emb_loc, float* e
                          uint32_t* start_flag, uint32_t start_value, float* loss, void* workspace,
                          size_t workspace_bytes, esr_stream_t stream) {
   TraceScope trace_scope_("esr_glove_train_step");
-  ESR_GLOVE_STEP_CHECKS("esr_glove_train_step")
+  const GloveMode gm = glove_mode();
+  const GloveStepArgs a{"esr_glove_train_step", emb, emb_shadow, emb_loc, emb_accum, bias, bias_accum, V, dtype, D, B, mode,
+                        lr, eps, workspace, workspace_bytes};
+  if (int rc = glove_step_checks(a)) return rc;
   ESR_REQUIRE(inputs && target && loss, "esr_glove_train_step: null pointer");
   ESR_REQUIRE(stamp >= 1 && stamp <= kStampMax, "esr_glove_train_step: stamp %u not in [1, %u]", stamp, kStampMax);
   ESR_REQUIRE((presorted_ids == nullptr) == (presorted_perm == nullptr),
               "esr_glove_train_step: presorted_ids and presorted_perm must both be set or both be NULL");
   ESR_REQUIRE(!plan || presorted_ids, "esr_glove_train_step: a plan goes with the sorted ids it was made from");
   ESR_REQUIRE(!plan || !((uintptr_t)plan & 255), "esr_glove_train_step: misaligned plan");
-  hipStream_t st = as_stream(stream);
   StepWs ws;
   step_ws_layout(B, D, (char*)workspace, &ws);
-  const int32_t* sorted_ids = presorted_ids;
-  const int32_t* perm = presorted_perm;
-  if (!sorted_ids) {
+  GloveBatch b{inputs, target, presorted_ids, presorted_perm, plan, long_runs, blocks_per_cu, start_flag, start_value, loss};
+  if (!b.sorted) {
     if (int rc = esr_segment_sort_ids(inputs, 2 * B, V, ws.sorted_ids, ws.perm, ws.sort_ws, ws.sort_ws_bytes, stream))
       return rc;
-    sorted_ids = ws.sorted_ids;
-    perm = ws.perm;
+    b.sorted = ws.sorted_ids;
+    b.perm = ws.perm;
   }
-  const GloveTables t{emb, emb_shadow, emb_loc, emb_accum, bias, bias_accum, D, dtype};
-  launch_glove_step(t, inputs, target, B, mode, lr, eps, stamp, sorted_ids, perm, plan, long_runs, blocks_per_cu,
-                    start_flag, start_value, loss, ws, st);
-  return check_launch("esr_glove_train_step");
+  return run_glove_steps(a, gm, 1, stamp, [&](int) { return b; }, ws, as_stream(stream));
 }
 
 int esr_glove_train_steps(void* emb, void* emb_shadow, uint8_t* emb_loc, float* emb_accum, float* bias,
@@ -1502,7 +1502,10 @@ int esr_glove_train_steps(void* emb, void* emb_shadow, uint8_t* emb_loc, float* 
                           const int32_t* sorted_ids, const int32_t* perm, void* plans, const int32_t* long_runs,
                           float* losses, void* workspace, size_t workspace_bytes, esr_stream_t stream) {
   TraceScope trace_scope_("esr_glove_train_steps");
-  ESR_GLOVE_STEP_CHECKS("esr_glove_train_steps")
+  const GloveMode gm = glove_mode();
+  const GloveStepArgs a{"esr_glove_train_steps", emb, emb_shadow, emb_loc, emb_accum, bias, bias_accum, V, dtype, D, B, mode,
+                        lr, eps, workspace, workspace_bytes};
+  if (int rc = glove_step_checks(a)) return rc;
   ESR_REQUIRE(nbatch >= 1 && nbatch <= kMaxGlovePlanBatch && inputs && targets && sorted_ids && perm && plans && losses &&
                   !((uintptr_t)plans & 255),
               "esr_glove_train_steps: nbatch=%d not in [1, %d], or a null / misaligned pointer", nbatch,
@@ -1510,16 +1513,14 @@ int esr_glove_train_steps(void* emb, void* emb_shadow, uint8_t* emb_loc, float* 
   ESR_REQUIRE(first_stamp >= 1 && first_stamp + (uint32_t)nbatch - 1 <= kStampMax,
               "esr_glove_train_steps: stamps %u .. %u leave [1, %u]", first_stamp, first_stamp + nbatch - 1, kStampMax);
   for (int i = 0; i < nbatch; ++i) ESR_REQUIRE(inputs[i] && targets[i], "esr_glove_train_steps: null list %d", i);
-  hipStream_t st = as_stream(stream);
   StepWs ws;
   step_ws_layout(B, D, (char*)workspace, &ws);
   const size_t stride = esr_glove_plan_bytes(B);
-  const GloveTables t{emb, emb_shadow, emb_loc, emb_accum, bias, bias_accum, D, dtype};
-  for (int b = 0; b < nbatch; ++b)
-    launch_glove_step(t, inputs[b], targets[b], B, mode, lr, eps, first_stamp + (uint32_t)b,
-                      sorted_ids + (int64_t)b * 2 * B, perm + (int64_t)b * 2 * B, (char*)plans + (size_t)b * stride,
-                      long_runs ? long_runs[b] : -1, 0, nullptr, 0u, losses + b, ws, st);
-  return check_launch("esr_glove_train_steps");
+  auto batch = [&](int i) {
+    return GloveBatch{inputs[i], targets[i], sorted_ids + (int64_t)i * 2 * B, perm + (int64_t)i * 2 * B,
+                      (char*)plans + (size_t)i * stride, long_runs ? long_runs[i] : -1, 0, nullptr, 0u, losses + i};
+  };
+  return run_glove_steps(a, gm, nbatch, first_stamp, batch, ws, as_stream(stream));
 }
 
 int esr_rows_consolidate(void* primary, const void* shadow, uint8_t* loc, int64_t V, int dtype, int D,

@@ -958,6 +958,24 @@ int esr_gather_rows_multi(const void* const* tables, const int64_t* row_offsets,
   return check_launch("esr_gather_rows_multi");
 }
 
+// hint[0] = gen when sorted_ids has a run of equal ids longer than `chunk` positions: what a caller needs to know to pass
+// long_runs = 0 (below, and to the one-pass steps) and so leave the long-run launch out
+__global__ __launch_bounds__(kBlock) void long_run_hint_kernel(const int32_t* __restrict__ sorted_ids, int64_t n, int chunk,
+                                                              int* __restrict__ hint, int gen) {
+  bool long_run = false;
+  for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p + chunk < n; p += (int64_t)gridDim.x * kBlock)
+    if (sorted_ids[p] == sorted_ids[p + chunk]) long_run = true;
+  if (__any(long_run) && (threadIdx.x & 63) == 0) hint[0] = gen;
+}
+
+int esr_long_run_hint(const int32_t* sorted_ids, int64_t n, int chunk, int32_t* hint, int32_t gen, esr_stream_t stream) {
+  ESR_REQUIRE(n >= 0 && chunk > 0 && hint && (n == 0 || sorted_ids), "esr_long_run_hint: bad arguments");
+  if (n <= chunk) return ESR_OK;
+  const int grid = (int)std::min<int64_t>(kMaxGrid, cdiv(n, kBlock));
+  hipLaunchKernelGGL(long_run_hint_kernel, dim3(grid), dim3(kBlock), 0, as_stream(stream), sorted_ids, n, chunk, hint, gen);
+  return check_launch("esr_long_run_hint");
+}
+
 int esr_sparse_adagrad_scatter_multi(void* const* tables, float* const* accums, const int64_t* row_offsets,
                                      int ntables, int dtype, int D, const int32_t* sorted_vids, const int32_t* perm,
                                      int64_t n, float* grad_rows, float lr, float eps, int long_runs,
