@@ -233,6 +233,10 @@ SIGNATURES = {
     "esr_itemknn_max_entries": (c_int, []),
     "esr_itemknn_recommend": (c_int, [c_i32p, c_i32p, c_f32p, c_i32p, c_i64, c_int, c_i32p, c_i64, c_vp, c_i64, c_int,
                                       c_int, c_i32p, c_f32p, c_i32p, c_vp]),
+    "esr_eval_max_truth": (c_int, []),
+    "esr_eval_max_width": (c_int, []),
+    "esr_eval_ranking": (c_int, [c_i32p, c_i64, c_int, c_i32p, c_i32p, c_i64, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp,
+                                 c_int, c_int, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_vp, c_vp]),
 }
 
 

@@ -1755,3 +1755,48 @@ def itemknn_recommend(table_ids, table_neighbours, table_scores, table_lengths, 
                                     _p(offsets), nq, int(k), int(bool(exclude_history)), _p(out_ids), _p(out_scores),
                                     _p(out_lengths), _stream()), "esr_itemknn_recommend")
     return out_ids, out_scores, out_lengths
+
+
+# ---------------------------------------------------------------------------------------------
+# ranking metrics of recommended lists against held-out truth sets (esr_eval.hip)
+def eval_max_truth():
+    """Distinct truth ids one query of eval_ranking may hold (its table in LDS)."""
+    return int(_lib.load().esr_eval_max_truth())
+
+
+def eval_max_width():
+    """The widest list eval_ranking scores."""
+    return int(_lib.load().esr_eval_max_width())
+
+
+def eval_ranking(rec_ids, rec_lengths, truth, truth_offsets, max_truth, ks, disc, cum_disc, count_repeats, listed):
+    """esr_eval_ranking: a dict of device tensors -- hits int32[nq, nk], first_hit / valid int32[nq], precision, recall,
+    rr, ap, ndcg float32[nq, nk] (ap and ndcg None with count_repeats) -- and the failure word (reading it syncs).
+    rec_ids int32[nq, width] with unit stride along a row (any row pitch); ks a sequence of ints (host); disc /
+    cum_disc float64 device tensors as include/esr_hip.h describes them."""
+    lib = _lib.load()
+    if not isinstance(rec_ids, torch.Tensor) or not rec_ids.is_cuda:
+        raise TypeError("rec_ids must be a CUDA/ROCm tensor (no CPU fallback exists)")
+    if rec_ids.dtype != torch.int32 or rec_ids.dim() != 2 or (rec_ids.shape[1] > 1 and rec_ids.stride(1) != 1):
+        raise TypeError("rec_ids must be int32 [nq, width] with unit stride along a row")
+    if rec_lengths is not None:
+        _req(rec_lengths, torch.int32, "rec_lengths")
+    _req(truth, torch.int32, "truth"), _req(truth_offsets, torch.int64, "truth_offsets")
+    _req(disc, torch.float64, "disc"), _req(cum_disc, torch.float64, "cum_disc")
+    dev, (nq, width) = rec_ids.device, rec_ids.shape
+    pitch = rec_ids.stride(0) if nq > 1 else width
+    nk = len(ks)
+    ks_host = (ctypes.c_int32 * max(nk, 1))(*[int(k) for k in ks])
+    out = {"hits": torch.empty((nq, nk), dtype=torch.int32, device=dev),
+           "first_hit": torch.empty(nq, dtype=torch.int32, device=dev),
+           "valid": torch.empty(nq, dtype=torch.int32, device=dev)}
+    for name in ("precision", "recall", "rr") + (() if count_repeats else ("ap", "ndcg")):
+        out[name] = torch.empty((nq, nk), dtype=torch.float32, device=dev)
+    out.setdefault("ap", None), out.setdefault("ndcg", None)
+    fail = torch.zeros(1, dtype=torch.int64, device=dev)
+    check(lib.esr_eval_ranking(_p(rec_ids), int(pitch), int(width), _p(rec_lengths), _p(truth), truth.numel(),
+                               _p(truth_offsets), nq, int(max_truth), ctypes.addressof(ks_host), nk, _p(disc), _p(cum_disc),
+                               int(bool(count_repeats)), int(bool(listed)), _p(out["hits"]), _p(out["first_hit"]),
+                               _p(out["valid"]), _p(out["precision"]), _p(out["recall"]), _p(out["rr"]), _p(out["ap"]),
+                               _p(out["ndcg"]), _p(fail), _stream()), "esr_eval_ranking")
+    return out, (int(fail.item()) if nq else 0)

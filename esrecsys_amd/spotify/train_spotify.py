@@ -165,6 +165,21 @@ def eval_batch(state, ys, all_tracks, all_albums, all_artists):
                         _recall(artists, [y["next_artist"] for y in ys], dev)], dim=1)
 
 
+def eval_metrics(state, ys, all_tracks, all_albums, all_artists, ks=(10, 100, 500)):
+    """The ranking metrics (``esrecsys_amd.evaluate.RankingMetrics``: hits, precision, recall, reciprocal rank, average
+    precision and nDCG at every cutoff of `ks`) of the track ids behind all_track_top_k_batch against each playlist's
+    ``next_track`` list, taken as a set.  eval_batch's track recall is the ``count_repeats=True, truth_size="listed"`` form
+    of the same kernel at ks=(500,)."""
+    from ..evaluate import ranking_metrics
+    _, top = all_track_top_k_batch(state, ys, all_albums, all_artists, k=max(int(k) for k in ks))
+    dev = top.device
+    tracks = ops.as_ids(all_tracks, dev).reshape(-1)[top.long()]
+    nexts = [_host_ids(y["next_track"]) for y in ys]
+    offsets = np.zeros(len(nexts) + 1, np.int64)
+    np.cumsum([v.size for v in nexts], out=offsets[1:])
+    return ranking_metrics(tracks, None, np.concatenate(nexts).astype(np.int32), offsets, ks=ks)
+
+
 def eval_steps(state, test_it, eval_steps, all_tracks, all_albums, all_artists, batch=256):
     """The eval of train_spotify.py:270-276: `eval_steps` playlists drawn from `test_it`, their eval_step metrics summed
     in float32 in playlist order and divided by eval_steps -- bit for bit the reference's loop -- scored `batch`

@@ -998,6 +998,38 @@ int esr_itemknn_recommend(const int32_t* table_ids, const int32_t* table_neighbo
                           const int64_t* offsets, int64_t nq, int k, int exclude_history, int32_t* out_ids,
                           float* out_scores, int32_t* out_lengths, esr_stream_t stream);
 
+/* ---- Ranking metrics of recommended lists against held-out truth sets (esr_eval.hip; the reference holds out all but the
+ * first tracks of a playlist, spotify/make_training.py:74-98, and reports the recall of the next tracks among the 500 best,
+ * train_spotify.py:113-131) ----
+ * Query q: the list rec_ids[q * rec_pitch .. + width) (int32, -1 behind a row's end; rec_lengths int32[nq] or NULL = width
+ * everywhere) against the truth ids truth[truth_offsets[q] .. truth_offsets[q + 1]) (int32[n] with int64[nq + 1] offsets, the
+ * CSR layout of the builders).  All of these are device memory; ks is HOST memory -- int32[nk], 1 <= nk <= 8, strictly
+ * ascending, ks[0] >= 1 -- because it is validated before the launch and travels with the kernel's arguments.
+ * With kmax = min(ks[nk - 1], width): position r (0-based) < min(rec_lengths[q], kmax) is a HIT if its id is a truth id and
+ * (count_repeats or no earlier position holds the same id).  c(k) = the hits at positions < k; walking the hits in ascending
+ * 1-based rank r with c = the hits so far: ap_sum += (double)c / r, dcg += disc[r - 1].  n_rel = the DISTINCT truth ids of
+ * the query (listed_size 0) or truth_offsets[q + 1] - truth_offsets[q] (listed_size 1).  Outputs, [nq, nk] unless stated:
+ *   hits int32 = c(k);  first_hit int32[nq] = the 1-based rank of the first hit within kmax, 0 if none;
+ *   precision = c / k;  recall = c / n_rel;  rr = 1 / first_hit if first_hit <= k else 0;
+ *   ap = ap_sum / min(k, n_rel);  ndcg = dcg / cum_disc[min(k, n_rel)];  valid int32[nq] = (n_rel > 0).
+ * Each float is that one fp64 expression rounded once to float; a query with n_rel == 0 gets zeros.  With count_repeats ap
+ * and ndcg are not defined (hits may exceed n_rel): they are not written and may be NULL.
+ * disc double[kmax]: disc[r - 1] = 1 / log2(r + 1); cum_disc double[kideal + 1] = [0, cumsum(disc)] continued to kideal =
+ * min(ks[nk - 1], max_truth) -- the ideal DCG at a cutoff above the width still counts min(k, n_rel) items.  Both are made by
+ * the caller in float64: the device evaluates no logarithm.
+ * max_truth: the caller's bound on truth_offsets[q + 1] - truth_offsets[q]; it sizes the table in LDS.  A query may hold at
+ * most esr_eval_max_truth() DISTINCT truth ids and width is at most esr_eval_max_width(): the caller checks both, nothing
+ * is ever truncated.  fail: a uint64 device word, zeroed by the call; bit 2 = a negative truth id (left out), bit 4 = truth
+ * offsets outside [0, n], falling or a set above max_truth (the query gets zeros), bit 8 = more distinct truth ids than the
+ * table takes.  nq == 0 is a no-op. */
+int esr_eval_max_truth(void);
+int esr_eval_max_width(void);
+int esr_eval_ranking(const int32_t* rec_ids, int64_t rec_pitch, int width, const int32_t* rec_lengths,
+                     const int32_t* truth, int64_t n, const int64_t* truth_offsets, int64_t nq, int max_truth,
+                     const int32_t* ks, int nk, const double* disc, const double* cum_disc, int count_repeats,
+                     int listed_size, int32_t* hits, int32_t* first_hit, int32_t* valid, float* precision, float* recall,
+                     float* rr, float* ap, float* ndcg, unsigned long long* fail, esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
