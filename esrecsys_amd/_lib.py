@@ -237,6 +237,21 @@ SIGNATURES = {
     "esr_eval_max_width": (c_int, []),
     "esr_eval_ranking": (c_int, [c_i32p, c_i64, c_int, c_i32p, c_i32p, c_i64, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp,
                                  c_int, c_int, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_vp, c_vp]),
+    "esr_usersim_tile": (c_int, []),
+    "esr_usersim_table_bytes": (c_size, [c_i64]),
+    "esr_usersim_table_init": (c_int, [c_vp, c_i64, c_vp]),
+    "esr_usersim_rehash": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "esr_usersim_accumulate": (c_int, [c_i32p, c_i32p, c_i64, c_vp, c_i32p, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64,
+                                       c_vp]),
+    "esr_usersim_finalize_workspace_bytes": (c_size, [c_i64]),
+    "esr_usersim_finalize": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_f32, c_i32p, c_i32p, c_f32p, c_i32p, c_vp,
+                                     c_vp, c_size, c_vp]),
+    "esr_userknn_max_entries": (c_int, []),
+    "esr_userknn_predict": (c_int, [c_i32p, c_i32p, c_f32p, c_i32p, c_i64, c_int, c_i32p, c_i64, c_vp, c_i32p, c_f32p, c_i64,
+                                    c_vp, c_i32p, c_i32p, c_i64, c_int, c_int, c_f32p, c_i32p, c_vp]),
+    "esr_userknn_recommend": (c_int, [c_i32p, c_i32p, c_f32p, c_i32p, c_i64, c_int, c_i32p, c_i64, c_vp, c_i32p, c_f32p,
+                                      c_i64, c_vp, c_i32p, c_i64, c_int, c_int, c_int, c_int, c_int, c_i32p, c_f32p, c_i32p,
+                                      c_vp]),
 }
 
 

@@ -1800,3 +1800,99 @@ def eval_ranking(rec_ids, rec_lengths, truth, truth_offsets, max_truth, ks, disc
                                _p(out["valid"]), _p(out["precision"]), _p(out["recall"]), _p(out["rr"]), _p(out["ap"]),
                                _p(out["ndcg"]), _p(fail), _stream()), "esr_eval_ranking")
     return out, (int(fail.item()) if nq else 0)
+
+
+# ---------------------------------------------------------------------------------------------
+# explicit ratings: the wide pair table, Pearson user similarity and the user-kNN affinity (esr_ratings.hip)
+def usersim_tile():
+    """T: the raters per chunk of the accumulate kernel; an item of n >= 2 raters is ceil(n / T) chunks."""
+    return int(_lib.load().esr_usersim_tile())
+
+
+def usersim_table(capacity, device):
+    """A fresh, empty WIDE pair table (four sums per slot) of `capacity` (a power of two >= 2) slots."""
+    lib = _lib.load()
+    table = _ws(_ws_bytes("esr_usersim_table_bytes", int(capacity)), device)
+    check(lib.esr_usersim_table_init(_p(table), int(capacity), _stream()), "esr_usersim_table_init")
+    return table
+
+
+def usersim_rehash(table, capacity, new_capacity):
+    """A wide table of new_capacity slots holding every pair of `table` with its four sums."""
+    lib = _lib.load()
+    new = _ws(_ws_bytes("esr_usersim_table_bytes", int(new_capacity)), table.device)
+    check(lib.esr_usersim_rehash(_p(table), int(capacity), _p(new), int(new_capacity), _stream()), "esr_usersim_rehash")
+    return new
+
+
+def usersim_accumulate(table, capacity, users, dev, item_offsets, item_ids, tile_prefix, item_begin, item_end, ntiles):
+    """Adds the user pairs of the items [item_begin, item_end) of the CSR-by-item ratings (users ascending inside an item)."""
+    lib = _lib.load()
+    _req(users, torch.int32, "users"), _req(dev, torch.int32, "dev"), _req(item_offsets, torch.int64, "item_offsets")
+    _req(item_ids, torch.int32, "item_ids"), _req(tile_prefix, torch.int64, "tile_prefix")
+    check(lib.esr_usersim_accumulate(_p(users), _p(dev), users.numel(), _p(item_offsets), _p(item_ids), _p(tile_prefix),
+                                     item_offsets.numel() - 1, int(item_begin), int(item_end), int(ntiles), _p(table),
+                                     int(capacity), _stream()), "esr_usersim_accumulate")
+
+
+def usersim_finalize(table, capacity, nnz, num_ids, min_overlap, min_similarity):
+    """(index int32[kept], other int32[kept], sim float32[kept], overlap int32[kept], dropped_flat): the kept rows
+    ascending by (index, other).  Reading the two counts syncs."""
+    lib = _lib.load()
+    dev = table.device
+    index = torch.empty(nnz, dtype=torch.int32, device=dev)
+    other = torch.empty(nnz, dtype=torch.int32, device=dev)
+    sim = torch.empty(nnz, dtype=torch.float32, device=dev)
+    overlap = torch.empty(nnz, dtype=torch.int32, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    ws = _ws(int(lib.esr_usersim_finalize_workspace_bytes(int(nnz))), dev)
+    check(lib.esr_usersim_finalize(_p(table), int(capacity), int(nnz), int(num_ids), int(min_overlap),
+                                   int(min_similarity is not None), float(min_similarity or 0.0), _p(index), _p(other),
+                                   _p(sim), _p(overlap), _p(counts), _p(ws), ws.numel(), _stream()), "esr_usersim_finalize")
+    kept, flat = counts.tolist()
+    return index[:kept], other[:kept], sim[:kept], overlap[:kept], flat
+
+
+def userknn_max_entries():
+    """The ratings of all neighbours that one query of userknn_recommend may gather (one workgroup sorts them in LDS)."""
+    return int(_lib.load().esr_userknn_max_entries())
+
+
+def _userknn_args(table_ids, table_neighbours, table_scores, table_lengths, users, row_offsets, items, ratings, mean):
+    _req(table_ids, torch.int32, "table.ids"), _req(table_neighbours, torch.int32, "table.neighbours")
+    _req(table_scores, torch.float32, "table.scores"), _req(table_lengths, torch.int32, "table.lengths")
+    _req(users, torch.int32, "users"), _req(row_offsets, torch.int64, "row_offsets"), _req(items, torch.int32, "items")
+    _req(ratings, torch.float32, "ratings"), _req(mean, torch.float64, "mean")
+    return (_p(table_ids), _p(table_neighbours), _p(table_scores), _p(table_lengths), table_ids.numel(),
+            int(table_neighbours.shape[1]), _p(users), users.numel(), _p(row_offsets), _p(items), _p(ratings), items.numel(),
+            _p(mean))
+
+
+def userknn_predict(table_ids, table_neighbours, table_scores, table_lengths, users, row_offsets, items, ratings, mean,
+                    query_users, query_items, center_neighbour, den_all):
+    """(affinity float32[nq], support int32[nq]) of the (user, item) queries."""
+    lib = _lib.load()
+    args = _userknn_args(table_ids, table_neighbours, table_scores, table_lengths, users, row_offsets, items, ratings, mean)
+    _req(query_users, torch.int32, "query_users"), _req(query_items, torch.int32, "query_items")
+    nq = query_users.numel()
+    aff = torch.empty(nq, dtype=torch.float32, device=users.device)
+    support = torch.empty(nq, dtype=torch.int32, device=users.device)
+    check(lib.esr_userknn_predict(*args, _p(query_users), _p(query_items), nq, int(bool(center_neighbour)),
+                                  int(bool(den_all)), _p(aff), _p(support), _stream()), "esr_userknn_predict")
+    return aff, support
+
+
+def userknn_recommend(table_ids, table_neighbours, table_scores, table_lengths, users, row_offsets, items, ratings, mean,
+                      query_users, k, exclude_rated, min_support, center_neighbour, den_all):
+    """(ids int32[nq, k], scores float32[nq, k], lengths int32[nq]) of the query users."""
+    lib = _lib.load()
+    args = _userknn_args(table_ids, table_neighbours, table_scores, table_lengths, users, row_offsets, items, ratings, mean)
+    _req(query_users, torch.int32, "query_users")
+    dev, nq = users.device, query_users.numel()
+    out_ids = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    out_scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    out_lengths = torch.empty(nq, dtype=torch.int32, device=dev)
+    check(lib.esr_userknn_recommend(*args, _p(query_users), nq, int(k), int(bool(exclude_rated)), int(min_support),
+                                    int(bool(center_neighbour)), int(bool(den_all)), _p(out_ids), _p(out_scores),
+                                    _p(out_lengths), _stream()), "esr_userknn_recommend")
+    return out_ids, out_scores, out_lengths

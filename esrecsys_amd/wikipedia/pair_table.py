@@ -38,15 +38,19 @@ class PairTable:
     factor is at most 1/2.  Growing re-inserts the occupied slots into a new table (esr_cooccur_rehash).
 
     A failure word raised by the device becomes a ``CooccurrenceError`` that starts with `what` and spells the bits with
-    `failures`; from then on every call raises."""
+    `failures`; from then on every call raises.
 
-    def __init__(self, capacity, device, failures=FAILURES, what="co-occurrence table", tensor=None):
+    `table_ops` = (make(capacity, device), rehash(tensor, capacity, new_capacity)) of a table with another slot layout
+    behind the same 256-byte header (the wide table of ``ratings``); the default is the narrow table's."""
+
+    def __init__(self, capacity, device, failures=FAILURES, what="co-occurrence table", tensor=None, table_ops=None):
         self.capacity = pow2_at_least(int(capacity))
         self.device, self.failures, self.what = device, failures, what
         self.tensor = tensor        # given: a table that a kernel filled whole (the dictionary lookup)
         self.used = 0
         self.rehashes = 0
         self.failed = None
+        self._make, self._rehash = table_ops if table_ops is not None else (ops.cooccur_table, ops.cooccur_rehash)
 
     def check_usable(self):
         if self.failed is not None:
@@ -56,9 +60,9 @@ class PairTable:
         self.check_usable()
         if self.tensor is None:
             self.capacity = max(self.capacity, capacity)
-            self.tensor = ops.cooccur_table(self.capacity, self.device)
+            self.tensor = self._make(self.capacity, self.device)
         elif capacity > self.capacity:
-            self.tensor = ops.cooccur_rehash(self.tensor, self.capacity, capacity)
+            self.tensor = self._rehash(self.tensor, self.capacity, capacity)
             self.capacity = capacity
             self.rehashes += 1
 

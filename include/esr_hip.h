@@ -1030,6 +1030,72 @@ int esr_eval_ranking(const int32_t* rec_ids, int64_t rec_pitch, int width, const
                      int listed_size, int32_t* hits, int32_t* first_hit, int32_t* valid, float* precision, float* recall,
                      float* rr, float* ap, float* ndcg, unsigned long long* fail, esr_stream_t stream);
 
+/* ---- Explicit ratings: Pearson user similarity and the user-kNN affinity (esr_ratings.hip; the collaborative-filtering job
+ * of the reference's book, chapter 5 "Data Processing": USim from the deviations of the co-rated items, Aff over the nearest
+ * users) ----
+ * The WIDE pair table: esr_usersim_table_bytes(capacity) bytes, 16-byte aligned, capacity a power of two >= 2 -- the
+ * 256-byte header of the esr_cooccur_* table (word 0: occupied slots, word 1: failure bits), keys uint64[capacity]
+ * (index << 32 | other, all ones = empty), then FOUR planes sums uint64[4][capacity]: n, P, Qa, Qb.  A slot is claimed once
+ * by a compare-and-swap on its key; the four sums are integer atomic adds, so nothing depends on their order.  Failure bits
+ * as there, and 128: the users of an item are not strictly ascending (a (user, item) given twice).
+ *   accumulate  ratings as CSR by item: item r of [item_begin, item_end) has the raters users[item_offsets[r] ..
+ *               item_offsets[r + 1]) (int32 >= 0, strictly ascending) with the fixed-point deviations dev (int32) and the id
+ *               item_ids[r] (only screened: a negative one raises bit 2).  Every p < q of an item adds n += 1, P += dev_p
+ *               dev_q (two's complement), Qa += dev_p^2, Qb += dev_q^2 to the key users[p] << 32 | users[q].  The work unit is
+ *               a T x T tile of an item's triangle, T = esr_usersim_tile(): with C = ceil(n / T) an item of n >= 2 raters
+ *               has C (C + 1) / 2 tiles, an item below two raters none; tile_prefix int64[nitems + 1] is the exclusive
+ *               prefix of those counts over ALL items (made by the caller, device memory) and ntiles =
+ *               tile_prefix[item_end] - tile_prefix[item_begin] (a prefix that disagrees raises bit 4 and adds nothing).
+ *               The caller keeps capacity >= occupied + sum over the range of n (n - 1) / 2, and m^2 * (items in all
+ *               calls) < 2^53 with m = the largest |dev|, so that every sum is exact in a double.
+ *   rehash      new_table (initialised here) receives every occupied slot with its four sums, and the failure word.
+ *   finalize    nnz = the header's occupied count, num_ids > every user id.  Per entry sim = float(double(P) /
+ *               (sqrt(double(Qa)) * sqrt(double(Qb)))), each fp64 operation rounded once; entries with Qa == 0 or Qb == 0
+ *               (counted in counts[1]), with n < min_overlap, or -- has_min_similarity -- with sim <= min_similarity are
+ *               dropped.  The kept rows go to index / other / sim / overlap [nnz] ascending by (index, other), index <
+ *               other; counts int64[2] (device) = {rows kept, entries dropped as flat}.
+ *               workspace: esr_usersim_finalize_workspace_bytes(nnz) bytes, 16-byte aligned.
+ * User-kNN over a neighbour table made by esr_neighbours_topk from (index, other, sim) with score 0 (table_ids, width = its
+ * k) and the ratings as CSR by user: users int32[nu] ascending, row_offsets int64[nu + 1] over items int32[R] (ascending and
+ * distinct inside a row) and ratings float[R]; mean double[nu] the users' mean ratings.  For the query user A with table row
+ * (U_j, s_j), j < length, the columns COUNTED for item i are those whose U_j rated i, taken in ascending j:
+ *   num = sum s_j (double(r[U_j, i]) - c_j), c_j = mean[A] (center 0) or mean[U_j] (center 1);
+ *   den = sum |s_j| over the counted columns (denominator 0) or sum s_j over the whole row (denominator 1);
+ *   affinity = float(mean[A] + num / den), or float(mean[A]) when no column counts or den == 0; -0 is written as +0.
+ * All of it fp64, each operation rounded once.  support = the number of counted columns.
+ *   predict     (query_users[q], query_items[q]) -> out_affinity float[nq], out_support int32[nq]; a user that table_ids or
+ *               users lacks gets (NaN, 0).
+ *   recommend   per query user the k best items among those its neighbours rated -- without the user's own with
+ *               exclude_rated, without those of support < min_support -- by (affinity descending, item ascending): out_ids
+ *               int32[nq, k] (-1 padded), out_scores float[nq, k] (0 padded), out_lengths int32[nq].  The affinity is
+ *               predict's bit for bit.  A query gathers the sum of its neighbours' row lengths, at most
+ *               esr_userknn_max_entries() (one workgroup sorts them in LDS): the caller checks that; the kernel answers
+ *               such a query with length -1, never truncated.  A user the table lacks gets length 0. */
+int esr_usersim_tile(void);
+size_t esr_usersim_table_bytes(int64_t capacity);
+int esr_usersim_table_init(void* table, int64_t capacity, esr_stream_t stream);
+int esr_usersim_rehash(const void* table, int64_t capacity, void* new_table, int64_t new_capacity, esr_stream_t stream);
+int esr_usersim_accumulate(const int32_t* users, const int32_t* dev, int64_t N, const int64_t* item_offsets,
+                           const int32_t* item_ids, const int64_t* tile_prefix, int64_t nitems, int64_t item_begin,
+                           int64_t item_end, int64_t ntiles, void* table, int64_t capacity, esr_stream_t stream);
+size_t esr_usersim_finalize_workspace_bytes(int64_t nnz);
+int esr_usersim_finalize(void* table, int64_t capacity, int64_t nnz, int64_t num_ids, int min_overlap,
+                         int has_min_similarity, float min_similarity, int32_t* index, int32_t* other, float* sim,
+                         int32_t* overlap, int64_t* counts, void* workspace, size_t workspace_bytes,
+                         esr_stream_t stream);
+int esr_userknn_max_entries(void);
+int esr_userknn_predict(const int32_t* table_ids, const int32_t* table_neighbours, const float* table_scores,
+                        const int32_t* table_lengths, int64_t u, int width, const int32_t* users, int64_t nu,
+                        const int64_t* row_offsets, const int32_t* items, const float* ratings, int64_t R,
+                        const double* mean, const int32_t* query_users, const int32_t* query_items, int64_t nq,
+                        int center, int denominator, float* out_affinity, int32_t* out_support, esr_stream_t stream);
+int esr_userknn_recommend(const int32_t* table_ids, const int32_t* table_neighbours, const float* table_scores,
+                          const int32_t* table_lengths, int64_t u, int width, const int32_t* users, int64_t nu,
+                          const int64_t* row_offsets, const int32_t* items, const float* ratings, int64_t R,
+                          const double* mean, const int32_t* query_users, int64_t nq, int k, int exclude_rated,
+                          int min_support, int center, int denominator, int32_t* out_ids, float* out_scores,
+                          int32_t* out_lengths, esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
