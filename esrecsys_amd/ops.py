@@ -1896,3 +1896,68 @@ def userknn_recommend(table_ids, table_neighbours, table_scores, table_lengths, 
                                     int(bool(center_neighbour)), int(bool(den_all)), _p(out_ids), _p(out_scores),
                                     _p(out_lengths), _stream()), "esr_userknn_recommend")
     return out_ids, out_scores, out_lengths
+
+
+# ---------------------------------------------------------------------------------------------
+# matrix factorisation of explicit ratings by alternating least squares (esr_als.hip)
+def als_max_rank():
+    """The largest rank esr_als_solve_rows and esr_als_predict take."""
+    return int(_lib.load().esr_als_max_rank())
+
+
+def als_geometry():
+    """(chunk, chunks_per_workgroup): a row's ratings are cut into chunks of `chunk` consecutive ratings; a wave solves a
+    row of up to one chunk, a workgroup one of up to chunks_per_workgroup chunks, longer rows go through workspace partials."""
+    chunk, per_wg = ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.load().esr_als_geometry(ctypes.byref(chunk), ctypes.byref(per_wg)), "esr_als_geometry")
+    return int(chunk.value), int(per_wg.value)
+
+
+def als_solve_rows(other_factors, row_offsets, cols, targets, row_begin, row_end, reg, weighted, out_factors, failed):
+    """One half-sweep over the rows [row_begin, row_end): out_factors[r] = the regularised least-squares solution of row r's
+    ratings against other_factors.  row_offsets is a HOST array (numpy int64[n_rows + 1]): the library sorts the rows into
+    its three classes from it.  `failed` (int32[1], device) collects the failure word; the caller zeroes and reads it."""
+    lib = _lib.load()
+    _req(other_factors, torch.float32, "other_factors"), _req(out_factors, torch.float32, "out_factors")
+    _req(cols, torch.int32, "cols"), _req(targets, torch.float32, "targets"), _req(failed, torch.int32, "failed")
+    if not isinstance(row_offsets, np.ndarray) or row_offsets.dtype != np.int64 or not row_offsets.flags.c_contiguous:
+        raise TypeError("row_offsets must be a contiguous numpy int64 array (host memory)")
+    row_begin, row_end = int(row_begin), int(row_end)
+    if not 0 <= row_begin <= row_end < row_offsets.size:
+        raise ValueError("rows [%d, %d) not inside the %d rows of row_offsets" % (row_begin, row_end, row_offsets.size - 1))
+    if out_factors.shape[0] < row_end or out_factors.shape[1] != other_factors.shape[1]:
+        raise ValueError("out_factors %s does not hold rows up to %d of rank %d"
+                         % (tuple(out_factors.shape), row_end, other_factors.shape[1]))
+    if int(row_offsets[row_end]) > cols.numel() or cols.numel() != targets.numel():
+        raise ValueError("row_offsets end at %d but there are %d cols and %d targets"
+                         % (int(row_offsets[row_end]), cols.numel(), targets.numel()))
+    n_other, rank = other_factors.shape
+    nnz = int(row_offsets[row_end] - row_offsets[row_begin])
+    ws = _ws(int(lib.esr_als_solve_workspace_bytes(row_end - row_begin, nnz, int(rank))), out_factors.device)
+    check(lib.esr_als_solve_rows(_p(other_factors), int(n_other), int(rank), row_offsets.ctypes.data, _p(cols), _p(targets),
+                                 row_begin, row_end, float(reg), int(bool(weighted)), _p(out_factors), _p(failed), _p(ws),
+                                 ws.numel(), _stream()), "esr_als_solve_rows")
+
+
+def als_predict(user_factors, item_factors, user_pos, item_pos, offset=None, targets=None):
+    """float32[nq]: float32(offset[u] + x_u . y_i) with the dot product summed in fp64 in ascending dimension (NaN where a
+    position is outside its table); with `targets` the residual float32(float64(targets) - that)."""
+    lib = _lib.load()
+    _req(user_factors, torch.float32, "user_factors"), _req(item_factors, torch.float32, "item_factors")
+    _req(user_pos, torch.int32, "user_pos"), _req(item_pos, torch.int32, "item_pos")
+    if offset is not None:
+        _req(offset, torch.float64, "offset")
+        if offset.numel() != user_factors.shape[0]:
+            raise ValueError("offset must have one entry per user row")
+    if targets is not None:
+        _req(targets, torch.float32, "targets")
+    nq = user_pos.numel()
+    if item_pos.numel() != nq or (targets is not None and targets.numel() != nq):
+        raise ValueError("user_pos, item_pos (and targets) must have one length")
+    if user_factors.shape[1] != item_factors.shape[1]:
+        raise ValueError("user_factors and item_factors differ in rank")
+    out = torch.empty(nq, dtype=torch.float32, device=user_factors.device)
+    check(lib.esr_als_predict(_p(user_factors), user_factors.shape[0], _p(item_factors), item_factors.shape[0],
+                              int(user_factors.shape[1]), _p(user_pos), _p(item_pos), _p(offset), _p(targets), nq, _p(out),
+                              _stream()), "esr_als_predict")
+    return out

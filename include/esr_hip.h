@@ -1096,6 +1096,39 @@ int esr_userknn_recommend(const int32_t* table_ids, const int32_t* table_neighbo
                           int min_support, int center, int denominator, int32_t* out_ids, float* out_scores,
                           int32_t* out_lengths, esr_stream_t stream);
 
+/* ---- Matrix factorisation of explicit ratings by alternating least squares (esr_als.hip) ----
+ * The model is r[u, i] ~ c[u] + x_u . y_i over factor tables float[n, rank], rank in [1, the max-rank query] (64).
+ *   geometry    chunk (even, >= 2): the ratings of a row are taken in CSR order and cut into chunks of that many;
+ *               chunks_per_workgroup: rows up to one chunk are solved by a wave, rows up to chunk * chunks_per_workgroup by
+ *               a workgroup, longer rows through partials in the workspace and a second launch.
+ *   solve_rows  one half-sweep over the rows [row_begin, row_end) of one side.  row_offsets int64[row_end + 1] is HOST
+ *               memory (ascending, >= 0): the call sorts the rows into the three classes from it; cols int32 (positions into
+ *               other_factors float[n_other, rank]) and targets float are device memory of row_offsets[row_end] entries.
+ *               Row r with n ratings (c_k, d_k) gets the solution of
+ *                   (sum_k y_k y_k^T + lam I) x = sum_k d_k y_k,  y_k = other_factors[c_k],  lam = reg * (weighted ? n : 1)
+ *               in out_factors[r], a row without ratings the zero vector.  Order: per chunk the Gram entries are the
+ *               k-ordered f32 fmaf chain from 0 of v_mfma_f32_32x32x2_f32, the right-hand side is the chain over the even
+ *               ratings plus the chain over the odd ones; chunk partials are added in ascending chunk order in f32; then lam
+ *               on the diagonal, an f32 Cholesky and two triangular solves.  The output row depends on its own ratings,
+ *               other_factors, reg and weighted only -- not on the row range, the grid or the other rows.  No floating-point
+ *               atomics.  failed (int32 word, device, zeroed by the caller): bit 30 is set by a column outside [0, n_other)
+ *               (never dereferenced; its rating counts as absent), and 1 is added per row whose pivot is not finite and
+ *               positive or whose solution is not finite -- that output row stays as it was.  out_factors must not overlap
+ *               other_factors.  workspace: the workspace-bytes query of (row_end - row_begin, the ratings of the range,
+ *               rank), 16-byte aligned; the call waits for the stream once (its row lists are copied from host memory).
+ *   predict     out[q] = float(offset[u] + sum_d double(x_u[d]) * double(y_i[d])), the sum in fp64 in ascending d from 0,
+ *               u = user_pos[q], i = item_pos[q] (positions; NaN where either is outside its table); offset double[nu] or
+ *               null (0).  With targets float[nq] (residual mode): out[q] = float(double(targets[q]) - that value). */
+int esr_als_max_rank(void);
+int esr_als_geometry(int* chunk, int* chunks_per_workgroup);
+size_t esr_als_solve_workspace_bytes(int64_t n_rows, int64_t nnz, int rank);
+int esr_als_solve_rows(const float* other_factors, int64_t n_other, int rank, const int64_t* row_offsets, const int32_t* cols,
+                       const float* targets, int64_t row_begin, int64_t row_end, float reg, int weighted, float* out_factors,
+                       int32_t* failed, void* workspace, size_t workspace_bytes, esr_stream_t stream);
+int esr_als_predict(const float* user_factors, int64_t nu, const float* item_factors, int64_t ni, int rank,
+                    const int32_t* user_pos, const int32_t* item_pos, const double* offset, const float* targets, int64_t nq,
+                    float* out, esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
