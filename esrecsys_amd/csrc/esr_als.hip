@@ -22,6 +22,24 @@
 //   failures    a column outside [0, n_other) is never dereferenced: its rating counts as absent and bit 30 of *failed is
 //               set; a pivot that is not finite and positive (or a solution that is not finite) leaves the output row as it
 //               was and adds 1 to *failed.
+//
+// Implicit feedback (Hu, Koren, Volinsky 2008): esr_als_gram and esr_als_solve_rows_implicit.  Every cell of the matrix is
+// fitted, preference 1 on a row's entries and 0 elsewhere, confidence 1 + w_k on the entries (w_k: a float per entry) and 1
+// elsewhere, so a row solves
+//     (G + sum_k w_k y_k y_k^T + lam I) x = sum_k c_k y_k,     G = Y^T Y,   c_k = fl32(1 + w_k),   lam = reg * (weighted ? n : 1).
+//   whole gram  esr_als_gram: the table is cut into segments of kAlsGramSegment consecutive rows; ONE wave owns a segment and
+//               accumulates its lower block triangle as one k-ordered f32 fmaf chain from 0 on the same MFMA scheme (both
+//               operands the same register, rows gathered straight into VGPRs, lanes at or above rank and an odd tail supply
+//               0) and writes it to the workspace; a second launch adds the segment partials per entry in fp64 in ascending
+//               segment order, rounds once to f32 and writes the entry and its mirror.  G is a function of the table alone:
+//               not of the grid, and a trailing all-zero row adds fma(0, 0, acc) = acc or a partial of zeros.
+//   order       (1) a row's entries in CSR order, cut into chunks of kAlsChunk as above; (2) within a chunk the lower-triangle
+//               entry (i, j), i >= j, is the k-ordered chain acc = fmaf(fl32(w_k * y_k[i]), y_k[j], acc) from 0 -- one VALU
+//               multiply per MFMA step scales the A operand, which indexes the row; (3) the right-hand side is
+//               fmaf(c_k, y_k[d], acc) over the chunk's even entries plus the same chain over its odd ones; (4) chunk partials
+//               are added in ascending order in f32; (5) then G[i][j] is added; (6) then lam on the diagonal; (7) then the
+//               Cholesky and the two solves above.  The same three row classes, the same workspace layout.
+//   failures    as above, and a weight that is negative or not finite counts as absent and sets bit 29 of *failed.
 // No kernel waits on another workgroup; every loop is bounded by a length the host wrote into the unit lists.
 #include <math.h>
 
@@ -39,6 +57,8 @@ constexpr int kAlsWaves = kBlock / kWave;
 constexpr int kAlsChunksPerWg = kAlsWaves;      // one chunk per wave of the workgroup
 constexpr int kAlsFinishBlock = 1024;           // the long rows' second launch: more threads, fewer partial loads each
 constexpr int kAlsFailBadPosition = 1 << 30;
+constexpr int kAlsFailBadWeight = 1 << 29;      // (implicit) a weight that is negative or not finite
+constexpr int kAlsGramSegment = 512;            // table rows per segment of esr_als_gram (even), one wave each
 constexpr int64_t kAlsMaxRows = (int64_t)1 << 30;
 
 struct AlsUnit {       // a row of class 1 or 2
@@ -63,6 +83,7 @@ struct AlsIn {
   int weighted;
   float* out;
   int32_t* failed;
+  const float* gram;   // (implicit) Y^T Y [rank, rank]; `targets` holds the weights w_k
 };
 template <bool HI>
 struct AlsAcc {
@@ -82,7 +103,8 @@ __device__ __forceinline__ void als_wave_sync() {
 }
 
 // the partial of the ratings [begin, begin + len) (len >= 1, at most kAlsChunk), from zero
-template <bool HI>
+// IMP: targets are the weights w_k -- the A operand (the row index) is fl32(w_k * y_k), the right-hand side takes fl32(1 + w_k)
+template <bool HI, bool IMP>
 __device__ __forceinline__ void als_chunk(const AlsIn& in, int64_t begin, int len, AlsAcc<HI>& a, int lane) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) a.ll[r] = 0.f, a.hl[r] = 0.f, a.hh[r] = 0.f;
@@ -90,7 +112,7 @@ __device__ __forceinline__ void als_chunk(const AlsIn& in, int64_t begin, int le
   const int dim = lane & 31, half = lane >> 5;
   const bool lo_live = dim < in.rank, hi_live = HI && dim + 32 < in.rank;
   const int dlo = lo_live ? dim : 0, dhi = hi_live ? dim + 32 : 0;   // a dead lane reads element 0 and drops it
-  bool bad = false;
+  bool bad = false, bad_weight = false;
   for (int b0 = 0; b0 < len; b0 += kWave) {
     const int k = b0 + lane;
     int32_t c = -1;
@@ -98,7 +120,9 @@ __device__ __forceinline__ void als_chunk(const AlsIn& in, int64_t begin, int le
     if (k < len) {
       c = in.cols[begin + k];
       d = in.targets[begin + k];
-      if (c < 0 || (int64_t)c >= in.n_other) bad = true, c = -1, d = 0.f;
+      const bool off = c < 0 || (int64_t)c >= in.n_other;
+      if (IMP && (!(d >= 0.f) || !(d < INFINITY))) bad_weight = true, c = -1, d = 0.f;
+      if (off) bad = true, c = -1, d = 0.f;
     }
     const int left = len - b0;
     const int steps = ((left < kWave ? left : kWave) + 1) >> 1;
@@ -113,25 +137,27 @@ __device__ __forceinline__ void als_chunk(const AlsIn& in, int64_t begin, int le
       const float* y = in.other + (int64_t)(cs < 0 ? 0 : cs) * in.rank;   // (row 0 exists: n_other >= 1 where a rating does)
       const float vlo = y[dlo];
       const float ylo = (cs >= 0 && lo_live) ? vlo : 0.f;
-      a.ll = __builtin_amdgcn_mfma_f32_32x32x2f32(ylo, ylo, a.ll, 0, 0, 0);
-      a.rlo = fmaf(ds, ylo, a.rlo);
+      const float rs = IMP ? __fadd_rn(1.f, ds) : ds;
+      a.ll = __builtin_amdgcn_mfma_f32_32x32x2f32(IMP ? __fmul_rn(ds, ylo) : ylo, ylo, a.ll, 0, 0, 0);
+      a.rlo = fmaf(rs, ylo, a.rlo);
       if (HI) {
         const float vhi = y[dhi];
         const float yhi = (cs >= 0 && hi_live) ? vhi : 0.f;
-        a.hl = __builtin_amdgcn_mfma_f32_32x32x2f32(yhi, ylo, a.hl, 0, 0, 0);
-        a.hh = __builtin_amdgcn_mfma_f32_32x32x2f32(yhi, yhi, a.hh, 0, 0, 0);
-        a.rhi = fmaf(ds, yhi, a.rhi);
+        const float ahi = IMP ? __fmul_rn(ds, yhi) : yhi;
+        a.hl = __builtin_amdgcn_mfma_f32_32x32x2f32(ahi, ylo, a.hl, 0, 0, 0);
+        a.hh = __builtin_amdgcn_mfma_f32_32x32x2f32(ahi, yhi, a.hh, 0, 0, 0);
+        a.rhi = fmaf(rs, yhi, a.rhi);
       }
     }
   }
   if (__any(bad) && lane == 0) atomicOr(in.failed, kAlsFailBadPosition);
+  if (IMP && __any(bad_weight) && lane == 0) atomicOr(in.failed, kAlsFailBadWeight);
 }
 
 // the partial as a matrix [rank][S] (lower block triangle: rows >= 32 x columns < 32 included, the transposed block not)
 // and a right-hand side [rank]
 template <bool HI>
-__device__ __forceinline__ void als_store_partial(const AlsAcc<HI>& a, float* __restrict__ A, int S, float* __restrict__ rhs,
-                                                  int n, int lane) {
+__device__ __forceinline__ void als_store_matrix(const AlsAcc<HI>& a, float* __restrict__ A, int S, int n, int lane) {
   const int col = lane & 31, half = lane >> 5;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -142,6 +168,13 @@ __device__ __forceinline__ void als_store_partial(const AlsAcc<HI>& a, float* __
       if (row + 32 < n && col + 32 < n) A[(row + 32) * S + col + 32] = a.hh[r];
     }
   }
+}
+
+template <bool HI>
+__device__ __forceinline__ void als_store_partial(const AlsAcc<HI>& a, float* __restrict__ A, int S, float* __restrict__ rhs,
+                                                  int n, int lane) {
+  const int col = lane & 31, half = lane >> 5;
+  als_store_matrix<HI>(a, A, S, n, lane);
   const float lo = a.rlo + __shfl_xor(a.rlo, 32, kWave);   // even ratings + odd ratings (the same bits in both halves)
   if (half == 0 && col < n) rhs[col] = lo;
   if (HI) {
@@ -157,11 +190,20 @@ __device__ __forceinline__ bool als_cell_written(int row, int col, int n) {
   return row >= n || (col < n && !(row < 32 && col >= 32));
 }
 
-// ONE wave: lam on the diagonal, Cholesky, both solves; writes the row or counts the failure
+// ONE wave: (IMP: G on the lower triangle, then) lam on the diagonal, Cholesky, both solves; writes the row or counts the
+// failure
+template <bool IMP>
 __device__ __forceinline__ void als_finish_row(const AlsIn& in, float* __restrict__ A, const float* __restrict__ rhs, int n,
                                                int S, int len, float* __restrict__ out, int lane) {
   const float lam = in.weighted ? in.reg * (float)len : in.reg;
   const bool live = lane < n;
+  if (IMP) {   // the Cholesky reads the lower triangle only
+    for (int e = lane; e < n * n; e += kWave) {
+      const int row = e / n, col = e - row * n;
+      if (col <= row) A[row * S + col] = A[row * S + col] + in.gram[e];
+    }
+    als_wave_sync();
+  }
   if (live) A[lane * S + lane] = A[lane * S + lane] + lam;
   als_wave_sync();
   bool ok = true;
@@ -203,7 +245,7 @@ __device__ __forceinline__ void als_finish_row(const AlsIn& in, float* __restric
 }
 
 // ---- class 1: a wave per row ----------------------------------------------------------------------------------------------
-template <bool HI>
+template <bool HI, bool IMP>
 __global__ __launch_bounds__(kBlock) void als_wave_rows_kernel(AlsIn in, const AlsUnit* __restrict__ units, int64_t n_units) {
   extern __shared__ __attribute__((aligned(16))) float als_lds[];
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
@@ -218,16 +260,16 @@ __global__ __launch_bounds__(kBlock) void als_wave_rows_kernel(AlsIn in, const A
       continue;
     }
     AlsAcc<HI> a;
-    als_chunk<HI>(in, un.begin, un.len < kAlsChunk ? un.len : kAlsChunk, a, lane);
+    als_chunk<HI, IMP>(in, un.begin, un.len < kAlsChunk ? un.len : kAlsChunk, a, lane);
     als_wave_sync();
     als_store_partial<HI>(a, A, S, rhs, n, lane);
     als_wave_sync();
-    als_finish_row(in, A, rhs, n, S, un.len, out, lane);
+    als_finish_row<IMP>(in, A, rhs, n, S, un.len, out, lane);
   }
 }
 
 // ---- class 2: a workgroup per row, a chunk per wave -------------------------------------------------------------------------
-template <bool HI>
+template <bool HI, bool IMP>
 __global__ __launch_bounds__(kBlock) void als_group_rows_kernel(AlsIn in, const AlsUnit* __restrict__ units, int64_t n_units) {
   extern __shared__ __attribute__((aligned(16))) float als_lds[];
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
@@ -240,7 +282,7 @@ __global__ __launch_bounds__(kBlock) void als_group_rows_kernel(AlsIn in, const 
     if (w < nch) {
       const int off = w * kAlsChunk, left = un.len - off;
       AlsAcc<HI> a;
-      als_chunk<HI>(in, un.begin + off, left < kAlsChunk ? left : kAlsChunk, a, lane);
+      als_chunk<HI, IMP>(in, un.begin + off, left < kAlsChunk ? left : kAlsChunk, a, lane);
       als_store_partial<HI>(a, als_lds + w * slot, S, als_lds + w * slot + n * S, n, lane);
     }
     __syncthreads();
@@ -251,12 +293,12 @@ __global__ __launch_bounds__(kBlock) void als_group_rows_kernel(AlsIn in, const 
       als_lds[e] = s;
     }
     __syncthreads();
-    if (w == 0) als_finish_row(in, als_lds, als_lds + n * S, n, S, un.len, in.out + (int64_t)un.row * n, lane);
+    if (w == 0) als_finish_row<IMP>(in, als_lds, als_lds + n * S, n, S, un.len, in.out + (int64_t)un.row * n, lane);
   }
 }
 
 // ---- class 3: a wave per chunk into the workspace, then a workgroup per row ---------------------------------------------------
-template <bool HI>
+template <bool HI, bool IMP>
 __global__ __launch_bounds__(kBlock) void als_chunk_partials_kernel(AlsIn in, const AlsChunkUnit* __restrict__ units,
                                                                     int64_t n_units, float* __restrict__ partials) {
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
@@ -265,12 +307,13 @@ __global__ __launch_bounds__(kBlock) void als_chunk_partials_kernel(AlsIn in, co
     const AlsChunkUnit un = units[u];
     if (un.len <= 0) continue;
     AlsAcc<HI> a;
-    als_chunk<HI>(in, un.begin, un.len < kAlsChunk ? un.len : kAlsChunk, a, lane);
+    als_chunk<HI, IMP>(in, un.begin, un.len < kAlsChunk ? un.len : kAlsChunk, a, lane);
     float* dst = partials + un.slot * P;
     als_store_partial<HI>(a, dst, n, dst + n * n, n, lane);
   }
 }
 
+template <bool IMP>
 __global__ __launch_bounds__(kAlsFinishBlock) void als_long_rows_kernel(AlsIn in, const AlsLongRow* __restrict__ rows,
                                                                         int64_t n_rows, const float* __restrict__ partials) {
   extern __shared__ __attribute__((aligned(16))) float als_lds[];
@@ -294,7 +337,67 @@ __global__ __launch_bounds__(kAlsFinishBlock) void als_long_rows_kernel(AlsIn in
       else als_lds[n * S + (e - n * n)] = s;
     }
     __syncthreads();
-    if (w == 0) als_finish_row(in, als_lds, als_lds + n * S, n, S, un.len, in.out + (int64_t)un.row * n, lane);
+    if (w == 0) als_finish_row<IMP>(in, als_lds, als_lds + n * S, n, S, un.len, in.out + (int64_t)un.row * n, lane);
+  }
+}
+
+// ---- the whole table's Gram matrix: a wave per segment into the workspace, then an fp64 sum per entry ------------------------------
+template <bool HI>
+__global__ __launch_bounds__(kBlock) void als_gram_segments_kernel(const float* __restrict__ table, int64_t n, int rank,
+                                                                   int64_t n_seg, float* __restrict__ partials) {
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+  const int dim = lane & 31, half = lane >> 5;
+  const bool lo_live = dim < rank, hi_live = HI && dim + 32 < rank;
+  const int dlo = lo_live ? dim : 0, dhi = hi_live ? dim + 32 : 0;   // a dead lane reads element 0 and drops it
+  for (int64_t s = (int64_t)blockIdx.x * kAlsWaves + w; s < n_seg; s += (int64_t)gridDim.x * kAlsWaves) {
+    const int64_t r0 = s * kAlsGramSegment;   // (< n: n_seg = ceil(n / kAlsGramSegment))
+    const int64_t left = n - r0;
+    const int len = (int)(left < kAlsGramSegment ? left : kAlsGramSegment);
+    AlsAcc<HI> a;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a.ll[r] = 0.f, a.hl[r] = 0.f, a.hh[r] = 0.f;
+    const int steps = (len + 1) >> 1;
+    // eight steps at a time, as als_chunk; a row at or above len is read as row r0 and dropped: fma(0, 0, acc) = acc
+    for (int s0 = 0; s0 < steps; s0 += 8)
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const int k = 2 * (s0 + t) + half;
+      const bool in_seg = k < len;
+      const float* y = table + (r0 + (in_seg ? k : 0)) * rank;
+      const float vlo = y[dlo];
+      const float ylo = (in_seg && lo_live) ? vlo : 0.f;
+      a.ll = __builtin_amdgcn_mfma_f32_32x32x2f32(ylo, ylo, a.ll, 0, 0, 0);
+      if (HI) {
+        const float vhi = y[dhi];
+        const float yhi = (in_seg && hi_live) ? vhi : 0.f;
+        a.hl = __builtin_amdgcn_mfma_f32_32x32x2f32(yhi, ylo, a.hl, 0, 0, 0);
+        a.hh = __builtin_amdgcn_mfma_f32_32x32x2f32(yhi, yhi, a.hh, 0, 0, 0);
+      }
+    }
+    als_store_matrix<HI>(a, partials + s * rank * rank, rank, rank, lane);
+  }
+}
+
+// entry (i, j), i >= j: the segment partials in ascending order in fp64, rounded once; the mirror gets the same bits
+__global__ __launch_bounds__(kBlock) void als_gram_sum_kernel(const float* __restrict__ partials, int64_t n_seg, int rank,
+                                                              float* __restrict__ out) {
+  const int P = rank * rank;
+  for (int e = blockIdx.x * kBlock + threadIdx.x; e < P; e += gridDim.x * kBlock) {
+    const int i = e / rank, j = e - i * rank;
+    if (j > i) continue;
+    double acc = 0.0;
+    int64_t s = 0;
+    for (; s + 8 <= n_seg; s += 8) {   // eight loads in flight, added strictly in order
+      float t[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) t[q] = partials[(s + q) * P + e];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc = acc + (double)t[q];
+    }
+    for (; s < n_seg; ++s) acc = acc + (double)partials[s * P + e];
+    const float g = (float)acc;
+    out[e] = g;
+    out[j * rank + i] = g;
   }
 }
 
@@ -349,16 +452,139 @@ static size_t als_layout(int64_t n_rows, int64_t nnz, int rank, char* base, AlsW
   return off + 256;
 }
 
-static int als_raise_lds(const void* fn, size_t bytes) {
+static int als_raise_lds(const char* who, const void* fn, size_t bytes) {
   if (bytes <= 65536) return ESR_OK;
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-    set_error("esr_als_solve_rows: cannot raise the LDS limit to %zu bytes", bytes);
+    set_error("%s: cannot raise the LDS limit to %zu bytes", who, bytes);
     return ESR_ELAUNCH;
   }
   return ESR_OK;
 }
 
 static bool als_finite(float x) { return x == x && x - x == 0.f; }
+
+static int64_t als_gram_segments(int64_t n) { return n > 0 ? cdiv(n, kAlsGramSegment) : 0; }
+static size_t als_gram_layout(int64_t n, int rank) {
+  rank = std::min(std::max(rank, 1), kAlsMaxRank);
+  return align_up(sizeof(float) * (size_t)als_gram_segments(n) * (size_t)(rank * rank), 256) + 256;
+}
+
+// the half-sweep of esr_als_solve_rows (targets) and of esr_als_solve_rows_implicit (IMP: `targets` are the weights, gram is
+// Y^T Y): one argument check, one row plan, one launch sequence
+template <bool IMP>
+static int als_solve_rows_impl(const char* fn, const float* other_factors, int64_t n_other, int rank, const int64_t* row_offsets,
+                               const int32_t* cols, const float* targets, const float* gram, int64_t row_begin, int64_t row_end,
+                               float reg, int weighted, float* out_factors, int32_t* failed, void* workspace,
+                               size_t workspace_bytes, esr_stream_t stream) {
+  TraceScope trace_scope_(fn);
+  ESR_REQUIRE(rank >= 1 && rank <= kAlsMaxRank, "%s: rank=%d not in [1, %d]", fn, rank, kAlsMaxRank);
+  ESR_REQUIRE(n_other >= 0 && n_other <= (int64_t)INT32_MAX, "%s: bad size n_other=%lld", fn, (long long)n_other);
+  ESR_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end - row_begin <= kAlsMaxRows && row_end <= (int64_t)INT32_MAX,
+              "%s: row range [%lld, %lld) out of order (or longer than 2^30 rows)", fn, (long long)row_begin,
+              (long long)row_end);
+  ESR_REQUIRE(als_finite(reg) && reg > 0.f, "%s: reg=%g must be finite and positive", fn, (double)reg);
+  ESR_REQUIRE(weighted == 0 || weighted == 1, "%s: weighted=%d is not 0 or 1", fn, weighted);
+  ESR_REQUIRE(row_offsets && out_factors && failed && (!IMP || gram), "%s: null pointer", fn);
+  ESR_REQUIRE(((uintptr_t)row_offsets & 7) == 0 && ((uintptr_t)out_factors & 3) == 0 && ((uintptr_t)failed & 3) == 0 &&
+                  ((uintptr_t)other_factors & 3) == 0 && ((uintptr_t)cols & 3) == 0 && ((uintptr_t)targets & 3) == 0,
+              "%s: misaligned pointer", fn);
+  ESR_REQUIRE(((uintptr_t)gram & 3) == 0, "%s: misaligned pointer (gram)", fn);
+  {  // the rows written against the table read
+    const uintptr_t o0 = (uintptr_t)(out_factors + row_begin * rank), o1 = (uintptr_t)(out_factors + row_end * rank);
+    const uintptr_t y0 = (uintptr_t)other_factors, y1 = (uintptr_t)(other_factors + n_other * rank);
+    ESR_REQUIRE(out_factors != other_factors && !(other_factors && o0 < y1 && y0 < o1),
+                "%s: out_factors aliases other_factors", fn);
+    const uintptr_t g0 = (uintptr_t)gram, g1 = g0 + sizeof(float) * (size_t)(rank * rank);
+    ESR_REQUIRE(!IMP || (out_factors != gram && !(o0 < g1 && g0 < o1)), "%s: out_factors aliases gram", fn);
+  }
+  const int64_t n_rows = row_end - row_begin;
+  if (n_rows == 0) return ESR_OK;
+  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < als_layout(n_rows, 0, rank, nullptr, nullptr)) {
+    set_error("%s: workspace %zu bytes < %zu required (or null, or misaligned)", fn, workspace_bytes,
+              als_layout(n_rows, 0, rank, nullptr, nullptr));
+    return ESR_EWORKSPACE;
+  }
+  // the row offsets are HOST memory: the class lists are made here
+  const int64_t first = row_offsets[row_begin], last = row_offsets[row_end];
+  ESR_REQUIRE(first >= 0 && last >= first, "%s: row offsets %lld .. %lld are not ascending from >= 0", fn,
+              (long long)first, (long long)last);
+  const int64_t nnz = last - first;
+  for (int64_t r = row_begin; r < row_end; ++r) {
+    const int64_t len = row_offsets[r + 1] - row_offsets[r];
+    ESR_REQUIRE(len >= 0 && len <= (int64_t)INT32_MAX && row_offsets[r + 1] <= last,
+                "%s: row offsets are not ascending at row %lld (or a row above 2^31 - 1 ratings)", fn, (long long)r);
+  }
+  ESR_REQUIRE(nnz == 0 || (other_factors && cols && targets && n_other >= 1),
+              "%s: null pointer (ratings or other_factors; or n_other=0 with ratings)", fn);
+  const size_t need = als_layout(n_rows, nnz, rank, nullptr, nullptr);
+  if (workspace_bytes < need) {
+    set_error("%s: workspace %zu bytes < %zu required", fn, workspace_bytes, need);
+    return ESR_EWORKSPACE;
+  }
+  AlsWs ws;
+  als_layout(n_rows, nnz, rank, (char*)workspace, &ws);
+  std::vector<AlsUnit> wave_rows, group_rows;
+  std::vector<AlsLongRow> long_rows;
+  std::vector<AlsChunkUnit> chunks;
+  for (int64_t r = row_begin; r < row_end; ++r) {
+    const int64_t a = row_offsets[r], len = row_offsets[r + 1] - a;
+    if (len <= kAlsChunk) wave_rows.push_back(AlsUnit{a, (int32_t)r, (int32_t)len});
+    else if (len <= (int64_t)kAlsChunk * kAlsChunksPerWg) group_rows.push_back(AlsUnit{a, (int32_t)r, (int32_t)len});
+    else {
+      long_rows.push_back(AlsLongRow{a, (long long)chunks.size(), (int32_t)r, (int32_t)len});
+      for (int64_t o = 0; o < len; o += kAlsChunk)
+        chunks.push_back(AlsChunkUnit{a + o, (long long)chunks.size(), (int32_t)std::min<int64_t>(kAlsChunk, len - o), 0});
+    }
+  }
+  if ((int64_t)long_rows.size() > ws.max_long || (int64_t)chunks.size() > ws.max_chunks) {  // (the layout's bound: never)
+    set_error("%s: internal: the long-row plan exceeds its bound", fn);
+    return ESR_EINVAL;
+  }
+  hipStream_t st = as_stream(stream);
+  const size_t n1 = wave_rows.size(), n2 = group_rows.size(), n3 = long_rows.size(), nc = chunks.size();
+  bool copied = true;
+  if (n1) copied &= hipMemcpyAsync(ws.units, wave_rows.data(), sizeof(AlsUnit) * n1, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (n2) copied &= hipMemcpyAsync(ws.units + n1, group_rows.data(), sizeof(AlsUnit) * n2, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (n3) copied &= hipMemcpyAsync(ws.long_rows, long_rows.data(), sizeof(AlsLongRow) * n3, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (nc) copied &= hipMemcpyAsync(ws.chunks, chunks.data(), sizeof(AlsChunkUnit) * nc, hipMemcpyHostToDevice, st) == hipSuccess;
+  // the lists are pageable host memory that dies with this call: the copies are complete before it goes on
+  if (!copied || hipStreamSynchronize(st) != hipSuccess) {
+    if (check_launch(fn) == ESR_OK) set_error("%s: the copy of the row lists failed", fn);
+    return ESR_ELAUNCH;
+  }
+  const bool hi = rank > 32;
+  const size_t lds4 = als_lds_bytes(rank, kAlsWaves), lds1 = als_lds_bytes(rank, 1);
+  const auto wave_rows_kernel = hi ? als_wave_rows_kernel<true, IMP> : als_wave_rows_kernel<false, IMP>;
+  const auto group_rows_kernel = hi ? als_group_rows_kernel<true, IMP> : als_group_rows_kernel<false, IMP>;
+  const auto chunk_partials_kernel = hi ? als_chunk_partials_kernel<true, IMP> : als_chunk_partials_kernel<false, IMP>;
+  // above the 64 KiB a kernel gets unasked (rank 64): raised on every such call, for the device the call runs on -- no flag
+  // that another device or another thread could find set
+  if (n1 && als_raise_lds(fn, (const void*)wave_rows_kernel, lds4)) return ESR_ELAUNCH;
+  if (n2 && als_raise_lds(fn, (const void*)group_rows_kernel, lds4)) return ESR_ELAUNCH;
+  const AlsIn in{other_factors, n_other, rank, cols, targets, reg, weighted, out_factors, failed, gram};
+  if (n1) {
+    const int grid = (int)std::min<int64_t>(kMaxGrid, cdiv((int64_t)n1, kAlsWaves));
+    ESR_KT(IMP ? "als_wave_rows_implicit" : "als_wave_rows", st,
+           hipLaunchKernelGGL(wave_rows_kernel, dim3(grid), dim3(kBlock), lds4, st, in, (const AlsUnit*)ws.units, (int64_t)n1));
+  }
+  if (n2) {
+    const int grid = (int)std::min<int64_t>(kMaxGrid, (int64_t)n2);
+    ESR_KT(IMP ? "als_group_rows_implicit" : "als_group_rows", st,
+           hipLaunchKernelGGL(group_rows_kernel, dim3(grid), dim3(kBlock), lds4, st, in, (const AlsUnit*)(ws.units + n1),
+                              (int64_t)n2));
+  }
+  if (n3) {
+    const int grid = (int)std::min<int64_t>(4 * kMaxGrid, cdiv((int64_t)nc, kAlsWaves));
+    ESR_KT(IMP ? "als_chunk_partials_implicit" : "als_chunk_partials", st,
+           hipLaunchKernelGGL(chunk_partials_kernel, dim3(grid), dim3(kBlock), 0, st, in, (const AlsChunkUnit*)ws.chunks,
+                              (int64_t)nc, ws.partials));
+    ESR_KT(IMP ? "als_long_rows_implicit" : "als_long_rows", st,
+           hipLaunchKernelGGL(als_long_rows_kernel<IMP>, dim3((int)std::min<int64_t>(kMaxGrid, (int64_t)n3)),
+                              dim3(kAlsFinishBlock), lds1, st, in, (const AlsLongRow*)ws.long_rows, (int64_t)n3,
+                              (const float*)ws.partials));
+  }
+  return check_launch(fn);
+}
 
 }  // namespace esr
 
@@ -382,111 +608,56 @@ size_t esr_als_solve_workspace_bytes(int64_t n_rows, int64_t nnz, int rank) {
 int esr_als_solve_rows(const float* other_factors, int64_t n_other, int rank, const int64_t* row_offsets, const int32_t* cols,
                        const float* targets, int64_t row_begin, int64_t row_end, float reg, int weighted, float* out_factors,
                        int32_t* failed, void* workspace, size_t workspace_bytes, esr_stream_t stream) {
-  TraceScope trace_scope_("esr_als_solve_rows");
-  ESR_REQUIRE(rank >= 1 && rank <= kAlsMaxRank, "esr_als_solve_rows: rank=%d not in [1, %d]", rank, kAlsMaxRank);
-  ESR_REQUIRE(n_other >= 0 && n_other <= (int64_t)INT32_MAX, "esr_als_solve_rows: bad size n_other=%lld", (long long)n_other);
-  ESR_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end - row_begin <= kAlsMaxRows && row_end <= (int64_t)INT32_MAX,
-              "esr_als_solve_rows: row range [%lld, %lld) out of order (or longer than 2^30 rows)", (long long)row_begin,
-              (long long)row_end);
-  ESR_REQUIRE(als_finite(reg) && reg > 0.f, "esr_als_solve_rows: reg=%g must be finite and positive", (double)reg);
-  ESR_REQUIRE(weighted == 0 || weighted == 1, "esr_als_solve_rows: weighted=%d is not 0 or 1", weighted);
-  ESR_REQUIRE(row_offsets && out_factors && failed, "esr_als_solve_rows: null pointer");
-  ESR_REQUIRE(((uintptr_t)row_offsets & 7) == 0 && ((uintptr_t)out_factors & 3) == 0 && ((uintptr_t)failed & 3) == 0 &&
-                  ((uintptr_t)other_factors & 3) == 0 && ((uintptr_t)cols & 3) == 0 && ((uintptr_t)targets & 3) == 0,
-              "esr_als_solve_rows: misaligned pointer");
-  {  // the rows written against the table read
-    const uintptr_t o0 = (uintptr_t)(out_factors + row_begin * rank), o1 = (uintptr_t)(out_factors + row_end * rank);
-    const uintptr_t y0 = (uintptr_t)other_factors, y1 = (uintptr_t)(other_factors + n_other * rank);
-    ESR_REQUIRE(out_factors != other_factors && !(other_factors && o0 < y1 && y0 < o1),
-                "esr_als_solve_rows: out_factors aliases other_factors");
+  return als_solve_rows_impl<false>("esr_als_solve_rows", other_factors, n_other, rank, row_offsets, cols, targets, nullptr,
+                                    row_begin, row_end, reg, weighted, out_factors, failed, workspace, workspace_bytes, stream);
+}
+
+int esr_als_solve_rows_implicit(const float* other_factors, int64_t n_other, int rank, const float* gram,
+                                const int64_t* row_offsets, const int32_t* cols, const float* weights, int64_t row_begin,
+                                int64_t row_end, float reg, int weighted, float* out_factors, int32_t* failed, void* workspace,
+                                size_t workspace_bytes, esr_stream_t stream) {
+  return als_solve_rows_impl<true>("esr_als_solve_rows_implicit", other_factors, n_other, rank, row_offsets, cols, weights, gram,
+                                   row_begin, row_end, reg, weighted, out_factors, failed, workspace, workspace_bytes, stream);
+}
+
+int esr_als_gram_geometry(int* segment) {
+  ESR_REQUIRE(segment, "esr_als_gram_geometry: null pointer");
+  *segment = kAlsGramSegment;
+  return ESR_OK;
+}
+
+size_t esr_als_gram_workspace_bytes(int64_t n, int rank) { return als_gram_layout(n, rank); }
+
+int esr_als_gram(const float* factors, int64_t n, int rank, float* out_gram, void* workspace, size_t workspace_bytes,
+                 esr_stream_t stream) {
+  TraceScope trace_scope_("esr_als_gram");
+  ESR_REQUIRE(rank >= 1 && rank <= kAlsMaxRank, "esr_als_gram: rank=%d not in [1, %d]", rank, kAlsMaxRank);
+  ESR_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX, "esr_als_gram: bad size n=%lld", (long long)n);
+  ESR_REQUIRE(out_gram && (n == 0 || factors), "esr_als_gram: null pointer");
+  ESR_REQUIRE(((uintptr_t)factors & 3) == 0 && ((uintptr_t)out_gram & 3) == 0, "esr_als_gram: misaligned pointer");
+  {
+    const uintptr_t o0 = (uintptr_t)out_gram, o1 = (uintptr_t)(out_gram + rank * rank);
+    const uintptr_t y0 = (uintptr_t)factors, y1 = (uintptr_t)(factors + n * rank);
+    ESR_REQUIRE(out_gram != factors && !(factors && o0 < y1 && y0 < o1), "esr_als_gram: out_gram aliases factors");
   }
-  const int64_t n_rows = row_end - row_begin;
-  if (n_rows == 0) return ESR_OK;
-  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < als_layout(n_rows, 0, rank, nullptr, nullptr)) {
-    set_error("esr_als_solve_rows: workspace %zu bytes < %zu required (or null, or misaligned)", workspace_bytes,
-              als_layout(n_rows, 0, rank, nullptr, nullptr));
+  const size_t need = als_gram_layout(n, rank);
+  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need) {
+    set_error("esr_als_gram: workspace %zu bytes < %zu required (or null, or misaligned)", workspace_bytes, need);
     return ESR_EWORKSPACE;
-  }
-  // the row offsets are HOST memory: the class lists are made here
-  const int64_t first = row_offsets[row_begin], last = row_offsets[row_end];
-  ESR_REQUIRE(first >= 0 && last >= first, "esr_als_solve_rows: row offsets %lld .. %lld are not ascending from >= 0",
-              (long long)first, (long long)last);
-  const int64_t nnz = last - first;
-  for (int64_t r = row_begin; r < row_end; ++r) {
-    const int64_t len = row_offsets[r + 1] - row_offsets[r];
-    ESR_REQUIRE(len >= 0 && len <= (int64_t)INT32_MAX && row_offsets[r + 1] <= last,
-                "esr_als_solve_rows: row offsets are not ascending at row %lld (or a row above 2^31 - 1 ratings)", (long long)r);
-  }
-  ESR_REQUIRE(nnz == 0 || (other_factors && cols && targets && n_other >= 1),
-              "esr_als_solve_rows: null pointer (ratings or other_factors; or n_other=0 with ratings)");
-  const size_t need = als_layout(n_rows, nnz, rank, nullptr, nullptr);
-  if (workspace_bytes < need) {
-    set_error("esr_als_solve_rows: workspace %zu bytes < %zu required", workspace_bytes, need);
-    return ESR_EWORKSPACE;
-  }
-  AlsWs ws;
-  als_layout(n_rows, nnz, rank, (char*)workspace, &ws);
-  std::vector<AlsUnit> wave_rows, group_rows;
-  std::vector<AlsLongRow> long_rows;
-  std::vector<AlsChunkUnit> chunks;
-  for (int64_t r = row_begin; r < row_end; ++r) {
-    const int64_t a = row_offsets[r], len = row_offsets[r + 1] - a;
-    if (len <= kAlsChunk) wave_rows.push_back(AlsUnit{a, (int32_t)r, (int32_t)len});
-    else if (len <= (int64_t)kAlsChunk * kAlsChunksPerWg) group_rows.push_back(AlsUnit{a, (int32_t)r, (int32_t)len});
-    else {
-      long_rows.push_back(AlsLongRow{a, (long long)chunks.size(), (int32_t)r, (int32_t)len});
-      for (int64_t o = 0; o < len; o += kAlsChunk)
-        chunks.push_back(AlsChunkUnit{a + o, (long long)chunks.size(), (int32_t)std::min<int64_t>(kAlsChunk, len - o), 0});
-    }
-  }
-  if ((int64_t)long_rows.size() > ws.max_long || (int64_t)chunks.size() > ws.max_chunks) {  // (the layout's bound: never)
-    set_error("esr_als_solve_rows: internal: the long-row plan exceeds its bound");
-    return ESR_EINVAL;
   }
   hipStream_t st = as_stream(stream);
-  const size_t n1 = wave_rows.size(), n2 = group_rows.size(), n3 = long_rows.size(), nc = chunks.size();
-  bool copied = true;
-  if (n1) copied &= hipMemcpyAsync(ws.units, wave_rows.data(), sizeof(AlsUnit) * n1, hipMemcpyHostToDevice, st) == hipSuccess;
-  if (n2) copied &= hipMemcpyAsync(ws.units + n1, group_rows.data(), sizeof(AlsUnit) * n2, hipMemcpyHostToDevice, st) == hipSuccess;
-  if (n3) copied &= hipMemcpyAsync(ws.long_rows, long_rows.data(), sizeof(AlsLongRow) * n3, hipMemcpyHostToDevice, st) == hipSuccess;
-  if (nc) copied &= hipMemcpyAsync(ws.chunks, chunks.data(), sizeof(AlsChunkUnit) * nc, hipMemcpyHostToDevice, st) == hipSuccess;
-  // the lists are pageable host memory that dies with this call: the copies are complete before it goes on
-  if (!copied || hipStreamSynchronize(st) != hipSuccess) {
-    if (check_launch("esr_als_solve_rows") == ESR_OK) set_error("esr_als_solve_rows: the copy of the row lists failed");
-    return ESR_ELAUNCH;
+  const int64_t n_seg = als_gram_segments(n);
+  float* partials = (float*)workspace;
+  if (n_seg) {
+    const int grid = (int)std::min<int64_t>(4 * kMaxGrid, cdiv(n_seg, kAlsWaves));
+    const auto segments_kernel = rank > 32 ? als_gram_segments_kernel<true> : als_gram_segments_kernel<false>;
+    ESR_KT("als_gram_segments", st,
+           hipLaunchKernelGGL(segments_kernel, dim3(grid), dim3(kBlock), 0, st, factors, n, rank, n_seg, partials));
   }
-  const bool hi = rank > 32;
-  const size_t lds4 = als_lds_bytes(rank, kAlsWaves), lds1 = als_lds_bytes(rank, 1);
-  // above the 64 KiB a kernel gets unasked (rank 64): raised on every such call, for the device the call runs on -- no flag
-  // that another device or another thread could find set
-  if (n1 && als_raise_lds((const void*)als_wave_rows_kernel<true>, lds4)) return ESR_ELAUNCH;
-  if (n2 && als_raise_lds((const void*)als_group_rows_kernel<true>, lds4)) return ESR_ELAUNCH;
-  const AlsIn in{other_factors, n_other, rank, cols, targets, reg, weighted, out_factors, failed};
-  if (n1) {
-    const int grid = (int)std::min<int64_t>(kMaxGrid, cdiv((int64_t)n1, kAlsWaves));
-    if (hi) ESR_KT("als_wave_rows", st, hipLaunchKernelGGL(als_wave_rows_kernel<true>, dim3(grid), dim3(kBlock), lds4, st, in,
-                                                           (const AlsUnit*)ws.units, (int64_t)n1));
-    else ESR_KT("als_wave_rows", st, hipLaunchKernelGGL(als_wave_rows_kernel<false>, dim3(grid), dim3(kBlock), lds4, st, in,
-                                                        (const AlsUnit*)ws.units, (int64_t)n1));
-  }
-  if (n2) {
-    const int grid = (int)std::min<int64_t>(kMaxGrid, (int64_t)n2);
-    if (hi) ESR_KT("als_group_rows", st, hipLaunchKernelGGL(als_group_rows_kernel<true>, dim3(grid), dim3(kBlock), lds4, st, in,
-                                                            (const AlsUnit*)(ws.units + n1), (int64_t)n2));
-    else ESR_KT("als_group_rows", st, hipLaunchKernelGGL(als_group_rows_kernel<false>, dim3(grid), dim3(kBlock), lds4, st, in,
-                                                         (const AlsUnit*)(ws.units + n1), (int64_t)n2));
-  }
-  if (n3) {
-    const int grid = (int)std::min<int64_t>(4 * kMaxGrid, cdiv((int64_t)nc, kAlsWaves));
-    if (hi) ESR_KT("als_chunk_partials", st, hipLaunchKernelGGL(als_chunk_partials_kernel<true>, dim3(grid), dim3(kBlock), 0, st, in,
-                                                                (const AlsChunkUnit*)ws.chunks, (int64_t)nc, ws.partials));
-    else ESR_KT("als_chunk_partials", st, hipLaunchKernelGGL(als_chunk_partials_kernel<false>, dim3(grid), dim3(kBlock), 0, st, in,
-                                                             (const AlsChunkUnit*)ws.chunks, (int64_t)nc, ws.partials));
-    ESR_KT("als_long_rows", st,
-           hipLaunchKernelGGL(als_long_rows_kernel, dim3((int)std::min<int64_t>(kMaxGrid, (int64_t)n3)), dim3(kAlsFinishBlock),
-                              lds1, st, in, (const AlsLongRow*)ws.long_rows, (int64_t)n3, (const float*)ws.partials));
-  }
-  return check_launch("esr_als_solve_rows");
+  ESR_KT("als_gram_sum", st,
+         hipLaunchKernelGGL(als_gram_sum_kernel, dim3((int)cdiv(rank * rank, kBlock)), dim3(kBlock), 0, st,
+                            (const float*)partials, n_seg, rank, out_gram));
+  return check_launch("esr_als_gram");
 }
 
 int esr_als_predict(const float* user_factors, int64_t nu, const float* item_factors, int64_t ni, int rank,

@@ -24,6 +24,10 @@ is a function of the inputs and the seed -- not of the grid or of ``max_rows_per
 Prediction.  One kernel computes ``float32(c[u] + sum_d float64(x[d]) * float64(y[d]))`` (fp64, ascending d, rounded once);
 ``residuals`` is ``float32(float64(d) - dot)`` by the same kernel; ``objective`` and ``rmse`` are fp64 torch reductions
 over those outputs and the factor tables.
+
+Implicit feedback.  ``ImplicitALS`` (below) is the confidence-weighted model of Hu, Koren and Volinsky for occurrence data:
+every cell is fitted, a half-sweep is one ``ops.als_gram`` and one ``ops.als_solve_rows_implicit``, and new documents are
+folded in by the same call (``fold_in``, ``recommend_documents``).
 """
 import math
 
@@ -221,57 +225,339 @@ class RatingsALS:
         Candidates are ``ops.retrieve_topk(x_u, item_factors, k', mode="exact")`` with ``k' = min(ni, k + r_max + slack)``,
         r_max the longest rated list among the queried users (0 without `exclude_rated`); they are re-scored by the predict
         kernel.  A k' above retrieve_topk's limit raises ``ValueError`` naming the query before any launch."""
-        k, slack = int(k), int(slack)
-        if not 1 <= k <= MAX_K:
-            raise ValueError("k = %d outside [1, %d]" % (k, MAX_K))
-        if slack < 0:
-            raise ValueError("slack = %d is negative" % slack)
+        with torch.cuda.device(self.device):
+            upos = self._positions(users, self.users).to(torch.int64)
+            return _recommend_rows(self.user_factors, self.user_mean, upos, self.item_factors, self.items, k, slack,
+                                   self._user_offsets if exclude_rated else None, self._key,
+                                   lambda q: "user %d" % int(_tensor(users, "users")[q]), "rated", "exclude_rated")
+
+
+def _recommend_rows(factors, offset, upos, item_factors, items, k, slack, seen_offsets, seen_key, name, verb, flag):
+    """The body ``RatingsALS.recommend`` and ``ImplicitALS.recommend`` / ``recommend_documents`` share.  Query q is row
+    ``upos[q]`` (int64, -1: unknown, an empty list) of ``factors``; its score of item position i is ``ops.als_predict`` of
+    that pair with ``offset`` (float64 per row, or None).  With ``seen_offsets`` (host CSR offsets of the rows' own items)
+    the pairs of ``seen_key`` (``row << 32 | item position``, ascending) are left out.  ``name(q)``, ``verb`` and ``flag``
+    word the refusal of a query with too many candidates."""
+    k, slack = int(k), int(slack)
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k = %d outside [1, %d]" % (k, MAX_K))
+    if slack < 0:
+        raise ValueError("slack = %d is negative" % slack)
+    dev = factors.device
+    exclude = seen_offsets is not None
+    nq, ni = int(upos.numel()), int(items.numel())
+    ids = torch.full((nq, k), -1, dtype=torch.int32, device=dev)
+    scores = torch.zeros((nq, k), dtype=torch.float32, device=dev)
+    lengths = torch.zeros(nq, dtype=torch.int32, device=dev)
+    if nq == 0 or ni == 0:
+        return ids, scores, lengths
+    known = upos >= 0
+    safe = upos.clamp(min=0)
+    r_max = 0
+    if exclude and bool(known.any()):
+        lens = torch.from_numpy(np.diff(seen_offsets)).to(dev)
+        rated = torch.where(known, lens[safe], torch.zeros_like(safe))
+        r_max = int(rated.max())
+        if k + r_max + slack > RETRIEVE_LIMIT and ni > RETRIEVE_LIMIT:
+            q = int(torch.argmax(rated))
+            raise ValueError("query %d (%s) %s %d items: k + rated + slack = %d candidates exceed the %d "
+                             "that retrieve_topk selects; lower k or query that user without %s"
+                             % (q, name(q), verb, r_max, k + r_max + slack, RETRIEVE_LIMIT, flag))
+    kc = min(ni, k + r_max + slack)
+    if kc > RETRIEVE_LIMIT:
+        raise ValueError("query 0: k + slack = %d candidates exceed the %d that retrieve_topk selects"
+                         % (k + slack, RETRIEVE_LIMIT))
+    queries = torch.where(known[:, None], factors[safe], torch.zeros((), device=dev)).contiguous()
+    _, cand = ops.retrieve_topk(queries, item_factors, kc, mode="exact")          # [nq, kc] item positions
+    cand = cand.to(torch.int64)
+    sc = ops.als_predict(factors, item_factors, upos[:, None].expand(nq, kc).to(torch.int32).contiguous().reshape(-1),
+                         cand.to(torch.int32).contiguous().reshape(-1), offset=offset).reshape(nq, kc)
+    drop = ~known[:, None].expand(nq, kc)
+    if exclude and seen_key.numel():
+        pair = (safe[:, None] << 32) | cand
+        at = torch.searchsorted(seen_key, pair.reshape(-1)).clamp(max=seen_key.numel() - 1).reshape(nq, kc)
+        drop = drop | (seen_key[at] == pair)
+    # (score descending, item ascending): positions ascend with ids; dropped candidates go last
+    by_item = torch.sort(cand, dim=1, stable=True)
+    sc_i, drop_i = torch.gather(sc, 1, by_item.indices), torch.gather(drop, 1, by_item.indices)
+    rank_key = torch.where(drop_i, torch.full_like(sc_i, -float("inf")), sc_i)
+    by_score = torch.sort(rank_key, dim=1, descending=True, stable=True)
+    live = (~torch.gather(drop_i, 1, by_score.indices))[:, :k]
+    kk = min(k, kc)
+    top_items = torch.gather(by_item.values, 1, by_score.indices)[:, :kk]
+    top_scores = torch.gather(sc_i, 1, by_score.indices)[:, :kk]
+    ids[:, :kk] = torch.where(live, items[top_items], torch.full_like(ids[:, :kk], -1))
+    scores[:, :kk] = torch.where(live, top_scores, torch.zeros_like(top_scores))
+    lengths = live.sum(1).to(torch.int32)
+    return ids, scores, lengths
+
+
+# ---- implicit feedback ---------------------------------------------------------------------------------------------------
+FAIL_BAD_WEIGHT = 1 << 29    # esr_als.hip: a weight that is negative or not finite
+
+
+def _ids_and_offsets(indices, doc_offsets, dev):
+    """(ids int64 on `dev`, host offsets int64[ndocs + 1]) of an id-document CSR given as host arrays or tensors."""
+    ids = _tensor(indices, "indices")
+    if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        raise TypeError("indices must be an integer array")
+    off = doc_offsets.detach().cpu().numpy() if isinstance(doc_offsets, torch.Tensor) else np.asarray(doc_offsets)
+    if off.dtype.kind not in "iu":
+        raise TypeError("doc_offsets must be an integer array")
+    off = np.ascontiguousarray(off.reshape(-1).astype(np.int64))
+    ids = ids.reshape(-1).to(dev).to(torch.int64)
+    if off.size < 1 or int(off[0]) != 0 or int(off[-1]) != ids.numel() or bool((np.diff(off) < 0).any()):
+        raise ValueError("doc_offsets must ascend from 0 to the %d ids of indices" % ids.numel())
+    return ids, off
+
+
+def _sum_events(major, minor, strength, n_major, alpha):
+    """Events (major, minor, strength float64) with repeats -> (key int64 ascending and distinct, major << 32 | minor; host
+    row offsets int64[n_major + 1]; w float32 = float32(alpha * the pair's strengths summed in fp64 in the events' order)).
+    The sum runs over a stable sort on the host (numpy add.reduceat): the same bits for the same events, whatever the
+    device did before -- torch plumbing, not a hot path."""
+    dev = major.device
+    key = (major.to(torch.int64) << 32) | minor.to(torch.int64)
+    key, order = torch.sort(key, stable=True)
+    ukey, counts = torch.unique_consecutive(key, return_counts=True)
+    if key.numel():
+        starts = (torch.cumsum(counts, 0) - counts).cpu().numpy()
+        sums = np.add.reduceat(strength[order].cpu().numpy().astype(np.float64), starts)
+    else:
+        sums = np.zeros(0, np.float64)
+    w = (np.float64(alpha) * sums).astype(np.float32)
+    rows = torch.bincount(ukey >> 32, minlength=n_major)
+    offsets = np.concatenate([[0], np.cumsum(rows.cpu().numpy().astype(np.int64))]).astype(np.int64)
+    return ukey, np.ascontiguousarray(offsets), torch.from_numpy(w).to(dev)
+
+
+class ImplicitALS:
+    """Confidence-weighted matrix factorisation of implicit feedback (Hu, Koren, Volinsky 2008) by ALS on the GPU.
+
+        model = ImplicitALS.from_documents(indices, doc_offsets, rank=32, alpha=40.0)   # user = document, strength = count
+        history = model.fit(sweeps=10)                     # the full-matrix objective after every half-sweep
+        x = model.fold_in(new_indices, new_offsets)        # factors of NEW documents against the fitted items, no retraining
+        rec_ids, rec_scores, rec_lengths = model.recommend_documents(context, context_offsets, k=500)
+
+    Model.  EVERY (user, item) cell is fitted: preference p = 1 where the pair was seen and 0 elsewhere, confidence
+    ``c = 1 + w`` with ``w = float32(alpha * strength)`` on the seen cells (repeated events add their strengths in fp64) and
+    1 on the rest.
+
+    Objective.  ``J = sum over ALL cells of c (p - x_u . y_i)^2 + reg (sum_u w_u |x_u|^2 + sum_i w_i |y_i|^2)``, w the
+    row's number of seen cells (``weighted_reg``) or 1 (the default).
+
+    Half-sweep.  One ``ops.als_gram`` of the other side (``G = Y^T Y``) and one ``ops.als_solve_rows_implicit`` per
+    ``max_rows_per_launch`` slice: a row with n seen cells solves ``(G + sum_k w_k y_k y_k^T + lam I) x = sum_k (1 + w_k)
+    y_k``, ``lam = reg * (n if weighted_reg else 1)``, in the order esr_als.hip states.  A solved row is a function of its
+    own (item, weight) list, the other side's factors, reg and weighted_reg alone, so ``fold_in`` of a training user's own
+    items returns that user's row bit for bit.  A row without seen cells gets the zero vector."""
+
+    def __init__(self, user, item, strength=None, rank=32, reg=0.01, alpha=40.0, weighted_reg=False, seed=0, init_scale=None,
+                 device=None, max_rows_per_launch=None):
+        rank = int(rank)
+        if not 1 <= rank <= max_rank():
+            raise ValueError("rank = %d outside [1, %d]" % (rank, max_rank()))
+        reg = float(reg)
+        if not (math.isfinite(reg) and reg > 0.0 and float(np.float32(reg)) > 0.0 and math.isfinite(float(np.float32(reg)))):
+            raise ValueError("reg = %r must be finite and positive" % (reg,))
+        alpha = float(alpha)
+        if not (math.isfinite(alpha) and alpha > 0.0):
+            raise ValueError("alpha = %r must be finite and positive" % (alpha,))
+        if max_rows_per_launch is not None and int(max_rows_per_launch) < 1:
+            raise ValueError("max_rows_per_launch = %r below 1" % (max_rows_per_launch,))
+        user, item = _tensor(user, "user"), _tensor(item, "item")
+        if strength is None:
+            _same_length("user and item", user, item)
+        else:
+            strength = _tensor(strength, "strength")
+            _same_length("user, item and strength", user, item, strength)
+        if user.dtype.is_floating_point or item.dtype.is_floating_point:
+            raise TypeError("user and item must be integer arrays")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise TypeError("device must be a CUDA/ROCm device (no CPU fallback exists)")
+        self.rank, self.reg, self.alpha, self.weighted_reg, self.seed = rank, reg, alpha, bool(weighted_reg), int(seed)
+        self.max_rows_per_launch = None if max_rows_per_launch is None else int(max_rows_per_launch)
+        self.init_scale = float(rank) ** -0.5 if init_scale is None else float(init_scale)
         dev = self.device
         with torch.cuda.device(dev):
+            user, item = user.to(dev).to(torch.int64), item.to(dev).to(torch.int64)
+            if user.numel() and (int(user.min()) < 0 or int(item.min()) < 0 or int(user.max()) >= 2 ** 31 - 1
+                                 or int(item.max()) >= 2 ** 31 - 1):
+                raise ValueError("user and item ids must lie in [0, 2^31 - 1)")
+            s64 = self._strengths(strength, user.numel())
+            users, upos = torch.unique(user, return_inverse=True)
+            items, ipos = torch.unique(item, return_inverse=True)
+            nu, ni = int(users.numel()), int(items.numel())
+            self.users, self.items = users.to(torch.int32).contiguous(), items.to(torch.int32).contiguous()
+            # CSR by user (items ascending) and its transpose (users ascending); one weight per distinct pair
+            key, self._user_offsets, w = _sum_events(upos, ipos, s64, nu, alpha)
+            if w.numel() and not bool(torch.isfinite(w).all()):
+                raise ValueError("alpha * strength does not fit a float32")
+            self._key = key                                             # upos << 32 | ipos, ascending: the seen pairs
+            self._row_upos = (key >> 32).to(torch.int32).contiguous()
+            self._row_ipos = (key & 0xFFFFFFFF).to(torch.int32).contiguous()
+            self._weights = w.contiguous()
+            _, self._item_offsets, order_i = _csr(self._row_ipos, self._row_upos, ni)
+            self._col_upos = self._row_upos[order_i].contiguous()
+            self._weights_by_item = self._weights[order_i].contiguous()
+            gen = torch.Generator(device="cpu").manual_seed(self.seed)
+            self.item_factors = (torch.randn(ni, rank, generator=gen) * self.init_scale).to(dev).contiguous()
+            self.user_factors = torch.zeros(nu, rank, dtype=torch.float32, device=dev)
+            self._failed = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._item_gram = None      # (Y^T Y, the version of item_factors it was made from): fold_in's cache
+
+    def _strengths(self, strength, n):
+        """float64[n] on the device: 1 per event without `strength`; refuses one that is not finite and positive."""
+        if strength is None:
+            return torch.ones(n, dtype=torch.float64, device=self.device)
+        s64 = strength.reshape(-1).to(device=self.device, dtype=torch.float64)
+        if s64.numel() and not bool((torch.isfinite(s64) & (s64 > 0)).all()):
+            raise ValueError("every strength must be finite and positive")
+        return s64
+
+    @classmethod
+    def from_documents(cls, indices, doc_offsets, **kw):
+        """The model of id documents ``indices[doc_offsets[d]:doc_offsets[d + 1]]``: the user is the document number, the
+        strength of (d, id) the id's occurrence count in d."""
+        ids, off = _ids_and_offsets(indices, doc_offsets, torch.device("cpu"))
+        docs = torch.from_numpy(np.repeat(np.arange(off.size - 1, dtype=np.int64), np.diff(off)))
+        return cls(docs, ids, None, **kw)
+
+    nnz = property(lambda self: int(self._weights.numel()))
+
+    # ---- the fit --------------------------------------------------------------------------------------------------------
+    def _raise(self, word, side):
+        if word & FAIL_BAD_POSITION:
+            raise FactorizationError("the %s half-sweep met a position outside the other side's table" % side)
+        if word & FAIL_BAD_WEIGHT:
+            raise FactorizationError("the %s half-sweep met a weight that is negative or not finite (bit 29)" % side)
+        if word:
+            raise FactorizationError("the %s half-sweep could not solve %d row(s): a pivot that is not finite and positive "
+                                     "(are the other side's factors finite?); those rows were left unchanged" % (side, word))
+
+    def _half_sweep(self, other, gram, offsets, cols, weights, out, side):
+        n_rows = offsets.size - 1
+        step = n_rows if self.max_rows_per_launch is None else self.max_rows_per_launch
+        with torch.cuda.device(self.device):
+            self._failed.zero_()
+            for a in range(0, n_rows, max(step, 1)):
+                ops.als_solve_rows_implicit(other, gram, offsets, cols, weights, a, min(a + step, n_rows), self.reg,
+                                            self.weighted_reg, out, self._failed)
+            word = int(self._failed.item())
+        self._raise(word, side)
+
+    def _gram_of_items(self):
+        """Y^T Y of the item factors, kept until they next change (solve_items, or an in-place torch write)."""
+        version = (self.item_factors._version, self.item_factors.data_ptr())
+        if self._item_gram is None or self._item_gram[1] != version:
+            with torch.cuda.device(self.device):
+                self._item_gram = (ops.als_gram(self.item_factors), version)
+        return self._item_gram[0]
+
+    def solve_users(self):
+        self._half_sweep(self.item_factors, self._gram_of_items(), self._user_offsets, self._row_ipos, self._weights,
+                         self.user_factors, "user")
+
+    def solve_items(self):
+        with torch.cuda.device(self.device):
+            gram = ops.als_gram(self.user_factors)
+        self._item_gram = None
+        self._half_sweep(self.user_factors, gram, self._item_offsets, self._col_upos, self._weights_by_item, self.item_factors,
+                         "item")
+
+    def sweep(self):
+        """One user half-sweep, then one item half-sweep."""
+        self.solve_users()
+        self.solve_items()
+
+    def fit(self, sweeps=10):
+        """`sweeps` sweeps; returns the objective after every half-sweep (2 per sweep), a list of float."""
+        history = []
+        for _ in range(int(sweeps)):
+            self.solve_users()
+            history.append(self.objective())
+            self.solve_items()
+            history.append(self.objective())
+        return history
+
+    def objective(self):
+        """J of the class text in fp64 torch (python float), without the matrix: the cells at confidence 1 and preference 0
+        sum to ``sum_u x_u^T (Y^T Y) x_u``; a seen cell with dot s adds ``(1 + w) (1 - s)^2 - s^2``."""
+        with torch.cuda.device(self.device):
+            X, Y = self.user_factors.to(torch.float64), self.item_factors.to(torch.float64)
+            everything = ((X @ (Y.t() @ Y)) * X).sum()
+            u, i = self._row_upos.to(torch.int64), self._row_ipos.to(torch.int64)
+            s = (X[u] * Y[i]).sum(1)
+            c = 1.0 + self._weights.to(torch.float64)
+            seen = (c * (1.0 - s) ** 2 - s * s).sum()
+            wu = torch.from_numpy(np.diff(self._user_offsets)).to(self.device).to(torch.float64)
+            wi = torch.from_numpy(np.diff(self._item_offsets)).to(self.device).to(torch.float64)
+            if not self.weighted_reg:
+                wu, wi = torch.ones_like(wu), torch.ones_like(wi)
+            return float(everything + seen + self.reg * (wu * (X * X).sum(1)).sum() + self.reg * (wi * (Y * Y).sum(1)).sum())
+
+    # ---- scores and recommendation ----------------------------------------------------------------------------------------
+    _positions = RatingsALS._positions
+
+    def score(self, users, items):
+        """float32[nq]: ``float32(x_u . y_i)`` (fp64 sum in ascending dimension); NaN where the user or the item is
+        unknown."""
+        users, items = _tensor(users, "users"), _tensor(items, "items")
+        _same_length("users and items", users, items)
+        with torch.cuda.device(self.device):
+            return ops.als_predict(self.user_factors, self.item_factors, self._positions(users, self.users),
+                                   self._positions(items, self.items))
+
+    def recommend(self, users, k=500, exclude_seen=True, slack=16):
+        """Per query user the k best items by (score descending, item id ascending), without the user's seen items when
+        `exclude_seen`: (rec_ids int32[nq, k] padded with -1, rec_scores float32[nq, k] padded with 0, rec_lengths
+        int32[nq]) as ``RatingsALS.recommend``, by the same candidate scheme; a score equals ``score`` of the pair bit for
+        bit, an unknown user gets an empty list."""
+        with torch.cuda.device(self.device):
             upos = self._positions(users, self.users).to(torch.int64)
-            nq, ni = int(upos.numel()), int(self.items.numel())
-            ids = torch.full((nq, k), -1, dtype=torch.int32, device=dev)
-            scores = torch.zeros((nq, k), dtype=torch.float32, device=dev)
-            lengths = torch.zeros(nq, dtype=torch.int32, device=dev)
-            if nq == 0 or ni == 0:
-                return ids, scores, lengths
-            known = upos >= 0
-            safe = upos.clamp(min=0)
-            r_max = 0
-            if exclude_rated and bool(known.any()):
-                lens = torch.from_numpy(np.diff(self._user_offsets)).to(dev)
-                rated = torch.where(known, lens[safe], torch.zeros_like(safe))
-                r_max = int(rated.max())
-                if k + r_max + slack > RETRIEVE_LIMIT and ni > RETRIEVE_LIMIT:
-                    q = int(torch.argmax(rated))
-                    raise ValueError("query %d (user %d) rated %d items: k + rated + slack = %d candidates exceed the %d "
-                                     "that retrieve_topk selects; lower k or query that user without exclude_rated"
-                                     % (q, int(_tensor(users, "users")[q]), r_max, k + r_max + slack, RETRIEVE_LIMIT))
-            kc = min(ni, k + r_max + slack)
-            if kc > RETRIEVE_LIMIT:
-                raise ValueError("query 0: k + slack = %d candidates exceed the %d that retrieve_topk selects"
-                                 % (k + slack, RETRIEVE_LIMIT))
-            queries = torch.where(known[:, None], self.user_factors[safe], torch.zeros((), device=dev)).contiguous()
-            _, cand = ops.retrieve_topk(queries, self.item_factors, kc, mode="exact")          # [nq, kc] item positions
-            cand = cand.to(torch.int64)
-            sc = ops.als_predict(self.user_factors, self.item_factors,
-                                 upos[:, None].expand(nq, kc).to(torch.int32).contiguous().reshape(-1),
-                                 cand.to(torch.int32).contiguous().reshape(-1), offset=self.user_mean).reshape(nq, kc)
-            drop = ~known[:, None].expand(nq, kc)
-            if exclude_rated and self._key.numel():
-                pair = (safe[:, None] << 32) | cand
-                at = torch.searchsorted(self._key, pair.reshape(-1)).clamp(max=self._key.numel() - 1).reshape(nq, kc)
-                drop = drop | (self._key[at] == pair)
-            # (score descending, item ascending): positions ascend with ids; dropped candidates go last
-            by_item = torch.sort(cand, dim=1, stable=True)
-            sc_i, drop_i = torch.gather(sc, 1, by_item.indices), torch.gather(drop, 1, by_item.indices)
-            rank_key = torch.where(drop_i, torch.full_like(sc_i, -float("inf")), sc_i)
-            by_score = torch.sort(rank_key, dim=1, descending=True, stable=True)
-            live = (~torch.gather(drop_i, 1, by_score.indices))[:, :k]
-            kk = min(k, kc)
-            top_items = torch.gather(by_item.values, 1, by_score.indices)[:, :kk]
-            top_scores = torch.gather(sc_i, 1, by_score.indices)[:, :kk]
-            ids[:, :kk] = torch.where(live, self.items[top_items], torch.full_like(ids[:, :kk], -1))
-            scores[:, :kk] = torch.where(live, top_scores, torch.zeros_like(top_scores))
-            lengths = live.sum(1).to(torch.int32)
-            return ids, scores, lengths
+            return _recommend_rows(self.user_factors, None, upos, self.item_factors, self.items, k, slack,
+                                   self._user_offsets if exclude_seen else None, self._key,
+                                   lambda q: "user %d" % int(_tensor(users, "users")[q]), "has seen", "exclude_seen")
+
+    # ---- new documents ------------------------------------------------------------------------------------------------------
+    def _fold_in(self, indices, doc_offsets, strengths):
+        ids, off = _ids_and_offsets(indices, doc_offsets, self.device)
+        ndocs = off.size - 1
+        with torch.cuda.device(self.device):
+            if strengths is not None:
+                strengths = _tensor(strengths, "strengths")
+                if strengths.numel() != ids.numel():
+                    raise ValueError("strengths must hold one value per id")
+            s64 = self._strengths(strengths, ids.numel())
+            docs = torch.from_numpy(np.repeat(np.arange(ndocs, dtype=np.int64), np.diff(off))).to(self.device)
+            ipos = self._positions(ids, self.items).to(torch.int64)
+            known = ipos >= 0                                            # ids unknown to the model are dropped
+            key, offsets, w = _sum_events(docs[known], ipos[known], s64[known], ndocs, self.alpha)
+            if w.numel() and not bool(torch.isfinite(w).all()):
+                raise ValueError("alpha * strength does not fit a float32")
+            out = torch.zeros(ndocs, self.rank, dtype=torch.float32, device=self.device)
+            if ndocs:
+                self._failed.zero_()
+                ops.als_solve_rows_implicit(self.item_factors, self._gram_of_items(), offsets,
+                                            (key & 0xFFFFFFFF).to(torch.int32).contiguous(), w.contiguous(), 0, ndocs,
+                                            self.reg, self.weighted_reg, out, self._failed)
+                self._raise(int(self._failed.item()), "fold-in")
+            return out, key, offsets
+
+    def fold_in(self, indices, doc_offsets, strengths=None):
+        """float32[ndocs, rank]: the user factors of NEW id documents against the fitted item factors -- one Gram (kept until
+        the item factors change) and one row-solve call, no retraining.  Ids the model does not know are dropped, a
+        repeated id adds its strengths (its count without `strengths`); a document without a known id gets zeros."""
+        return self._fold_in(indices, doc_offsets, strengths)[0]
+
+    def recommend_documents(self, indices, doc_offsets, k=500, exclude_seen=True, slack=16):
+        """``fold_in`` of the documents, then ``recommend``'s candidates, scores and order per document: (rec_ids, rec_scores,
+        rec_lengths), what ``evaluate.ranking_metrics`` takes.  The (context, context_offsets) of
+        ``evaluate.split_holdout`` go in as they are."""
+        factors, key, offsets = self._fold_in(indices, doc_offsets, None)
+        with torch.cuda.device(self.device):
+            upos = torch.arange(factors.shape[0], dtype=torch.int64, device=self.device)
+            return _recommend_rows(factors, None, upos, self.item_factors, self.items, k, slack,
+                                   offsets if exclude_seen else None, key, lambda q: "document %d" % q, "holds",
+                                   "exclude_seen")

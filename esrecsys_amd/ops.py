@@ -1961,3 +1961,61 @@ def als_predict(user_factors, item_factors, user_pos, item_pos, offset=None, tar
                               int(user_factors.shape[1]), _p(user_pos), _p(item_pos), _p(offset), _p(targets), nq, _p(out),
                               _stream()), "esr_als_predict")
     return out
+
+
+# implicit-feedback ALS: the whole-table Gram matrix and the confidence-weighted row solve (esr_als.hip)
+def als_gram_geometry():
+    """segment: esr_als_gram cuts the table into segments of that many consecutive rows, one f32 chain per entry each."""
+    segment = ctypes.c_int(0)
+    check(_lib.load().esr_als_gram_geometry(ctypes.byref(segment)), "esr_als_gram_geometry")
+    return int(segment.value)
+
+
+def als_gram(factors, out=None):
+    """float32[rank, rank] = factors^T factors of a float32 table [n, rank] (the full symmetric matrix): per segment of
+    als_gram_geometry() rows a k-ordered f32 chain, the segments added in fp64 in ascending order and rounded once."""
+    lib = _lib.load()
+    _req(factors, torch.float32, "factors")
+    if factors.dim() != 2:
+        raise ValueError("factors must be [n, rank]")
+    n, rank = factors.shape
+    if out is None:
+        out = torch.empty((rank, rank), dtype=torch.float32, device=factors.device)
+    _req(out, torch.float32, "out")
+    if tuple(out.shape) != (rank, rank):
+        raise ValueError("out %s is not [%d, %d]" % (tuple(out.shape), rank, rank))
+    ws = _ws(int(lib.esr_als_gram_workspace_bytes(int(n), int(rank))), factors.device)
+    check(lib.esr_als_gram(_p(factors), int(n), int(rank), _p(out), _p(ws), ws.numel(), _stream()), "esr_als_gram")
+    return out
+
+
+def als_solve_rows_implicit(other_factors, gram, row_offsets, cols, weights, row_begin, row_end, reg, weighted, out_factors,
+                            failed):
+    """One implicit-feedback half-sweep over the rows [row_begin, row_end): out_factors[r] solves
+    (gram + sum_k w_k y_k y_k^T + lam I) x = sum_k (1 + w_k) y_k over row r's entries.  `gram` is als_gram(other_factors);
+    row_offsets is a HOST array (numpy int64[n_rows + 1]) as in als_solve_rows; `failed` (int32[1], device) collects the
+    failure word (bit 30: a column outside the table, bit 29: a weight that is negative or not finite)."""
+    lib = _lib.load()
+    _req(other_factors, torch.float32, "other_factors"), _req(out_factors, torch.float32, "out_factors")
+    _req(gram, torch.float32, "gram")
+    _req(cols, torch.int32, "cols"), _req(weights, torch.float32, "weights"), _req(failed, torch.int32, "failed")
+    if not isinstance(row_offsets, np.ndarray) or row_offsets.dtype != np.int64 or not row_offsets.flags.c_contiguous:
+        raise TypeError("row_offsets must be a contiguous numpy int64 array (host memory)")
+    row_begin, row_end = int(row_begin), int(row_end)
+    if not 0 <= row_begin <= row_end < row_offsets.size:
+        raise ValueError("rows [%d, %d) not inside the %d rows of row_offsets" % (row_begin, row_end, row_offsets.size - 1))
+    if out_factors.shape[0] < row_end or out_factors.shape[1] != other_factors.shape[1]:
+        raise ValueError("out_factors %s does not hold rows up to %d of rank %d"
+                         % (tuple(out_factors.shape), row_end, other_factors.shape[1]))
+    n_other, rank = other_factors.shape
+    if tuple(gram.shape) != (rank, rank):
+        raise ValueError("gram %s is not [%d, %d]" % (tuple(gram.shape), rank, rank))
+    if int(row_offsets[row_end]) > cols.numel() or cols.numel() != weights.numel():
+        raise ValueError("row_offsets end at %d but there are %d cols and %d weights"
+                         % (int(row_offsets[row_end]), cols.numel(), weights.numel()))
+    nnz = int(row_offsets[row_end] - row_offsets[row_begin])
+    ws = _ws(int(lib.esr_als_solve_workspace_bytes(row_end - row_begin, nnz, int(rank))), out_factors.device)
+    check(lib.esr_als_solve_rows_implicit(_p(other_factors), int(n_other), int(rank), _p(gram), row_offsets.ctypes.data,
+                                          _p(cols), _p(weights), row_begin, row_end, float(reg), int(bool(weighted)),
+                                          _p(out_factors), _p(failed), _p(ws), ws.numel(), _stream()),
+          "esr_als_solve_rows_implicit")

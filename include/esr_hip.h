@@ -1129,6 +1129,34 @@ int esr_als_predict(const float* user_factors, int64_t nu, const float* item_fac
                     const int32_t* user_pos, const int32_t* item_pos, const double* offset, const float* targets, int64_t nq,
                     float* out, esr_stream_t stream);
 
+/* ---- Implicit-feedback ALS (Hu, Koren, Volinsky 2008; esr_als.hip) ----
+ * Every (row, column) cell is fitted: preference 1 on a row's entries and 0 elsewhere, confidence 1 + w_k on the entries and 1
+ * elsewhere.  A row with n entries solves (G + sum_k w_k y_k y_k^T + lam I) x = sum_k c_k y_k, G = Y^T Y of the other side's
+ * whole table, c_k = float(1 + w_k), lam = reg * (weighted ? n : 1).
+ *   gram        out_gram float[rank, rank] = factors^T factors of a float table [n, rank]: the full symmetric matrix (the upper
+ *               triangle holds the bits of the lower).  The table is cut into segments of `segment` consecutive rows (the
+ *               geometry query); a segment's entry is ONE k-ordered f32 fmaf chain from 0 (v_mfma_f32_32x32x2_f32, both operands
+ *               the same register), the segment partials are added per entry in fp64 in ascending segment order and rounded
+ *               once.  A function of the table alone: not of the grid, not of trailing all-zero rows; n = 0 gives zeros.  No
+ *               floating-point atomics.  workspace: the gram workspace-bytes query of (n, rank), 16-byte aligned.
+ *   solve_rows_implicit   the arguments of solve_rows with weights float[nnz] (w_k >= 0) in the place of targets and gram (device,
+ *               float[rank, rank], what gram wrote for other_factors).  Order: the entries in CSR order in chunks of the
+ *               geometry's chunk; within a chunk the lower-triangle entry (i, j), i >= j, is the k-ordered chain
+ *               acc = fmaf(float(w_k * y_k[i]), y_k[j], acc) from 0 and the right-hand side is fmaf(c_k, y_k[d], acc) over the
+ *               chunk's even entries plus the same chain over its odd ones; chunk partials are added in ascending order in f32;
+ *               then G[i][j] is added; then lam on the diagonal; then the Cholesky and the two solves of solve_rows.  The same
+ *               three row classes and the same workspace query.  A row without entries gets the zero vector.  failed: bit 30
+ *               and the count as solve_rows; a weight that is negative or not finite counts as absent and sets bit 29.
+ *               out_factors must overlap neither other_factors nor gram. */
+int esr_als_gram_geometry(int* segment);
+size_t esr_als_gram_workspace_bytes(int64_t n, int rank);
+int esr_als_gram(const float* factors, int64_t n, int rank, float* out_gram, void* workspace, size_t workspace_bytes,
+                 esr_stream_t stream);
+int esr_als_solve_rows_implicit(const float* other_factors, int64_t n_other, int rank, const float* gram,
+                                const int64_t* row_offsets, const int32_t* cols, const float* weights, int64_t row_begin,
+                                int64_t row_end, float reg, int weighted, float* out_factors, int32_t* failed, void* workspace,
+                                size_t workspace_bytes, esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
