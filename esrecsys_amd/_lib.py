@@ -263,6 +263,11 @@ SIGNATURES = {
     "esr_als_gram": (c_int, [c_f32p, c_i64, c_int, c_f32p, c_vp, c_size, c_vp]),
     "esr_als_solve_rows_implicit": (c_int, [c_f32p, c_i64, c_int, c_f32p, c_vp, c_i32p, c_f32p, c_i64, c_i64, c_f32, c_int,
                                             c_f32p, c_i32p, c_vp, c_size, c_vp]),
+    "esr_bpr_geometry": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "esr_bpr_sample": (c_int, [c_vp, c_i32p, c_i32p, c_i64, c_i64, c_i64, c_uint64, c_uint32, c_i64, c_i64, c_i32p, c_i32p,
+                               c_i32p, c_i32p, c_i32p, c_vp]),
+    "esr_bpr_fwd_bwd": (c_int, [c_f32p, c_i64, c_f32p, c_i64, c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i64, c_f32, c_f32p,
+                                c_f32p, c_f32p, c_i32p, c_vp]),
 }
 
 

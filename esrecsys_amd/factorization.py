@@ -27,7 +27,9 @@ over those outputs and the factor tables.
 
 Implicit feedback.  ``ImplicitALS`` (below) is the confidence-weighted model of Hu, Koren and Volinsky for occurrence data:
 every cell is fitted, a half-sweep is one ``ops.als_gram`` and one ``ops.als_solve_rows_implicit``, and new documents are
-folded in by the same call (``fold_in``, ``recommend_documents``).
+folded in by the same call (``fold_in``, ``recommend_documents``).  ``BPR`` (further below) is the model of the same family
+that is trained on the ranking itself: Bayesian Personalised Ranking over triples sampled on the device (esr_bpr.hip), updated
+by the row-sparse engine.
 """
 import math
 
@@ -561,3 +563,164 @@ class ImplicitALS:
             return _recommend_rows(factors, None, upos, self.item_factors, self.items, k, slack,
                                    offsets if exclude_seen else None, key, lambda q: "document %d" % q, "holds",
                                    "exclude_seen")
+
+
+# ---- Bayesian Personalised Ranking --------------------------------------------------------------------------------------
+OPTIMIZERS = ("adagrad", "sgd")
+ADAGRAD_INIT = 0.1           # optax.adagrad's initial accumulator value, as everywhere in this package
+FIT_GROUP = 64               # steps per sampler launch of BPR.fit
+
+
+class BPR:
+    """Matrix factorisation trained on the ranking itself (Rendle, Freudenthaler, Gantner, Schmidt-Thieme, UAI 2009).
+
+        model = BPR.from_documents(indices, doc_offsets, rank=64)       # user = document, a repeated id is one seen pair
+        losses = model.fit(steps=2000)                                  # the mean loss of every step
+        rec_ids, rec_scores, rec_lengths = model.recommend(users, k=500)     # straight into evaluate.ranking_metrics
+
+    Step.  ``batch`` triples (user u, seen item i, unseen item j) are drawn on the device (``ops.bpr_sample``: Philox keyed
+    by ``seed``, a function of (seed, step, slot) and the seen pairs alone; a triple whose 15 candidates were all seen is
+    dropped: ``valid = 0``).  The objective of a step is the sum over its valid triples of ``softplus(-d) + (reg / 2)
+    (|x_u|^2 + |y_i|^2 + |y_j|^2)``, ``d = x_u . y_i - x_u . y_j``.  ``ops.bpr_fwd_bwd`` writes one gradient row per
+    occurrence; rows of a repeated id add (the engine's segment sum in a fixed order: Rendle's per-triple SGD taken as a
+    minibatch) and the row-sparse engine applies Adagrad (``ops.sparse_adagrad_multi`` over both tables at once) or SGD
+    (``ops.sparse_sgd``, users then items).  The fit is a function of the inputs and the seed.
+
+    ``users`` / ``items``: int32 ascending ids; ``user_factors`` / ``item_factors``: float32 [nu, rank] / [ni, rank], both
+    ``randn * init_scale`` from the seeded CPU generator (users first); ``step``: the steps taken so far."""
+
+    def __init__(self, user, item, rank=64, reg=0.01, lr=0.05, optimizer="adagrad", batch=65536, seed=0, init_scale=None,
+                 device=None):
+        rank = int(rank)
+        _, top, mult = ops.bpr_geometry()
+        if not mult <= rank <= top or rank % mult:
+            raise ValueError("rank = %d is not a multiple of %d in [%d, %d]" % (rank, mult, mult, top))
+        reg, lr = float(reg), float(lr)
+        f32_max = float(np.finfo(np.float32).max)
+        if not (math.isfinite(reg) and 0.0 <= reg <= f32_max):
+            raise ValueError("reg = %r must be finite (as a float32) and not negative" % (reg,))
+        if not (math.isfinite(lr) and abs(lr) <= f32_max):
+            raise ValueError("lr = %r must be finite (as a float32)" % (lr,))
+        if optimizer not in OPTIMIZERS:
+            raise ValueError("optimizer must be 'adagrad' or 'sgd', got %r" % (optimizer,))
+        batch = int(batch)
+        if not 1 <= batch <= 2 ** 31 - 1:
+            raise ValueError("batch = %d outside [1, 2^31 - 1]" % batch)
+        user, item = _tensor(user, "user"), _tensor(item, "item")
+        _same_length("user and item", user, item)
+        if user.numel() == 0:
+            raise ValueError("no (user, item) pair: BPR needs at least one seen pair")
+        if user.dtype.is_floating_point or item.dtype.is_floating_point:
+            raise TypeError("user and item must be integer arrays")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise TypeError("device must be a CUDA/ROCm device (no CPU fallback exists)")
+        self.rank, self.reg, self.lr, self.optimizer, self.batch, self.seed = rank, reg, lr, optimizer, batch, int(seed)
+        self.init_scale = float(rank) ** -0.5 if init_scale is None else float(init_scale)
+        self.step = 0
+        dev = self.device
+        with torch.cuda.device(dev):
+            user, item = user.to(dev).to(torch.int64), item.to(dev).to(torch.int64)
+            if int(user.min()) < 0 or int(item.min()) < 0 or int(user.max()) >= 2 ** 31 - 1 or int(item.max()) >= 2 ** 31 - 1:
+                raise ValueError("user and item ids must lie in [0, 2^31 - 1)")
+            users, upos = torch.unique(user, return_inverse=True)
+            items, ipos = torch.unique(item, return_inverse=True)
+            nu, ni = int(users.numel()), int(items.numel())
+            self.users, self.items = users.to(torch.int32).contiguous(), items.to(torch.int32).contiguous()
+            key = torch.unique((upos << 32) | ipos)                     # repeated events collapse to one seen pair
+            rows = torch.bincount(key >> 32, minlength=nu)
+            self._user_offsets = np.ascontiguousarray(
+                np.concatenate([[0], np.cumsum(rows.cpu().numpy().astype(np.int64))]).astype(np.int64))
+            self._key = key                                             # upos << 32 | ipos, ascending: the seen pairs
+            self._row_upos = (key >> 32).to(torch.int32).contiguous()
+            self._row_ipos = (key & 0xFFFFFFFF).to(torch.int32).contiguous()
+            self._offsets_dev = torch.from_numpy(self._user_offsets).to(dev)    # the sampler reads the CSR on the device
+            gen = torch.Generator(device="cpu").manual_seed(self.seed)
+            self.user_factors = (torch.randn(nu, rank, generator=gen) * self.init_scale).to(dev).contiguous()
+            self.item_factors = (torch.randn(ni, rank, generator=gen) * self.init_scale).to(dev).contiguous()
+            self.user_accum = torch.full((nu, rank), ADAGRAD_INIT, dtype=torch.float32, device=dev)
+            self.item_accum = torch.full((ni, rank), ADAGRAD_INIT, dtype=torch.float32, device=dev)
+            self._failed = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    @classmethod
+    def from_documents(cls, indices, doc_offsets, **kw):
+        """The model of id documents ``indices[doc_offsets[d]:doc_offsets[d + 1]]``: the user is the document number, every
+        distinct id of d one seen pair."""
+        ids, off = _ids_and_offsets(indices, doc_offsets, torch.device("cpu"))
+        docs = torch.from_numpy(np.repeat(np.arange(off.size - 1, dtype=np.int64), np.diff(off)))
+        return cls(docs, ids, **kw)
+
+    nnz = property(lambda self: int(self._key.numel()))
+
+    # ---- training -------------------------------------------------------------------------------------------------------
+    def sample(self, K, step0=None, seed=None):
+        """(u, i, j, valid) int32 [K, batch] and dropped int32[K]: the triples of the global steps step0 .. step0 + K - 1
+        (``step0`` = the next step to take when None) as positions into ``users`` / ``items``."""
+        with torch.cuda.device(self.device):
+            return ops.bpr_sample(self._offsets_dev, self._row_upos, self._row_ipos, self.users.numel(), self.items.numel(),
+                                  self.seed if seed is None else int(seed), self.step if step0 is None else int(step0),
+                                  int(K), self.batch)
+
+    def _update(self, u, i, j, grads):
+        nu, ni, B = int(self.users.numel()), int(self.items.numel()), u.numel()
+        if self.optimizer == "adagrad":
+            sorted_ids, perm = ops.segment_sort_multi([u, i, j], [0, nu, nu], nu + ni)
+            ops.sparse_adagrad_multi([self.user_factors, self.item_factors], [self.user_accum, self.item_accum],
+                                     [0, nu, nu + ni], sorted_ids, perm, grads, self.lr)
+        else:
+            sorted_ids, perm = ops.segment_sort(u, nu)
+            ops.sparse_sgd(self.user_factors, sorted_ids, perm, grads[:B], self.lr)
+            sorted_ids, perm = ops.segment_sort(ops.concat_offset_ids([i, j], [0, 0]), ni)
+            ops.sparse_sgd(self.item_factors, sorted_ids, perm, grads[B:], self.lr)
+
+    def train_steps(self, K):
+        """K steps: one sampler launch, then per step the forward / backward, the sort and the update.  Returns the mean
+        loss over the valid triples of every step (an fp64 sum of the per-triple losses divided on the host; NaN for a step
+        without a valid triple).  Raises ``FactorizationError`` when a kernel met a position outside its table."""
+        K = int(K)
+        if K < 1:
+            raise ValueError("K = %d below 1" % K)
+        with torch.cuda.device(self.device):
+            u, i, j, valid, dropped = self.sample(K)
+            self._failed.zero_()
+            sums = torch.empty(K, dtype=torch.float64, device=self.device)
+            for k in range(K):
+                loss_t, _, grads = ops.bpr_fwd_bwd(self.user_factors, self.item_factors, u[k], i[k], j[k], valid[k], self.reg,
+                                                   failed=self._failed)
+                self._update(u[k], i[k], j[k], grads)
+                sums[k] = loss_t.to(torch.float64).sum()
+            self.step += K
+            word = int(self._failed.item())
+            sums, kept = sums.cpu().numpy(), self.batch - dropped.cpu().numpy().astype(np.int64)
+        if word & FAIL_BAD_POSITION:
+            raise FactorizationError("a BPR step met a position outside its table (bit 30)")
+        return [float(s) / int(n) if n else float("nan") for s, n in zip(sums, kept)]
+
+    def fit(self, steps):
+        """`steps` steps in groups of 64 (one sampler launch per group); returns every step's mean loss."""
+        losses, steps = [], int(steps)
+        for a in range(0, steps, FIT_GROUP):
+            losses += self.train_steps(min(FIT_GROUP, steps - a))
+        return losses
+
+    def auc(self, K=1, seed=None):
+        """The fraction of K * batch sampled triples (valid ones) that the model orders correctly, ``d > 0``; a tie counts
+        half.  The triples are steps 0 .. K - 1 of `seed` (``self.seed + 1`` when None: not a training stream, and the same
+        triples before and after training).  NaN when no triple is valid."""
+        with torch.cuda.device(self.device):
+            u, i, j, valid, _ = self.sample(int(K), step0=0, seed=self.seed + 1 if seed is None else seed)
+            self._failed.zero_()
+            _, d, _ = ops.bpr_fwd_bwd(self.user_factors, self.item_factors, u.reshape(-1), i.reshape(-1), j.reshape(-1),
+                                      valid.reshape(-1), self.reg, want_grads=False, want_diff=True, failed=self._failed)
+            ok = valid.reshape(-1) != 0
+            n = int(ok.sum())
+            wins, ties = int(((d > 0) & ok).sum()), int(((d == 0) & ok).sum())
+            word = int(self._failed.item())
+        if word & FAIL_BAD_POSITION:
+            raise FactorizationError("auc met a position outside its table (bit 30)")
+        return (wins + 0.5 * ties) / n if n else float("nan")
+
+    # ---- scores and recommendation ----------------------------------------------------------------------------------------
+    _positions = RatingsALS._positions
+    score = ImplicitALS.score
+    recommend = ImplicitALS.recommend

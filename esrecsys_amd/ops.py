@@ -2019,3 +2019,72 @@ def als_solve_rows_implicit(other_factors, gram, row_offsets, cols, weights, row
                                           _p(cols), _p(weights), row_begin, row_end, float(reg), int(bool(weighted)),
                                           _p(out_factors), _p(failed), _p(ws), ws.numel(), _stream()),
           "esr_als_solve_rows_implicit")
+
+
+# ---------------------------------------------------------------------------------------------
+# Bayesian Personalised Ranking (esr_bpr.hip): the triple sampler and the fused logistic forward / backward
+def bpr_geometry():
+    """(max_tries, max_rank, rank_multiple): the negative candidates the sampler tries per triple; bpr_fwd_bwd takes a rank
+    that is a multiple of rank_multiple and at most max_rank."""
+    tries, rank, mult = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.load().esr_bpr_geometry(ctypes.byref(tries), ctypes.byref(rank), ctypes.byref(mult)), "esr_bpr_geometry")
+    return int(tries.value), int(rank.value), int(mult.value)
+
+
+def bpr_sample(row_offsets, row_upos, row_ipos, nu, ni, seed, step0, K, B):
+    """K steps of B (user, seen item, unseen item) triples drawn on the device: (u, i, j, valid) int32 [K, B] -- row k is
+    global step step0 + k (mod 2^32) -- and dropped int32[K], the count of valid == 0 per step.  The seen pairs are a CSR by
+    user on the DEVICE: row_offsets int64[nu + 1], row_upos / row_ipos int32[nnz], item positions ascending within a row.
+    The rule is esr_bpr_sample.h's: a triple is a function of (seed, step, slot, CSR) alone; the multiply-high draws are
+    biased by at most nnz / 2^32 (the pair) and ni / 2^32 (a candidate) relative."""
+    lib = _lib.load()
+    _req(row_offsets, torch.int64, "row_offsets"), _req(row_upos, torch.int32, "row_upos")
+    _req(row_ipos, torch.int32, "row_ipos")
+    nu, ni, K, B, nnz = int(nu), int(ni), int(K), int(B), row_upos.numel()
+    if row_ipos.numel() != nnz or row_offsets.numel() != nu + 1:
+        raise ValueError("bpr_sample: row_offsets holds %d entries for nu = %d, row_upos %d and row_ipos %d pairs"
+                         % (row_offsets.numel(), nu, nnz, row_ipos.numel()))
+    lim = 2 ** 31 - 1
+    if not (1 <= nnz <= lim and 1 <= ni <= lim and 1 <= nu <= lim and 1 <= K <= lim and 1 <= B <= lim):
+        raise ValueError("bpr_sample: nu=%d ni=%d nnz=%d K=%d B=%d (each in [1, 2^31 - 1])" % (nu, ni, nnz, K, B))
+    out = torch.empty((4, K, B), dtype=torch.int32, device=row_upos.device)
+    dropped = torch.empty(K, dtype=torch.int32, device=row_upos.device)
+    check(lib.esr_bpr_sample(_p(row_offsets), _p(row_upos), _p(row_ipos), nu, ni, nnz, int(seed) & (2 ** 64 - 1),
+                             int(step0) & 0xFFFFFFFF, K, B, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _p(dropped),
+                             _stream()), "esr_bpr_sample")
+    return out[0], out[1], out[2], out[3], dropped
+
+
+def bpr_fwd_bwd(user_table, item_table, u, i, j, valid, reg, want_grads=True, want_diff=False, failed=None):
+    """(loss_t float32[B], diff_t float32[B] or None, grads float32[3 B, D] or None) of the triples (u, i, j) int32[B]:
+    d = x_u . (y_i - y_j), loss_t = softplus(-d), diff_t = d, and the gradient rows [user ; positive ; negative] in
+    occurrence order with the L2 term reg * row (include/esr_hip.h).  valid int32[B] or None (all valid): a triple with
+    valid = 0 gives zeros.  `failed` (int32[1], device; a scratch word when None) gets bit 30 when an id lies outside its
+    table -- that triple gives zeros too; the caller zeroes and reads it."""
+    lib = _lib.load()
+    _req(user_table, torch.float32, "user_table"), _req(item_table, torch.float32, "item_table")
+    _req(u, torch.int32, "u"), _req(i, torch.int32, "i"), _req(j, torch.int32, "j")
+    if user_table.dim() != 2 or item_table.dim() != 2 or user_table.shape[1] != item_table.shape[1]:
+        raise ValueError("user_table and item_table must be [n, rank] of one rank")
+    B, D = u.numel(), int(user_table.shape[1])
+    if i.numel() != B or j.numel() != B:
+        raise ValueError("u, i and j must have one length")
+    if valid is not None:
+        _req(valid, torch.int32, "valid")
+        if valid.numel() != B:
+            raise ValueError("valid must hold one entry per triple")
+    _, max_rank, mult = bpr_geometry()
+    if D % mult or not mult <= D <= max_rank:
+        raise ValueError("rank = %d is not a multiple of %d in [%d, %d]" % (D, mult, mult, max_rank))
+    dev = user_table.device
+    if failed is None:
+        failed = torch.zeros(1, dtype=torch.int32, device=dev)
+    _req(failed, torch.int32, "failed")
+    loss_t = torch.empty(B, dtype=torch.float32, device=dev)
+    diff_t = torch.empty(B, dtype=torch.float32, device=dev) if want_diff else None
+    grads = torch.empty((3 * B, D), dtype=torch.float32, device=dev) if want_grads else None
+    if B:
+        check(lib.esr_bpr_fwd_bwd(_p(user_table), user_table.shape[0], _p(item_table), item_table.shape[0], D, _p(u), _p(i),
+                                  _p(j), _p(valid), B, float(reg), _p(loss_t), _p(diff_t), _p(grads), _p(failed), _stream()),
+              "esr_bpr_fwd_bwd")
+    return loss_t, diff_t, grads

@@ -1157,6 +1157,35 @@ int esr_als_solve_rows_implicit(const float* other_factors, int64_t n_other, int
                                 int64_t row_end, float reg, int weighted, float* out_factors, int32_t* failed, void* workspace,
                                 size_t workspace_bytes, esr_stream_t stream);
 
+/* ---- Bayesian Personalised Ranking (Rendle et al., UAI 2009; esr_bpr.hip) ----
+ * -log sigmoid(x_u . y_i - x_u . y_j) over sampled (user, seen item, unseen item) triples.  No workspace.
+ *   geometry    max_tries = the negative candidates tried per triple (15); the fwd_bwd kernel takes D that is a multiple of
+ *               rank_multiple (4) and at most max_rank (128).
+ *   sample      K steps of B triples in one launch, outputs int32 [K, B] row-major, row k = global step step0 + k (mod
+ *               2^32).  The seen pairs are a CSR by user: row_offsets int64[nu + 1], row_upos / row_ipos int32[nnz], item
+ *               positions ascending within a row, pairs distinct.  The rule is esr_bpr_sample.h's bpr_sample_triple: Philox
+ *               block b = philox4x32_10((t, s, b, 0), (seed low, seed high)); word 0 of block 0 picks the pair by
+ *               multiply-high; the next 15 words are the negative candidates in order, the first one not in the user's row
+ *               (binary search) wins; if all are seen the last one is written with valid = 0.  A triple is a function of
+ *               (seed, s, t, the CSR) alone.  dropped int32[K] = the exact count of valid == 0 per step (zeroed by the call;
+ *               integer atomics).  1 <= nnz, ni, nu, K, B <= 2^31 - 1.
+ *   fwd_bwd     per triple t with x = user_table[u[t]], yi = item_table[i[t]], yj = item_table[j[t]] (f32 tables):
+ *               d = sum_k x[k] (yi[k] - yj[k]) in f32 in the order esr_bpr.hip states (a function of D alone),
+ *               loss_t[t] = max(-d, 0) + log1pf(expf(-|d|)), diff_t[t] = d (diff_t may be null), g = sigmoid(-d), and into
+ *               grads float[3 B, D] = [user rows ; positive rows ; negative rows] in occurrence order
+ *                 g_u = -g (yi - yj) + reg x,  g_i = -g x + reg yi,  g_j = g x + reg yj.
+ *               grads null: forward only.  valid int32[B] or null (all valid): a triple with valid = 0 writes three zero
+ *               rows, loss_t = 0 and diff_t = 0 and reads no row.  A u, i or j outside its table does the same and sets bit
+ *               30 of *failed (the caller zeroes and reads it).  No reduction across triples: an output depends on its own
+ *               triple, reg and D only.  Tables and grads 16-byte aligned. */
+int esr_bpr_geometry(int* max_tries, int* max_rank, int* rank_multiple);
+int esr_bpr_sample(const int64_t* row_offsets, const int32_t* row_upos, const int32_t* row_ipos, int64_t nu, int64_t ni,
+                   int64_t nnz, uint64_t seed, uint32_t step0, int64_t K, int64_t B, int32_t* out_u, int32_t* out_i,
+                   int32_t* out_j, int32_t* out_valid, int32_t* dropped, esr_stream_t stream);
+int esr_bpr_fwd_bwd(const float* user_table, int64_t nu, const float* item_table, int64_t ni, int D, const int32_t* u,
+                    const int32_t* i, const int32_t* j, const int32_t* valid, int64_t B, float reg, float* loss_t,
+                    float* diff_t, float* grads, int32_t* failed, esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
