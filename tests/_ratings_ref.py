@@ -68,6 +68,38 @@ def ref_similarity(sums, min_overlap=1, min_similarity=None):
             flat)
 
 
+def vec_similarity(user, item, dev, min_overlap=1, min_similarity=None):
+    """``ref_similarity(ref_sums(user, item, dev), min_overlap, min_similarity)`` restated with arrays, for inputs of
+    half a million pairs: per item the raters ascending and ``np.triu_indices`` over them, the pairs of all items reduced
+    by their 64-bit key ``a << 32 | b`` in int64 (the sums stay below 2^53, the builder's own bound), and ``ref_sim``'s
+    three roundings taken on whole arrays.  Pinned to the loop version, array for array, by test_ratings_ref.py."""
+    user, item, dev = (np.asarray(x, np.int64) for x in (user, item, dev))
+    order = np.lexsort((user, item))
+    user, item, dev = user[order], item[order], dev[order]
+    cut = np.flatnonzero(np.diff(item)) + 1
+    key, P, Qa, Qb = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for a, b in zip(np.concatenate([[0], cut]), np.concatenate([cut, [item.size]])):
+        u, d = user[a:b], dev[a:b]
+        assert (np.diff(u) > 0).all(), "a (user, item) occurs twice"
+        p, q = np.triu_indices(u.size, 1)
+        key.append((u[p] << 32) | u[q]), P.append(d[p] * d[q]), Qa.append(d[p] * d[p]), Qb.append(d[q] * d[q])
+    key, P, Qa, Qb = (np.concatenate(x) for x in (key, P, Qa, Qb))
+    if key.size == 0:
+        return ref_similarity({}, min_overlap, min_similarity)
+    keys, inverse, n = np.unique(key, return_inverse=True, return_counts=True)
+    by_key = np.argsort(inverse, kind="stable")
+    first = np.concatenate([[0], np.cumsum(n)[:-1]])
+    P, Qa, Qb = (np.add.reduceat(x[by_key], first) for x in (P, Qa, Qb))
+    flat = (Qa == 0) | (Qb == 0)
+    with np.errstate(all="ignore"):
+        sim = (P.astype(np.float64) / (np.sqrt(Qa.astype(np.float64)) * np.sqrt(Qb.astype(np.float64)))).astype(np.float32)
+    keep = ~flat & (n >= min_overlap)
+    if min_similarity is not None:
+        keep &= ~(sim <= np.float32(min_similarity))
+    return ((keys[keep] >> 32).astype(np.int32), (keys[keep] & 0xFFFFFFFF).astype(np.int32), sim[keep],
+            n[keep].astype(np.int32), int(flat.sum()))
+
+
 class RefUserKnn:
     """table = (ids, neighbours, scores, counts, lengths) as tests/_neighbours_ref.ref_neighbours returns it."""
 

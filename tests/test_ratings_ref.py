@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from _neighbours_ref import ref_neighbours
-from _ratings_ref import RefUserKnn, ref_deviations, ref_latest, ref_sim, ref_similarity, ref_sums
+from _ratings_ref import RefUserKnn, ref_deviations, ref_latest, ref_sim, ref_similarity, ref_sums, vec_similarity
 from esrecsys_amd import ratings as rt
 
 # 3 users x 4 items.  Means: user 1 -> 4, user 2 -> 3.5, user 3 -> 3.
@@ -63,6 +63,29 @@ def test_a_flat_user_is_dropped_and_counted():
     sums = ref_sums([1, 1, 2, 2], [10, 20, 10, 20], [0, 0, 3, -3])
     assert sums == {(1, 2): [2, 0, 0, 18]}
     assert ref_similarity(sums)[4] == 1 and ref_similarity(sums)[0].size == 0
+
+
+def test_the_vectorised_similarity_equals_the_loop_version():
+    """``vec_similarity`` (the oracle of test_gpu_ratings_scale.py) against ``ref_similarity(ref_sums(...))`` on the
+    rows of test_gpu_ratings.geometry(): every array equal, the float32 similarities through their bits, under every
+    filter that the GPU tests use; and on the inputs that end in no pair at all."""
+    from test_gpu_ratings import geometry          # host arrays; the tile size comes from the library, no device
+    user, item, dev = geometry()
+    kept = set()
+    for min_overlap, min_similarity in ((1, None), (2, None), (1, 0.0), (1, 0.25), (1, -1.0), (2, 0.0), (3, None)):
+        want = ref_similarity(ref_sums(user, item, dev), min_overlap, min_similarity)
+        got = vec_similarity(user, item, dev, min_overlap, min_similarity)
+        for g, w in zip(got[:4], want[:4]):
+            assert g.dtype == w.dtype and np.array_equal(g, w)
+        assert np.array_equal(got[2].view(np.uint32), want[2].view(np.uint32))
+        assert got[4] == want[4] == 2 and isinstance(got[4], int)
+        kept.add(want[0].size)
+    assert len(kept) >= 5 and min(kept) < max(kept) // 2             # the filters cut differently, and deep
+    for rows in (([], [], []), ([1, 2], [7, 8], [3, 4]), ([1, 2], [7, 7], [0, 5])):        # nothing, no pair, one flat pair
+        got, want = vec_similarity(*rows), ref_similarity(ref_sums(*rows))
+        assert all(g.dtype == w.dtype and g.size == w.size == 0 for g, w in zip(got[:4], want[:4])) and got[4] == want[4]
+    with pytest.raises(AssertionError, match="occurs twice"):
+        vec_similarity([1, 1], [7, 7], [3, 4])
 
 
 def test_latest_ratings_against_the_oracle():
