@@ -268,6 +268,10 @@ SIGNATURES = {
                                c_i32p, c_i32p, c_i32p, c_vp]),
     "esr_bpr_fwd_bwd": (c_int, [c_f32p, c_i64, c_f32p, c_i64, c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i64, c_f32, c_f32p,
                                 c_f32p, c_f32p, c_i32p, c_vp]),
+    "esr_warp_geometry": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "esr_warp_step": (c_int, [c_f32p, c_i64, c_f32p, c_i64, c_int, c_vp, c_i32p, c_i32p, c_i64, c_f32p, c_uint64, c_uint32,
+                              c_i64, c_int, c_f32, c_f32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p,
+                              c_i32p, c_vp]),
 }
 
 

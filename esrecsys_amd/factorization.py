@@ -29,7 +29,8 @@ Implicit feedback.  ``ImplicitALS`` (below) is the confidence-weighted model of 
 every cell is fitted, a half-sweep is one ``ops.als_gram`` and one ``ops.als_solve_rows_implicit``, and new documents are
 folded in by the same call (``fold_in``, ``recommend_documents``).  ``BPR`` (further below) is the model of the same family
 that is trained on the ranking itself: Bayesian Personalised Ranking over triples sampled on the device (esr_bpr.hip), updated
-by the row-sparse engine.
+by the row-sparse engine; ``WARP`` (last) is BPR's model trained with the rank-weighted margin loss, its negatives searched
+for on the device by one fused call (esr_warp.hip).
 """
 import math
 
@@ -724,3 +725,101 @@ class BPR:
     _positions = RatingsALS._positions
     score = ImplicitALS.score
     recommend = ImplicitALS.recommend
+
+
+# ---- WARP ---------------------------------------------------------------------------------------------------------------
+RANK_WEIGHTS = ("harmonic", "log1p")
+
+
+def warp_rank_weight(rank_weight, ni):
+    """float32[ni + 1] on the host: entry r is the step weight of an estimated rank r.  "harmonic": H_r = sum_{k <= r} 1 / k
+    (WSABIE's), an fp64 cumulative sum rounded once, entry 0 = 0; "log1p": ln(1 + r); or an array of ni + 1 finite,
+    non-negative values taken as they are."""
+    ni = int(ni)
+    if isinstance(rank_weight, str):
+        if rank_weight not in RANK_WEIGHTS:
+            raise ValueError("rank_weight must be 'harmonic', 'log1p' or an array of ni + 1 values, got %r" % (rank_weight,))
+        r = np.arange(ni + 1, dtype=np.float64)
+        if rank_weight == "harmonic":
+            table = np.concatenate([[0.0], np.cumsum(1.0 / r[1:])])
+        else:
+            table = np.log1p(r)
+        return table.astype(np.float32)
+    table = np.asarray(rank_weight.detach().cpu().numpy() if isinstance(rank_weight, torch.Tensor) else rank_weight, np.float64)
+    if table.shape != (ni + 1,):
+        raise ValueError("rank_weight holds %s values, not ni + 1 = %d" % (table.shape, ni + 1))
+    if not np.isfinite(table).all() or (table < 0).any() or (table > float(np.finfo(np.float32).max)).any():
+        raise ValueError("rank_weight must hold finite (as float32), non-negative values")
+    return table.astype(np.float32)
+
+
+class WARP(BPR):
+    """Matrix factorisation trained by WARP, the weighted approximate-rank pairwise loss (Weston, Bengio, Usunier, "WSABIE",
+    IJCAI 2011): BPR's model, state and update, with the negative searched for instead of drawn.
+
+        model = WARP.from_documents(indices, doc_offsets, rank=64, max_trials=32)
+        losses = model.fit(steps=2000)                      # model.mean_trials: how hard negatives have become, per step
+        rec_ids, rec_scores, rec_lengths = model.recommend(users, k=500)
+
+    Step.  Per slot a seen pair (u, i) and up to ``max_trials`` candidates come from BPR's Philox stream; the first unseen
+    candidate j with ``x_u . y_i - x_u . y_j < margin`` is the negative; with N unseen candidates walked the positive's rank
+    is estimated as ``r = max(1, (ni - len_u) // N)`` and the slot's objective is ``rank_weight[r] * (margin - d) + (reg / 2)
+    (|x_u|^2 + |y_i|^2 + |y_j|^2)``.  A slot whose candidates all keep the margin is dropped (``valid = 0``).  One
+    ``ops.warp_step`` call does all of it (esr_warp.hip; the rule is esr_warp_sample.h's); the update is ``BPR``'s.
+
+    The constructor arguments, ``users`` / ``items``, the factors, the accumulators and ``step`` are ``BPR``'s; ``auc``
+    (over BPR's uniformly drawn triples), ``score`` and ``recommend`` are inherited."""
+
+    def __init__(self, user, item, rank=64, reg=0.01, lr=0.05, optimizer="adagrad", batch=65536, seed=0, init_scale=None,
+                 device=None, max_trials=32, margin=1.0, rank_weight="harmonic"):
+        top, _, _ = ops.warp_geometry()
+        max_trials, margin = int(max_trials), float(margin)
+        if not 1 <= max_trials <= top:
+            raise ValueError("max_trials = %d outside [1, %d]" % (max_trials, top))
+        if not (math.isfinite(margin) and abs(margin) <= float(np.finfo(np.float32).max)):
+            raise ValueError("margin = %r must be finite (as a float32)" % (margin,))
+        if isinstance(rank_weight, str) and rank_weight not in RANK_WEIGHTS:
+            raise ValueError("rank_weight must be 'harmonic', 'log1p' or an array of ni + 1 values, got %r" % (rank_weight,))
+        super().__init__(user, item, rank=rank, reg=reg, lr=lr, optimizer=optimizer, batch=batch, seed=seed,
+                         init_scale=init_scale, device=device)
+        self.max_trials, self.margin = max_trials, margin
+        self.rank_weight = torch.from_numpy(warp_rank_weight(rank_weight, self.items.numel())).to(self.device)
+        self.mean_trials = []
+
+    def _warp_step(self, step, want_grads):
+        return ops.warp_step(self.user_factors, self.item_factors, self._offsets_dev, self._row_upos, self._row_ipos,
+                             self.rank_weight, self.seed, step, self.batch, self.max_trials, self.margin, self.reg,
+                             want_grads=want_grads, failed=self._failed)
+
+    def step_triples(self, step=None):
+        """(u, i, j, valid, trials) int32[batch] of global step `step` (the next step to take when None) against the
+        factors as they stand: forward only, nothing is updated."""
+        with torch.cuda.device(self.device):
+            self._failed.zero_()
+            out = self._warp_step(self.step if step is None else int(step), False)
+            if int(self._failed.item()) & FAIL_BAD_POSITION:
+                raise FactorizationError("a WARP step met a position outside its table (bit 30)")
+        return out[:5]
+
+    def train_steps(self, K):
+        """K steps: per step one ``ops.warp_step`` call, the sort and the update.  Returns the mean loss over the valid slots
+        of every step (an fp64 sum of the per-slot losses divided on the host; NaN for a step without a valid slot) and
+        appends every step's mean ``trials`` to ``mean_trials``.  Raises ``FactorizationError`` when the kernel met a
+        position outside its table."""
+        K = int(K)
+        if K < 1:
+            raise ValueError("K = %d below 1" % K)
+        with torch.cuda.device(self.device):
+            self._failed.zero_()
+            sums = torch.empty((3, K), dtype=torch.float64, device=self.device)      # loss, valid slots, trials
+            for k in range(K):
+                u, i, j, valid, trials, loss_t, _, grads = self._warp_step(self.step + k, True)
+                self._update(u, i, j, grads)
+                sums[0, k], sums[1, k], sums[2, k] = loss_t.to(torch.float64).sum(), valid.sum(), trials.sum()
+            self.step += K
+            word = int(self._failed.item())
+            sums = sums.cpu().numpy()
+        if word & FAIL_BAD_POSITION:
+            raise FactorizationError("a WARP step met a position outside its table (bit 30)")
+        self.mean_trials += [float(n) / self.batch for n in sums[2]]
+        return [float(s) / int(n) if n else float("nan") for s, n in zip(sums[0], sums[1])]

@@ -2088,3 +2088,57 @@ def bpr_fwd_bwd(user_table, item_table, u, i, j, valid, reg, want_grads=True, wa
                                   _p(j), _p(valid), B, float(reg), _p(loss_t), _p(diff_t), _p(grads), _p(failed), _stream()),
               "esr_bpr_fwd_bwd")
     return loss_t, diff_t, grads
+
+
+# ---------------------------------------------------------------------------------------------
+# WARP (esr_warp.hip): the fused sample / score / search / weight / gradient step
+def warp_geometry():
+    """(max_trials, max_rank, rank_multiple): the most candidates one search may walk; warp_step takes a rank that is a
+    multiple of rank_multiple and at most max_rank."""
+    trials, rank, mult = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.load().esr_warp_geometry(ctypes.byref(trials), ctypes.byref(rank), ctypes.byref(mult)), "esr_warp_geometry")
+    return int(trials.value), int(rank.value), int(mult.value)
+
+
+def warp_step(user_factors, item_factors, offsets, row_upos, row_ipos, rank_weight, seed, step, B, max_trials, margin, reg,
+              want_grads=True, want_diff=False, failed=None):
+    """One WARP step of B slots in one launch: (u, i, j, valid, trials) int32[B], loss_t float32[B], diff float32[B] or None
+    and grads float32[3 B, D] or None.  The seen pairs are bpr_sample's CSR on the DEVICE (offsets int64[nu + 1], row_upos /
+    row_ipos int32[nnz]); rank_weight is float32[ni + 1].  The rule is esr_warp_sample.h's: the pair and the candidates
+    come from bpr_sample's Philox stream; the first unseen candidate within max_trials whose d = x_u . y_i - x_u . y_j is
+    below margin is the negative, trials counts the unseen candidates walked, w = rank_weight[max(1, (ni - len_u) //
+    trials)], loss_t = w (margin - d) and grads = [user ; positive ; negative] rows with the L2 term reg * row.  A slot
+    without a violating candidate has valid = 0 and zeros.  `failed` (int32[1], device; a scratch word when None) gets
+    bit 30 when an item position lies outside the table; the caller zeroes and reads it."""
+    lib = _lib.load()
+    _req(user_factors, torch.float32, "user_factors"), _req(item_factors, torch.float32, "item_factors")
+    _req(offsets, torch.int64, "offsets"), _req(row_upos, torch.int32, "row_upos"), _req(row_ipos, torch.int32, "row_ipos")
+    _req(rank_weight, torch.float32, "rank_weight")
+    if user_factors.dim() != 2 or item_factors.dim() != 2 or user_factors.shape[1] != item_factors.shape[1]:
+        raise ValueError("user_factors and item_factors must be [n, rank] of one rank")
+    nu, ni, D, nnz, B = int(user_factors.shape[0]), int(item_factors.shape[0]), int(user_factors.shape[1]), row_upos.numel(), int(B)
+    if row_ipos.numel() != nnz or offsets.numel() != nu + 1 or rank_weight.numel() != ni + 1:
+        raise ValueError("warp_step: offsets holds %d entries for nu = %d, row_upos %d and row_ipos %d pairs, rank_weight %d "
+                         "entries for ni = %d" % (offsets.numel(), nu, nnz, row_ipos.numel(), rank_weight.numel(), ni))
+    lim = 2 ** 31 - 1
+    if not (1 <= nnz <= lim and 1 <= ni <= lim and 1 <= nu <= lim and 1 <= B <= lim):
+        raise ValueError("warp_step: nu=%d ni=%d nnz=%d B=%d (each in [1, 2^31 - 1])" % (nu, ni, nnz, B))
+    top_trials, max_rank, mult = warp_geometry()
+    if D % mult or not mult <= D <= max_rank:
+        raise ValueError("rank = %d is not a multiple of %d in [%d, %d]" % (D, mult, mult, max_rank))
+    max_trials = int(max_trials)
+    if not 1 <= max_trials <= top_trials:
+        raise ValueError("max_trials = %d outside [1, %d]" % (max_trials, top_trials))
+    dev = user_factors.device
+    if failed is None:
+        failed = torch.zeros(1, dtype=torch.int32, device=dev)
+    _req(failed, torch.int32, "failed")
+    ids = torch.empty((5, B), dtype=torch.int32, device=dev)
+    loss_t = torch.empty(B, dtype=torch.float32, device=dev)
+    diff = torch.empty(B, dtype=torch.float32, device=dev) if want_diff else None
+    grads = torch.empty((3 * B, D), dtype=torch.float32, device=dev) if want_grads else None
+    check(lib.esr_warp_step(_p(user_factors), nu, _p(item_factors), ni, D, _p(offsets), _p(row_upos), _p(row_ipos), nnz,
+                            _p(rank_weight), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, B, max_trials, float(margin),
+                            float(reg), _p(ids[0]), _p(ids[1]), _p(ids[2]), _p(ids[3]), _p(ids[4]), _p(loss_t), _p(diff),
+                            _p(grads), _p(failed), _stream()), "esr_warp_step")
+    return ids[0], ids[1], ids[2], ids[3], ids[4], loss_t, diff, grads

@@ -1186,6 +1186,34 @@ int esr_bpr_fwd_bwd(const float* user_table, int64_t nu, const float* item_table
                     const int32_t* i, const int32_t* j, const int32_t* valid, int64_t B, float reg, float* loss_t,
                     float* diff_t, float* grads, int32_t* failed, esr_stream_t stream);
 
+/* ---- WARP (Weston, Bengio, Usunier, IJCAI 2011; esr_warp.hip) ----
+ * The rank-weighted margin loss over (user, seen item, violating unseen item) triples: one fused call that samples the pair,
+ * scores the positive, searches the candidate stream for a negative that violates the margin, weights the step by the rank
+ * estimate and writes the loss and the gradient rows.  No workspace.  The rule of a slot is stated in full in
+ * esrecsys_amd/csrc/esr_warp_sample.h (warp_slot), the text the kernel's pieces and a stand-alone host program compile.
+ *   geometry    max_trials = the most candidates a search may walk (255); D is a multiple of rank_multiple (4) and at most
+ *               max_rank (128).
+ *   step        B slots of global step `step` under `seed`.  The CSR, the Philox stream and the candidates are those of
+ *               esr_bpr_sample (for c < 15 the candidates are BPR's).  s_i = x_u . y_i and every s_j = x_u . y_j in f32 in the
+ *               order esr_bpr.hip states for one row; a candidate in u's row is skipped and not counted; otherwise
+ *               trials += 1 and d = s_i - s_j; the first candidate with d < margin (strict) within max_trials candidates is
+ *               the negative.  Then r = max(1, (ni - len_u) / trials), w = rank_weight[r] (rank_weight float[ni + 1]),
+ *               loss_t = w (margin - d), diff_t = d (may be null) and into grads float[3 B, D] = [user rows ; positive
+ *               rows ; negative rows]  g_u = reg x - w (yi - yj),  g_i = reg yi - w x,  g_j = reg yj + w x.  grads null:
+ *               forward only.  A slot without a violating candidate has out_valid = 0, out_j = the last candidate walked,
+ *               out_trials = its count of unseen candidates (may be 0) and zeros in loss_t, diff_t and its three rows.  An
+ *               item position outside the table (ill-formed CSR) sets bit 30 of *failed (the caller zeroes and reads it);
+ *               that slot reads no row and writes j = 0, valid = 0, trials = 0 and zeros.  A slot is a function of (seed,
+ *               step, slot, CSR, tables, max_trials, margin, reg, rank_weight) alone: not of B or the launch.  1 <= nnz, ni,
+ *               nu, B <= 2^31 - 1; 1 <= max_trials <= 255; margin finite; reg finite and not negative.  Tables and grads
+ *               16-byte aligned. */
+int esr_warp_geometry(int* max_trials, int* max_rank, int* rank_multiple);
+int esr_warp_step(const float* user_table, int64_t nu, const float* item_table, int64_t ni, int D, const int64_t* row_offsets,
+                  const int32_t* row_upos, const int32_t* row_ipos, int64_t nnz, const float* rank_weight, uint64_t seed,
+                  uint32_t step, int64_t B, int max_trials, float margin, float reg, int32_t* out_u, int32_t* out_i,
+                  int32_t* out_j, int32_t* out_valid, int32_t* out_trials, float* loss_t, float* diff_t, float* grads,
+                  int32_t* failed, esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
