@@ -272,6 +272,10 @@ SIGNATURES = {
     "esr_warp_step": (c_int, [c_f32p, c_i64, c_f32p, c_i64, c_int, c_vp, c_i32p, c_i32p, c_i64, c_f32p, c_uint64, c_uint32,
                               c_i64, c_int, c_f32, c_f32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p,
                               c_i32p, c_vp]),
+    "esr_bag_geometry": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "esr_bag_sum": (c_int, [c_f32p, c_i64, c_int, c_vp, c_i32p, c_f32p, c_i64, c_i64, c_i32p, c_i64, c_f32p, c_i32p, c_vp]),
+    "esr_bag_expand": (c_int, [c_f32p, c_i64, c_int, c_vp, c_i32p, c_f32p, c_i64, c_i64, c_i32p, c_f32p, c_i32p, c_vp, c_i64,
+                               c_i64, c_f32, c_i32p, c_f32p, c_i32p, c_vp]),
 }
 
 

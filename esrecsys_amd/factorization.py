@@ -30,7 +30,8 @@ every cell is fitted, a half-sweep is one ``ops.als_gram`` and one ``ops.als_sol
 folded in by the same call (``fold_in``, ``recommend_documents``).  ``BPR`` (further below) is the model of the same family
 that is trained on the ranking itself: Bayesian Personalised Ranking over triples sampled on the device (esr_bpr.hip), updated
 by the row-sparse engine; ``WARP`` (last) is BPR's model trained with the rank-weighted margin loss, its negatives searched
-for on the device by one fused call (esr_warp.hip).
+for on the device by one fused call (esr_warp.hip).  ``HybridBPR`` is BPR over users and items that are weighted sums of
+feature embeddings (esr_bag.hip): side information and cold start.
 """
 import math
 
@@ -592,6 +593,13 @@ class BPR:
 
     def __init__(self, user, item, rank=64, reg=0.01, lr=0.05, optimizer="adagrad", batch=65536, seed=0, init_scale=None,
                  device=None):
+        user, item = self._configure(user, item, rank, reg, lr, optimizer, batch, seed, init_scale, device)
+        with torch.cuda.device(self.device):
+            nu, ni = self._index_pairs(user, item)
+            self._init_tables(nu, ni)
+
+    def _configure(self, user, item, rank, reg, lr, optimizer, batch, seed, init_scale, device):
+        """The checks that need no device, then the hyper-parameters as attributes; returns the flat (user, item) tensors."""
         rank = int(rank)
         _, top, mult = ops.bpr_geometry()
         if not mult <= rank <= top or rank % mult:
@@ -619,29 +627,41 @@ class BPR:
         self.rank, self.reg, self.lr, self.optimizer, self.batch, self.seed = rank, reg, lr, optimizer, batch, int(seed)
         self.init_scale = float(rank) ** -0.5 if init_scale is None else float(init_scale)
         self.step = 0
+        return user, item
+
+    def _index_pairs(self, user, item):
+        """users / items, the CSR of the seen pairs on the host and on the device; returns (nu, ni)."""
         dev = self.device
-        with torch.cuda.device(dev):
-            user, item = user.to(dev).to(torch.int64), item.to(dev).to(torch.int64)
-            if int(user.min()) < 0 or int(item.min()) < 0 or int(user.max()) >= 2 ** 31 - 1 or int(item.max()) >= 2 ** 31 - 1:
-                raise ValueError("user and item ids must lie in [0, 2^31 - 1)")
-            users, upos = torch.unique(user, return_inverse=True)
-            items, ipos = torch.unique(item, return_inverse=True)
-            nu, ni = int(users.numel()), int(items.numel())
-            self.users, self.items = users.to(torch.int32).contiguous(), items.to(torch.int32).contiguous()
-            key = torch.unique((upos << 32) | ipos)                     # repeated events collapse to one seen pair
-            rows = torch.bincount(key >> 32, minlength=nu)
-            self._user_offsets = np.ascontiguousarray(
-                np.concatenate([[0], np.cumsum(rows.cpu().numpy().astype(np.int64))]).astype(np.int64))
-            self._key = key                                             # upos << 32 | ipos, ascending: the seen pairs
-            self._row_upos = (key >> 32).to(torch.int32).contiguous()
-            self._row_ipos = (key & 0xFFFFFFFF).to(torch.int32).contiguous()
-            self._offsets_dev = torch.from_numpy(self._user_offsets).to(dev)    # the sampler reads the CSR on the device
-            gen = torch.Generator(device="cpu").manual_seed(self.seed)
-            self.user_factors = (torch.randn(nu, rank, generator=gen) * self.init_scale).to(dev).contiguous()
-            self.item_factors = (torch.randn(ni, rank, generator=gen) * self.init_scale).to(dev).contiguous()
-            self.user_accum = torch.full((nu, rank), ADAGRAD_INIT, dtype=torch.float32, device=dev)
-            self.item_accum = torch.full((ni, rank), ADAGRAD_INIT, dtype=torch.float32, device=dev)
-            self._failed = torch.zeros(1, dtype=torch.int32, device=dev)
+        user, item = user.to(dev).to(torch.int64), item.to(dev).to(torch.int64)
+        if int(user.min()) < 0 or int(item.min()) < 0 or int(user.max()) >= 2 ** 31 - 1 or int(item.max()) >= 2 ** 31 - 1:
+            raise ValueError("user and item ids must lie in [0, 2^31 - 1)")
+        users, upos = torch.unique(user, return_inverse=True)
+        items, ipos = torch.unique(item, return_inverse=True)
+        nu, ni = int(users.numel()), int(items.numel())
+        self.users, self.items = users.to(torch.int32).contiguous(), items.to(torch.int32).contiguous()
+        key = torch.unique((upos << 32) | ipos)                     # repeated events collapse to one seen pair
+        rows = torch.bincount(key >> 32, minlength=nu)
+        self._user_offsets = np.ascontiguousarray(
+            np.concatenate([[0], np.cumsum(rows.cpu().numpy().astype(np.int64))]).astype(np.int64))
+        self._key = key                                             # upos << 32 | ipos, ascending: the seen pairs
+        self._row_upos = (key >> 32).to(torch.int32).contiguous()
+        self._row_ipos = (key & 0xFFFFFFFF).to(torch.int32).contiguous()
+        self._offsets_dev = torch.from_numpy(self._user_offsets).to(dev)    # the sampler reads the CSR on the device
+        self._failed = torch.zeros(1, dtype=torch.int32, device=dev)
+        return nu, ni
+
+    def _new_tables(self, nu, ni):
+        """(user table [nu, rank], item table [ni, rank], their Adagrad accumulators): ``randn * init_scale`` from the seeded
+        CPU generator, users first."""
+        dev, rank = self.device, self.rank
+        gen = torch.Generator(device="cpu").manual_seed(self.seed)
+        user = (torch.randn(nu, rank, generator=gen) * self.init_scale).to(dev).contiguous()
+        item = (torch.randn(ni, rank, generator=gen) * self.init_scale).to(dev).contiguous()
+        return (user, item, torch.full((nu, rank), ADAGRAD_INIT, dtype=torch.float32, device=dev),
+                torch.full((ni, rank), ADAGRAD_INIT, dtype=torch.float32, device=dev))
+
+    def _init_tables(self, nu, ni):
+        self.user_factors, self.item_factors, self.user_accum, self.item_accum = self._new_tables(nu, ni)
 
     @classmethod
     def from_documents(cls, indices, doc_offsets, **kw):
@@ -823,3 +843,301 @@ class WARP(BPR):
             raise FactorizationError("a WARP step met a position outside its table (bit 30)")
         self.mean_trials += [float(n) / self.batch for n in sums[2]]
         return [float(s) / int(n) if n else float("nan") for s, n in zip(sums[0], sums[1])]
+
+
+# ---- hybrid BPR: entities as sums of feature embeddings -----------------------------------------------------------------
+def _feature_coo(features, side):
+    """(entity int64, feature int64, weight float32 or None) of a ``(entity_id, feature_id, weight or None)`` triple as flat
+    host arrays, with the refusals that need nothing else: lengths, integer ids, finite weights."""
+    if len(features) != 3:
+        raise ValueError("%s_features must be (entity_id, feature_id, weight or None)" % side)
+    ent, feat = _tensor(features[0], "entity_id"), _tensor(features[1], "feature_id")
+    _same_length("%s_features' entity_id and feature_id" % side, ent, feat)
+    if ent.dtype.is_floating_point or feat.dtype.is_floating_point or ent.dtype == torch.bool or feat.dtype == torch.bool:
+        raise TypeError("%s_features' entity_id and feature_id must be integer arrays" % side)
+    ent, feat = ent.cpu().numpy().astype(np.int64), feat.cpu().numpy().astype(np.int64)
+    weight = None
+    if features[2] is not None:
+        w = _tensor(features[2], "weight")
+        _same_length("%s_features' entity_id and weight" % side, _tensor(features[0], "entity_id"), w)
+        w = w.cpu().numpy().astype(np.float64)
+        if not np.isfinite(w).all() or (np.abs(w) > float(np.finfo(np.float32).max)).any():
+            raise ValueError("%s_features: a weight is not finite (as a float32)" % side)
+        weight = w.astype(np.float32)
+    return ent, feat, weight
+
+
+def _bag_table(epos, fpos, weight, n, identity, side):
+    """The bag table of n entities on the host: (offsets int64[n + 1], feat int32[nnz], weight float32[nnz] or None).  With
+    `identity` entity e's bag starts with the indicator row e (weight 1) and the side features' rows follow, shifted by n;
+    within a bag the side features ascend.  A repeated (entity, feature) pair is refused."""
+    key = (epos << 32) | fpos
+    order = np.argsort(key, kind="stable")
+    key = key[order]
+    if key.size > 1 and (key[1:] == key[:-1]).any():
+        at = int(np.flatnonzero(key[1:] == key[:-1])[0])
+        raise ValueError("%s_features: the pair (entity position %d, feature position %d) is given twice"
+                         % (side, key[at] >> 32, key[at] & 0xFFFFFFFF))
+    lead = 1 if identity else 0
+    counts = np.bincount(epos, minlength=n).astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(counts + lead)]).astype(np.int64)
+    nnz = int(offsets[-1])
+    if nnz < 1:
+        raise ValueError("%s side: no entity has a feature" % side)
+    if nnz > 2 ** 31 - 1:
+        raise ValueError("%s side: %d feature occurrences exceed 2^31 - 1" % (side, nnz))
+    e_sorted = key >> 32
+    starts = np.concatenate([[0], np.cumsum(counts)])[:-1]
+    at = offsets[e_sorted] + lead + (np.arange(key.size) - starts[e_sorted])
+    feat = np.empty(nnz, np.int32)
+    feat[at] = (key & 0xFFFFFFFF) + (n if identity else 0)
+    w = None
+    if weight is not None:
+        w = np.ones(nnz, np.float32)
+        w[at] = weight[order]
+    if identity:
+        feat[offsets[:-1]] = np.arange(n, dtype=np.int32)
+    return np.ascontiguousarray(offsets), feat, w
+
+
+class _Bags:
+    """A bag table on the device (``ops.bag_sum`` / ``ops.bag_expand``) and its bags' lengths."""
+
+    def __init__(self, offsets, feat, weight, dev):
+        self.n = offsets.size - 1
+        self.offsets = torch.from_numpy(offsets).to(dev)
+        self.feat = torch.from_numpy(feat).to(dev)
+        self.weight = None if weight is None else torch.from_numpy(weight).to(dev)
+        self.lengths = torch.from_numpy(np.diff(offsets)).to(dev)
+
+    def args(self):
+        return self.offsets, self.feat, self.weight
+
+
+class HybridBPR(BPR):
+    """BPR over users and items that are weighted sums of feature embeddings (Kula, "Metadata Embeddings for User and Item
+    Cold-start Recommendations", 2015: LightFM's model, trained with the BPR step).
+
+        model = HybridBPR(user, item, item_features=(item_id, tag_id, None), rank=64)
+        losses = model.fit(steps=2000)
+        new_ids, new_rows = model.compose_items(new_item_id, new_tag_id)      # items that were in no training pair
+        rec_ids, rec_scores, rec_lengths = model.recommend(users, k=500, extra_items=(new_ids, new_rows))
+
+    Representation.  ``x_u = sum_f w[u, f] e_f`` over the features of u's bag (``ops.bag_sum``: a fmaf chain in the bag's
+    order), and the same for items.  ``*_features`` is ``(entity_id, feature_id, weight or None)`` in COO form; raw ids
+    become positions through ``torch.unique`` / a sorted search.  ``identity[side]`` gives every entity one indicator
+    feature of weight 1, placed first in its bag; its rows are rows [0, n) of the side's embedding table and the side
+    features' rows follow in ascending id (``user_feature_ids`` / ``item_feature_ids``).  With identity-only bags the model
+    is BPR's.
+
+    Step.  Compose the batch's rows (``P`` for u, ``Q`` for [i ; j]), run ``ops.bpr_fwd_bwd`` on them with reg = 0, hand the
+    gradient rows back to the features with ``ops.bag_expand`` (which adds ``reg * e_f`` per occurrence) and update the
+    embedding tables through the row-sparse engine as BPR does.  The objective of a step is ``sum_valid softplus(-d) +
+    (reg / 2) sum |e_f|^2`` over every feature occurrence of the valid triples' three bags.
+
+    ``user_embeddings`` [nfu, rank] / ``item_embeddings`` [nfi, rank] are initialised like BPR's tables (seeded CPU
+    generator, users first); ``user_factors`` / ``item_factors`` are the composed tables of every known entity
+    (``user_rows()`` / ``item_rows()``), which ``score``, ``recommend`` and ``auc`` read."""
+
+    def __init__(self, user, item, user_features=None, item_features=None, identity=(True, True), rank=64, reg=0.01, lr=0.05,
+                 optimizer="adagrad", batch=65536, seed=0, init_scale=None, device=None):
+        identity = tuple(bool(v) for v in identity)
+        if len(identity) != 2:
+            raise ValueError("identity must be a (user side, item side) pair")
+        given = (user_features, item_features)
+        for side, feats, ident in zip(("user", "item"), given, identity):
+            if feats is None and not ident:
+                raise ValueError("%s side: identity is off and no %s_features are given: its entities would have no feature"
+                                 % (side, side))
+        coo = [None if f is None else _feature_coo(f, side) for side, f in zip(("user", "item"), given)]
+        # (the pairs' own host checks come first, as BPR's; the features are then checked against the pairs' ids on the host)
+        ids = [_tensor(user, "user"), _tensor(item, "item")]
+        tables = []
+        if not any(t.dtype.is_floating_point for t in ids) and ids[0].numel() == ids[1].numel() and ids[0].numel():
+            for side, t, c, ident in zip(("user", "item"), ids, coo, identity):
+                tables.append(self._host_bags(side, np.unique(t.cpu().numpy().astype(np.int64)), c, ident))
+        user, item = self._configure(user, item, rank, reg, lr, optimizer, batch, seed, init_scale, device)
+        self.identity = identity
+        with torch.cuda.device(self.device):
+            nu, ni = self._index_pairs(user, item)
+            (ubag, ufeat), (ibag, ifeat) = tables
+            self._user_bags, self._item_bags = _Bags(*ubag, self.device), _Bags(*ibag, self.device)
+            self.user_feature_ids = torch.from_numpy(ufeat).to(self.device)
+            self.item_feature_ids = torch.from_numpy(ifeat).to(self.device)
+            self._init_tables((nu if identity[0] else 0) + ufeat.size, (ni if identity[1] else 0) + ifeat.size)
+
+    @staticmethod
+    def _host_bags(side, known, coo, identity):
+        """((offsets, feat, weight), side feature ids int64 ascending) of one side on the host; `known` = the side's entity
+        ids, ascending."""
+        n = known.size
+        if coo is None:
+            ent = fpos = np.zeros(0, np.int64)
+            weight, feature_ids = None, np.zeros(0, np.int64)
+        else:
+            ent, feat, weight = coo
+            at = np.searchsorted(known, ent).clip(max=n - 1)
+            if ent.size and (known[at] != ent).any():
+                raise ValueError("%s_features: entity id %d occurs in no (user, item) pair"
+                                 % (side, int(ent[known[at] != ent][0])))
+            ent = at.astype(np.int64)
+            feature_ids, fpos = np.unique(feat, return_inverse=True)
+            fpos = fpos.reshape(-1).astype(np.int64)
+            if n + feature_ids.size > 2 ** 31 - 1:
+                raise ValueError("%s side: more than 2^31 - 1 feature rows" % side)
+        return _bag_table(ent, fpos, weight, n, identity, side), feature_ids
+
+    def _init_tables(self, nfu, nfi):
+        self.user_embeddings, self.item_embeddings, self.user_accum, self.item_accum = self._new_tables(nfu, nfi)
+        self._composed = None
+
+    # ---- the composed tables ------------------------------------------------------------------------------------------------
+    def _compose_all(self):
+        key = (self.step, self.user_embeddings._version, self.item_embeddings._version)
+        if self._composed is None or self._composed[0] != key:
+            with torch.cuda.device(self.device):
+                self._failed.zero_()
+                rows = (ops.bag_sum(self.user_embeddings, *self._user_bags.args(), failed=self._failed),
+                        ops.bag_sum(self.item_embeddings, *self._item_bags.args(), failed=self._failed))
+                if int(self._failed.item()) & FAIL_BAD_POSITION:
+                    raise FactorizationError("a bag names a feature position outside its table (bit 30)")
+            self._composed = (key,) + rows
+        return self._composed[1:]
+
+    def user_rows(self):
+        """float32[nu, rank]: every known user composed from the embeddings as they stand (kept until the next step)."""
+        return self._compose_all()[0]
+
+    def item_rows(self):
+        """float32[ni, rank]: every known item composed from the embeddings as they stand (kept until the next step)."""
+        return self._compose_all()[1]
+
+    user_factors = property(user_rows)
+    item_factors = property(item_rows)
+
+    # ---- training -------------------------------------------------------------------------------------------------------
+    def _step(self, u, ij, valid, valid2, oo_u, oo_i, Mu, Mi, ar, ar_b):
+        """One step on the triples (u, [i ; j]); returns loss_t."""
+        B = u.numel()
+        ue, ie, ub, ib = self.user_embeddings, self.item_embeddings, self._user_bags, self._item_bags
+        P = ops.bag_sum(ue, *ub.args(), rows=u, failed=self._failed)
+        Q = ops.bag_sum(ie, *ib.args(), rows=ij, failed=self._failed)
+        loss_t, _, grads = ops.bpr_fwd_bwd(P, Q, ar, ar, ar_b, valid, 0.0, failed=self._failed)
+        out_feat = torch.empty(Mu + Mi, dtype=torch.int32, device=self.device)
+        out_grads = torch.empty((Mu + Mi, self.rank), dtype=torch.float32, device=self.device)
+        fu, fi, gu, gi = out_feat[:Mu], out_feat[Mu:], out_grads[:Mu], out_grads[Mu:]
+        ops.bag_expand(ue, *ub.args(), u, grads[:B], valid, oo_u, Mu, self.reg, out=(fu, gu), failed=self._failed)
+        ops.bag_expand(ie, *ib.args(), ij, grads[B:], valid2, oo_i, Mi, self.reg, out=(fi, gi), failed=self._failed)
+        nfu, nfi = ue.shape[0], ie.shape[0]
+        if self.optimizer == "adagrad":
+            if Mu + Mi:
+                sorted_ids, perm = ops.segment_sort_multi([fu, fi], [0, nfu], nfu + nfi)
+                ops.sparse_adagrad_multi([ue, ie], [self.user_accum, self.item_accum], [0, nfu, nfu + nfi], sorted_ids, perm,
+                                         out_grads, self.lr)
+        else:
+            for table, f, g, nf in ((ue, fu, gu, nfu), (ie, fi, gi, nfi)):
+                if f.numel():
+                    sorted_ids, perm = ops.segment_sort(f, nf)
+                    ops.sparse_sgd(table, sorted_ids, perm, g, self.lr)
+        return loss_t
+
+    def train_steps(self, K):
+        """K steps: one sampler launch, every step's ``out_offsets`` by one torch scan, one read of the expanded sizes, then
+        per step the two compositions, the forward / backward, the two expansions, the sort and the update.  Returns
+        BPR's per-step mean loss.  Raises ``ValueError`` when a step's expanded occurrences exceed 2^31 - 1 and
+        ``FactorizationError`` when a kernel met a position outside its table."""
+        K = int(K)
+        if K < 1:
+            raise ValueError("K = %d below 1" % K)
+        dev, B = self.device, self.batch
+        with torch.cuda.device(dev):
+            u, i, j, valid, dropped = self.sample(K)
+            ij, valid2 = torch.cat([i, j], dim=1), torch.cat([valid, valid], dim=1)
+            oo_u = torch.zeros((K, B + 1), dtype=torch.int64, device=dev)
+            oo_i = torch.zeros((K, 2 * B + 1), dtype=torch.int64, device=dev)
+            oo_u[:, 1:] = torch.cumsum(self._user_bags.lengths[u.to(torch.int64)], 1)
+            oo_i[:, 1:] = torch.cumsum(self._item_bags.lengths[ij.to(torch.int64)], 1)
+            sizes = torch.stack([oo_u[:, -1], oo_i[:, -1]]).cpu().numpy()            # the one read of sizes
+            if int((sizes[0] + sizes[1]).max()) > 2 ** 31 - 1:
+                raise ValueError("a step expands to %d feature occurrences, above 2^31 - 1: lower batch"
+                                 % int((sizes[0] + sizes[1]).max()))
+            ar = torch.arange(2 * B, dtype=torch.int32, device=dev)
+            self._failed.zero_()
+            sums = torch.empty(K, dtype=torch.float64, device=dev)
+            for k in range(K):
+                loss_t = self._step(u[k], ij[k], valid[k], valid2[k], oo_u[k], oo_i[k], int(sizes[0, k]), int(sizes[1, k]),
+                                    ar[:B], ar[B:])
+                sums[k] = loss_t.to(torch.float64).sum()
+            self.step += K
+            self._composed = None
+            word = int(self._failed.item())
+            sums, kept = sums.cpu().numpy(), self.batch - dropped.cpu().numpy().astype(np.int64)
+        if word & FAIL_BAD_POSITION:
+            raise FactorizationError("a hybrid BPR step met a position outside its table (bit 30)")
+        return [float(s) / int(n) if n else float("nan") for s, n in zip(sums, kept)]
+
+    # ---- cold start -------------------------------------------------------------------------------------------------------
+    def _compose_new(self, side, entity_id, feature_id, weight):
+        known = (self.users if side == "user" else self.items).cpu().numpy().astype(np.int64)
+        feature_ids = (self.user_feature_ids if side == "user" else self.item_feature_ids).cpu().numpy()
+        table = self.user_embeddings if side == "user" else self.item_embeddings
+        ent, feat, weight = _feature_coo((entity_id, feature_id, weight), side)
+        if ent.size == 0:
+            raise ValueError("compose_%ss: no (entity, feature) pair" % side)
+        if ent.min() < 0 or ent.max() >= 2 ** 31 - 1:
+            raise ValueError("entity ids must lie in [0, 2^31 - 1)")
+        if np.isin(ent, known).any():
+            raise ValueError("compose_%ss: %s %d was in training: recommend ranks it already"
+                             % (side, side, int(ent[np.isin(ent, known)][0])))
+        fpos = np.searchsorted(feature_ids, feat).clip(max=max(feature_ids.size - 1, 0))
+        if feature_ids.size == 0 or (feature_ids[fpos] != feat).any():
+            bad = feat if feature_ids.size == 0 else feat[feature_ids[fpos] != feat]
+            raise ValueError("compose_%ss: feature id %d was not seen in training" % (side, int(bad[0])))
+        ids, epos = np.unique(ent, return_inverse=True)
+        shift = known.size if self.identity[0 if side == "user" else 1] else 0
+        offsets, bag_feat, w = _bag_table(epos.reshape(-1).astype(np.int64), fpos.astype(np.int64) + shift, weight, ids.size,
+                                          False, side)
+        with torch.cuda.device(self.device):
+            bags = _Bags(offsets, bag_feat, w, self.device)
+            self._failed.zero_()
+            rows = ops.bag_sum(table, *bags.args(), failed=self._failed)
+            if int(self._failed.item()) & FAIL_BAD_POSITION:
+                raise FactorizationError("compose_%ss met a feature position outside the table (bit 30)" % side)
+            return torch.from_numpy(ids.astype(np.int32)).to(self.device), rows
+
+    def compose_items(self, entity_id, feature_id, weight=None):
+        """(ids int32[n] ascending, rows float32[n, rank]) of items that were NOT in training, composed from known features
+        only (no identity row).  A feature id the model never saw, a known item or a repeated pair raises ``ValueError``."""
+        return self._compose_new("item", entity_id, feature_id, weight)
+
+    def compose_users(self, entity_id, feature_id, weight=None):
+        """``compose_items`` for users: rows to score against ``item_rows()`` (``ops.retrieve_topk``, ``ops.als_predict``)."""
+        return self._compose_new("user", entity_id, feature_id, weight)
+
+    def recommend(self, users, k=500, exclude_seen=True, slack=16, extra_items=None):
+        """``BPR.recommend`` on the composed tables.  ``extra_items`` = the ``(ids, rows)`` of ``compose_items``: those items
+        are ranked together with the known ones by the same (score descending, item id ascending) order and are never
+        "seen"."""
+        with torch.cuda.device(self.device):
+            upos = self._positions(users, self.users).to(torch.int64)
+            rows, items, key = self.item_factors, self.items, self._key
+            if extra_items is not None:
+                ids, extra = extra_items
+                ids = _tensor(ids, "extra ids").to(self.device).to(torch.int64)
+                if not isinstance(extra, torch.Tensor) or extra.dtype != torch.float32 or extra.dim() != 2 or \
+                        tuple(extra.shape) != (ids.numel(), self.rank):
+                    raise ValueError("extra_items must be (ids[n], float32 rows[n, rank])")
+                both = torch.cat([items.to(torch.int64), ids])
+                if torch.unique(both).numel() != both.numel():
+                    raise ValueError("extra_items repeats an item id or names a known item")
+                if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= 2 ** 31 - 1):
+                    raise ValueError("item ids must lie in [0, 2^31 - 1)")
+                order = torch.argsort(both)
+                place = torch.empty_like(order)
+                place[order] = torch.arange(order.numel(), device=self.device)      # old position -> position by id
+                rows = torch.cat([rows, extra.to(self.device)])[order].contiguous()
+                items = both[order].to(torch.int32).contiguous()
+                key = ((key >> 32) << 32) | place[key & 0xFFFFFFFF]                 # (monotone per user: still ascending)
+            return _recommend_rows(self.user_factors, None, upos, rows, items, k, slack,
+                                   self._user_offsets if exclude_seen else None, key,
+                                   lambda q: "user %d" % int(_tensor(users, "users")[q]), "has seen", "exclude_seen")

@@ -2142,3 +2142,97 @@ def warp_step(user_factors, item_factors, offsets, row_upos, row_ipos, rank_weig
                             float(reg), _p(ids[0]), _p(ids[1]), _p(ids[2]), _p(ids[3]), _p(ids[4]), _p(loss_t), _p(diff),
                             _p(grads), _p(failed), _stream()), "esr_warp_step")
     return ids[0], ids[1], ids[2], ids[3], ids[4], loss_t, diff, grads
+
+
+# ---------------------------------------------------------------------------------------------
+# Bag tables (esr_bag.hip): rows composed as weighted sums of feature rows, and the transpose for the optimiser
+def bag_geometry():
+    """(max_rank, rank_multiple): bag_sum and bag_expand take a rank that is a multiple of rank_multiple and at most
+    max_rank -- bpr_fwd_bwd's geometry."""
+    rank, mult = ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.load().esr_bag_geometry(ctypes.byref(rank), ctypes.byref(mult)), "esr_bag_geometry")
+    return int(rank.value), int(mult.value)
+
+
+def _bag_args(who, table, offsets, feat, weight, rows):
+    """The checks bag_sum and bag_expand share.  Returns (nf, D, nnz, n_bags, n)."""
+    _req(table, torch.float32, "table"), _req(offsets, torch.int64, "offsets"), _req(feat, torch.int32, "feat")
+    if table.dim() != 2:
+        raise ValueError("%s: table must be [nf, rank]" % who)
+    nf, D, nnz, n_bags = int(table.shape[0]), int(table.shape[1]), feat.numel(), offsets.numel() - 1
+    max_rank, mult = bag_geometry()
+    if D % mult or not mult <= D <= max_rank:
+        raise ValueError("rank = %d is not a multiple of %d in [%d, %d]" % (D, mult, mult, max_rank))
+    if weight is not None:
+        _req(weight, torch.float32, "weight")
+        if weight.numel() != nnz:
+            raise ValueError("%s: weight must hold one entry per feat entry" % who)
+    lim = 2 ** 31 - 1
+    if not (1 <= nf <= lim and 1 <= nnz <= lim and 1 <= n_bags <= lim):
+        raise ValueError("%s: nf=%d nnz=%d n_bags=%d (each in [1, 2^31 - 1])" % (who, nf, nnz, n_bags))
+    if rows is not None:
+        _req(rows, torch.int32, "rows")
+    n = n_bags if rows is None else rows.numel()
+    if n > lim:
+        raise ValueError("%s: n=%d above 2^31 - 1" % (who, n))
+    return nf, D, nnz, n_bags, n
+
+
+def bag_sum(table, offsets, feat, weight, rows=None, out=None, failed=None):
+    """out float32[n, D]: row r is the bag b = rows[r] (int32[n], any order, repeats allowed; every bag in order when None)
+    of the bag table (offsets int64[n_bags + 1], feat int32[nnz] positions into table float32[nf, D], weight float32[nnz]
+    or None = all 1) composed by the rule of esr_bag_rule.h: acc = fmaf(w[k], table[feat[k]], acc) over the bag's
+    occurrences in ascending order from +0.0.  An empty bag gives zeros.  `failed` (int32[1], device; a scratch word when
+    None) gets bit 30 when a bag number or feature position lies outside its table -- that row is zeros; the caller zeroes
+    and reads it."""
+    lib = _lib.load()
+    nf, D, nnz, n_bags, n = _bag_args("bag_sum", table, offsets, feat, weight, rows)
+    dev = table.device
+    if out is None:
+        out = torch.empty((n, D), dtype=torch.float32, device=dev)
+    _req(out, torch.float32, "out")
+    if out.numel() != n * D:
+        raise ValueError("bag_sum: out must be [n, rank]")
+    if failed is None:
+        failed = torch.zeros(1, dtype=torch.int32, device=dev)
+    _req(failed, torch.int32, "failed")
+    if n:
+        check(lib.esr_bag_sum(_p(table), nf, D, _p(offsets), _p(feat), _p(weight), nnz, n_bags, _p(rows), n, _p(out),
+                              _p(failed), _stream()), "esr_bag_sum")
+    return out
+
+
+def bag_expand(table, offsets, feat, weight, rows, grad_rows, valid, out_offsets, M, reg, out=None, failed=None):
+    """(out_feat int32[M], out_grads float32[M, D]): the gradients grad_rows float32[n, D] of the rows bag_sum composed for
+    `rows`, handed to the features as one row per occurrence: occurrence k of selected bag r lands at p = out_offsets[r] +
+    (k - offsets[b]) with out_feat[p] = feat[k] and out_grads[p] = fmaf(w[k], grad_rows[r], reg * table[feat[k]]).
+    out_offsets int64[n + 1] is the exclusive scan of the selected bags' lengths and M = out_offsets[n], both computed by
+    the caller.  valid int32[n] or None (all valid): valid[r] == 0 gives zero rows and the table is not read.  `out` = an
+    (out_feat, out_grads) pair to write into.  `failed` as bag_sum's; a refused occurrence gives out_feat = 0 and zeros."""
+    lib = _lib.load()
+    nf, D, nnz, n_bags, n = _bag_args("bag_expand", table, offsets, feat, weight, rows)
+    _req(grad_rows, torch.float32, "grad_rows"), _req(out_offsets, torch.int64, "out_offsets")
+    M = int(M)
+    if grad_rows.numel() != n * D or out_offsets.numel() != n + 1:
+        raise ValueError("bag_expand: grad_rows must be [n, rank] and out_offsets hold n + 1 entries")
+    if not 0 <= M <= 2 ** 31 - 1:
+        raise ValueError("bag_expand: M=%d expanded occurrences outside [0, 2^31 - 1]" % M)
+    if valid is not None:
+        _req(valid, torch.int32, "valid")
+        if valid.numel() != n:
+            raise ValueError("bag_expand: valid must hold one entry per selected bag")
+    dev = table.device
+    if out is None:
+        out = (torch.empty(M, dtype=torch.int32, device=dev), torch.empty((M, D), dtype=torch.float32, device=dev))
+    out_feat, out_grads = out
+    _req(out_feat, torch.int32, "out[0]"), _req(out_grads, torch.float32, "out[1]")
+    if out_feat.numel() != M or out_grads.numel() != M * D:
+        raise ValueError("bag_expand: out must be (int32[M], float32[M, rank])")
+    if failed is None:
+        failed = torch.zeros(1, dtype=torch.int32, device=dev)
+    _req(failed, torch.int32, "failed")
+    if n:
+        check(lib.esr_bag_expand(_p(table), nf, D, _p(offsets), _p(feat), _p(weight), nnz, n_bags, _p(rows), _p(grad_rows),
+                                 _p(valid), _p(out_offsets), n, M, float(reg), _p(out_feat), _p(out_grads), _p(failed),
+                                 _stream()), "esr_bag_expand")
+    return out_feat, out_grads

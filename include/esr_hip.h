@@ -1214,6 +1214,38 @@ int esr_warp_step(const float* user_table, int64_t nu, const float* item_table, 
                   int32_t* out_j, int32_t* out_valid, int32_t* out_trials, float* loss_t, float* diff_t, float* grads,
                   int32_t* failed, esr_stream_t stream);
 
+/* ---- Bag tables (Kula, LightFM, 2015; esr_bag.hip) ----
+ * A user or an item of the hybrid model is the weighted sum of the embedding rows of its features.  A bag table is a CSR
+ * over entities: bag_offsets int64[n_bags + 1], bag_feat int32[nnz] (row positions into table float[nf, D]) and bag_weight
+ * float[nnz] or null (every weight 1).  The rule of both calls is stated in esrecsys_amd/csrc/esr_bag_rule.h, the text the
+ * kernels and a stand-alone host program compile.  No workspace; the calls never synchronise.
+ *   geometry    D is a multiple of rank_multiple (4) and at most max_rank (128): esr_bpr_fwd_bwd's geometry.
+ *   sum         out float[n, D]: row r is bag b = rows[r] (rows int32[n], any order, repeats allowed) or b = r (rows null,
+ *               n <= n_bags): out[r, c] = acc after acc = fmaf(w[k], table[feat[k], c], acc) for k = off[b] .. off[b + 1] - 1
+ *               ascending, from +0.0f.  An empty bag gives a zero row.  An element depends on its own bag and column only:
+ *               not on n, the launch or the bags beside it.
+ *   expand      the transpose for the optimiser.  grad_rows float[n, D] are the composed rows' gradients, valid int32[n] or
+ *               null (all valid), out_offsets int64[n + 1] the exclusive scan of the selected bags' lengths (computed by the
+ *               caller), M = out_offsets[n] the rows of out_feat int32[M] / out_grads float[M, D].  Occurrence k of
+ *               selected bag r is output row p = out_offsets[r] + (k - off[b]):  out_feat[p] = feat[k],
+ *               out_grads[p, c] = fmaf(w[k], grad_rows[r, c], reg * table[feat[k], c]); with valid[r] == 0 the row is zeros
+ *               and the table is not read.  Every output row of [out_offsets[r], out_offsets[r + 1]) (clamped into [0, M])
+ *               is written; an output row depends on its own occurrence only.
+ * Refusals on the device: a bag number outside [0, n_bags) or a feature position outside [0, nf) sets bit 30 of *failed (the
+ * caller zeroes and reads it), reads no row and writes zeros -- the whole row of sum; the one output row of expand, with
+ * out_feat = 0, as does an output row that the bag has no occurrence for.  The row bounds off[b], off[b + 1] are clamped into
+ * [0, nnz]: an ill-formed CSR gives a wrong row, never a read outside the arrays.
+ * 1 <= nf, nnz, n_bags <= 2^31 - 1; 0 <= n, M <= 2^31 - 1 (n = 0: nothing is launched); reg finite and not negative.
+ * table, grad_rows, out and out_grads 16-byte aligned, the int64 arrays 8-byte aligned. */
+int esr_bag_geometry(int* max_rank, int* rank_multiple);
+int esr_bag_sum(const float* table, int64_t nf, int D, const int64_t* bag_offsets, const int32_t* bag_feat,
+                const float* bag_weight, int64_t nnz, int64_t n_bags, const int32_t* rows, int64_t n, float* out,
+                int32_t* failed, esr_stream_t stream);
+int esr_bag_expand(const float* table, int64_t nf, int D, const int64_t* bag_offsets, const int32_t* bag_feat,
+                   const float* bag_weight, int64_t nnz, int64_t n_bags, const int32_t* rows, const float* grad_rows,
+                   const int32_t* valid, const int64_t* out_offsets, int64_t n, int64_t M, float reg, int32_t* out_feat,
+                   float* out_grads, int32_t* failed, esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
