@@ -18,7 +18,7 @@ SOURCES = ["esr_core.hip", "esr_glove.hip", "esr_triplet.hip", "esr_inbatch.hip"
 HEADERS = [os.path.join(HERE, "..", "include", "esr_probe.h"), os.path.join(CSRC, "esr_common.h"), os.path.join(CSRC, "esr_versioned.h"), os.path.join(CSRC, "esr_inbatch_mfma.h"),
            os.path.join(HERE, "..", "include", "esr_hip.h"), os.path.join(CSRC, "esr_adam.h"), os.path.join(CSRC, "esr_segment.h"), os.path.join(CSRC, "esr_cooccur_table.h"),
            os.path.join(CSRC, "esr_philox.h"), os.path.join(CSRC, "esr_rank_keys.h"), os.path.join(CSRC, "esr_wide_table.h"),
-           os.path.join(CSRC, "esr_bpr_sample.h"), os.path.join(CSRC, "esr_warp_sample.h"), os.path.join(CSRC, "esr_bag_rule.h")]
+           os.path.join(CSRC, "esr_bpr_sample.h"), os.path.join(CSRC, "esr_warp_sample.h"), os.path.join(CSRC, "esr_bag_rule.h"), os.path.join(CSRC, "esr_row4.h")]
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

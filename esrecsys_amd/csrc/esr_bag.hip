@@ -3,9 +3,7 @@
 // gradients back to the features as one row per occurrence for the row-sparse engine (esr_sort.hip, esr_optim.hip).  The
 // rule of both is esr_bag_rule.h's; factorization.HybridBPR drives them around the unchanged esr_bpr_fwd_bwd.
 //
-// Layout, as bpr_fwd_bwd_kernel: one selected bag per group of G lanes, G the power of two >= D / 4 (1 .. 32): lane l of the
-// group holds elements 4 l .. 4 l + 3 of every row as one float4 (lanes with 4 l >= D hold nothing), so every row load and
-// store is 16 bytes per lane and 64 / G bags share a wave.
+// Layout: one selected bag per group of G lanes in the float4 row-group layout of esr_row4.h.
 //
 // Sum.  The group walks its bag's occurrences in ascending order; per element the chain acc = fmaf(w[k], E[feat[k], c], acc)
 // from +0.0f.  The feat / weight words and the rows of kBagUnroll occurrences are loaded together before their four chain
@@ -24,6 +22,7 @@
 // polled.  Registers (hipcc -O3, gfx950, no scratch): DESIGN.md section 4l.
 #include "esr_bag_rule.h"
 #include "esr_common.h"
+#include "esr_row4.h"
 
 namespace esr {
 
@@ -38,13 +37,12 @@ __global__ __launch_bounds__(kBlock) void bag_sum_kernel(const float* __restrict
                                                          const float* __restrict__ bag_weight, int64_t nnz, int64_t n_bags,
                                                          const int32_t* __restrict__ rows, int64_t n, float* __restrict__ out,
                                                          int32_t* __restrict__ failed) {
-  constexpr int kGroups = kBlock / G;
-  const int lig = threadIdx.x % G, nvec = D >> 2;
-  const bool holds = lig < nvec;  // (D = 100: 25 of the 32 lanes hold a chunk)
-  const int64_t ngroups = (int64_t)gridDim.x * kGroups;
-  for (int64_t r = (int64_t)blockIdx.x * kGroups + threadIdx.x / G; r < n; r += ngroups) {  // (uniform per group)
+  const int lig = row4_lig<G>();
+  const bool holds = row4_holds(lig, D);
+  const int64_t ngroups = row4_stride<G>();
+  for (int64_t r = row4_first<G>(); r < n; r += ngroups) {  // (uniform per group)
     const int64_t b = rows ? (int64_t)rows[r] : r;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 acc = row4_zero();
     bool bad = !bag_number_ok(b, n_bags);
     if (!bad) {
       const BagSpan s = bag_span(bag_offsets, b, nnz);
@@ -62,8 +60,7 @@ __global__ __launch_bounds__(kBlock) void bag_sum_kernel(const float* __restrict
         for (int q = 0; q < kBagUnroll; ++q) {
           const bool ok = bag_feat_ok(f[q], nf);
           bad |= !ok;
-          e[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (ok && holds) e[q] = *reinterpret_cast<const float4*>(table + f[q] * D + 4 * lig);
+          e[q] = row4_load(table, f[q], D, lig, ok && holds);
         }
 #pragma unroll
         for (int q = 0; q < kBagUnroll; ++q) acc = bag_step4(w[q], e[q], acc);
@@ -73,16 +70,14 @@ __global__ __launch_bounds__(kBlock) void bag_sum_kernel(const float* __restrict
         const float w = bag_weight ? bag_weight[k] : 1.0f;
         const bool ok = bag_feat_ok(f, nf);
         bad |= !ok;
-        float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok && holds) e = *reinterpret_cast<const float4*>(table + f * D + 4 * lig);
-        acc = bag_step4(w, e, acc);
+        acc = bag_step4(w, row4_load(table, f, D, lig, ok && holds), acc);
       }
     }
     if (bad) {
-      acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      acc = row4_zero();
       if (lig == 0) atomicOr(failed, kBagFailBad);
     }
-    if (holds) *reinterpret_cast<float4*>(out + r * D + 4 * lig) = acc;
+    row4_store(out, r, D, lig, holds, acc);
   }
 }
 
@@ -97,11 +92,10 @@ __global__ __launch_bounds__(kBlock) void bag_expand_kernel(const float* __restr
                                                             const int64_t* __restrict__ out_offsets, int64_t n, int64_t M,
                                                             float reg, int32_t* __restrict__ out_feat,
                                                             float* __restrict__ out_grads, int32_t* __restrict__ failed) {
-  constexpr int kGroups = kBlock / G;
-  const int lig = threadIdx.x % G, nvec = D >> 2;
-  const bool holds = lig < nvec;
-  const int64_t ngroups = (int64_t)gridDim.x * kGroups;
-  for (int64_t r = (int64_t)blockIdx.x * kGroups + threadIdx.x / G; r < n; r += ngroups) {  // (uniform per group)
+  const int lig = row4_lig<G>();
+  const bool holds = row4_holds(lig, D);
+  const int64_t ngroups = row4_stride<G>();
+  for (int64_t r = row4_first<G>(); r < n; r += ngroups) {  // (uniform per group)
     const int64_t b = rows ? (int64_t)rows[r] : r;
     int64_t q0 = out_offsets[r], q1 = out_offsets[r + 1];
     q0 = q0 < 0 ? 0 : (q0 > M ? M : q0);
@@ -112,12 +106,12 @@ __global__ __launch_bounds__(kBlock) void bag_expand_kernel(const float* __restr
     if (!bad) s = bag_span(bag_offsets, b, nnz);
     bad |= (s.hi - s.lo) != (q1 - q0);  // (a bad bag number with no output rows is still refused: the first test stands)
     const bool live = !valid || valid[r] != 0;
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live && holds) g = *reinterpret_cast<const float4*>(grad_rows + r * D + 4 * lig);
+    float4 g = row4_zero();
+    if (live && holds) g = *row4_ptr(grad_rows, r, D, lig);
     for (int64_t q = q0; q < q1; ++q) {
       const int64_t k = s.lo + (q - q0);
       int64_t f = 0;
-      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 o = row4_zero();
       if (k < s.hi) {
         f = bag_feat[k];
         if (!bag_feat_ok(f, nf)) {
@@ -125,12 +119,13 @@ __global__ __launch_bounds__(kBlock) void bag_expand_kernel(const float* __restr
           f = 0;
         } else if (live && holds) {
           const float w = bag_weight ? bag_weight[k] : 1.0f;
-          const float4 e = *reinterpret_cast<const float4*>(table + f * D + 4 * lig);
+          const float4 e = *row4_ptr(table, f, D, lig);
           o = make_float4(bag_expand_elem(w, g.x, reg, e.x), bag_expand_elem(w, g.y, reg, e.y),
                           bag_expand_elem(w, g.z, reg, e.z), bag_expand_elem(w, g.w, reg, e.w));
         }
       }
       if (lig == 0) out_feat[q] = (int32_t)f;
+      // (row4_store's text, spelled out: through the helper this loop's address arithmetic is scheduled differently)
       if (holds) *reinterpret_cast<float4*>(out_grads + q * D + 4 * lig) = o;
     }
     if (bad && lig == 0) atomicOr(failed, kBagFailBad);
@@ -158,16 +153,6 @@ static int bag_table_args(const char* who, const float* table, int64_t nf, int D
 
 using namespace esr;
 
-#define ESR_BAG_DISPATCH(G, LAUNCH) \
-  switch (G) {                      \
-    case 1: LAUNCH(1); break;       \
-    case 2: LAUNCH(2); break;       \
-    case 4: LAUNCH(4); break;       \
-    case 8: LAUNCH(8); break;       \
-    case 16: LAUNCH(16); break;     \
-    default: LAUNCH(32); break;     \
-  }
-
 extern "C" {
 
 int esr_bag_geometry(int* max_rank, int* rank_multiple) {
@@ -188,15 +173,10 @@ int esr_bag_sum(const float* table, int64_t nf, int D, const int64_t* bag_offset
   ESR_REQUIRE(rows || n <= n_bags, "%s: n=%lld exceeds n_bags=%lld without rows", who, (long long)n, (long long)n_bags);
   if (n == 0) return ESR_OK;
   hipStream_t st = as_stream(stream);
-  int G = 1;
-  while (G < D / 4) G <<= 1;
-  const int grid = grid_for_groups(n, G);
-#define ESR_BAG_SUM_LAUNCH(GG)                                                                                            \
-  ESR_KT("bag_sum", st,                                                                                                   \
-         hipLaunchKernelGGL(bag_sum_kernel<GG>, dim3(grid), dim3(kBlock), 0, st, table, nf, D, bag_offsets, bag_feat,     \
-                            bag_weight, nnz, n_bags, rows, n, out, failed))
-  ESR_BAG_DISPATCH(G, ESR_BAG_SUM_LAUNCH)
-#undef ESR_BAG_SUM_LAUNCH
+  const int G = row4_lanes(D), grid = grid_for_groups(n, G);
+  ESR_DISPATCH_G(G, ESR_KT("bag_sum", st,
+                           hipLaunchKernelGGL(bag_sum_kernel<GG>, dim3(grid), dim3(kBlock), 0, st, table, nf, D, bag_offsets,
+                                              bag_feat, bag_weight, nnz, n_bags, rows, n, out, failed)));
   return check_launch(who);
 }
 
@@ -217,16 +197,11 @@ int esr_bag_expand(const float* table, int64_t nf, int D, const int64_t* bag_off
   ESR_REQUIRE(rows || n <= n_bags, "%s: n=%lld exceeds n_bags=%lld without rows", who, (long long)n, (long long)n_bags);
   if (n == 0) return ESR_OK;
   hipStream_t st = as_stream(stream);
-  int G = 1;
-  while (G < D / 4) G <<= 1;
-  const int grid = grid_for_groups(n, G);
-#define ESR_BAG_EXPAND_LAUNCH(GG)                                                                                           \
-  ESR_KT("bag_expand", st,                                                                                                  \
-         hipLaunchKernelGGL(bag_expand_kernel<GG>, dim3(grid), dim3(kBlock), 0, st, table, nf, D, bag_offsets, bag_feat,    \
-                            bag_weight, nnz, n_bags, rows, grad_rows, valid, out_offsets, n, M, reg, out_feat, out_grads,   \
-                            failed))
-  ESR_BAG_DISPATCH(G, ESR_BAG_EXPAND_LAUNCH)
-#undef ESR_BAG_EXPAND_LAUNCH
+  const int G = row4_lanes(D), grid = grid_for_groups(n, G);
+  ESR_DISPATCH_G(G, ESR_KT("bag_expand", st,
+                           hipLaunchKernelGGL(bag_expand_kernel<GG>, dim3(grid), dim3(kBlock), 0, st, table, nf, D, bag_offsets,
+                                              bag_feat, bag_weight, nnz, n_bags, rows, grad_rows, valid, out_offsets, n, M, reg,
+                                              out_feat, out_grads, failed)));
   return check_launch(who);
 }
 

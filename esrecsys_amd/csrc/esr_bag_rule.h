@@ -14,18 +14,11 @@
 #include <math.h>
 #include <stdint.h>
 
-#ifndef ESR_HD
-#if defined(__HIPCC__)
-#define ESR_HD __host__ __device__
-#else
-#define ESR_HD
-#endif
-#endif
+#include "esr_row4.h"
 
 namespace esr {
 
-constexpr int kBagMaxRank = 128;      // 32 lanes x one float4, BPR's geometry
-constexpr int kBagRankMultiple = 4;
+constexpr int kBagMaxRank = kRow4MaxRank, kBagRankMultiple = kRow4RankMultiple;  // (tests/host name these)
 constexpr int kBagFailBad = 1 << 30;  // as FAIL_BAD_POSITION of esr_als.hip
 constexpr int kBagUnroll = 4;         // feature rows whose loads the sum kernel issues together (the fmaf chain keeps its order)
 

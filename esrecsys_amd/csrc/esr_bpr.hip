@@ -7,9 +7,8 @@
 // and added to dropped[k] by one integer atomic per wave.  Integer arithmetic only; the only loops are the 15 candidates
 // and the 31-probe binary search; no workgroup waits on another and nothing is polled.
 //
-// Forward / backward.  One triple per group of G lanes, G the power of two >= D / 4 (1 .. 32): lane l of the group holds
-// elements 4 l .. 4 l + 3 of the three rows as one float4 each (lanes with 4 l >= D hold zeros), so every row load and
-// every gradient store is 16 bytes per lane and 64 / G triples share a wave.
+// Forward / backward.  One triple per group of G lanes in the float4 row-group layout of esr_row4.h: lane l of the group
+// holds elements 4 l .. 4 l + 3 of the three rows as one float4 each.
 //   Summation order of d = sum_k x[k] (yi[k] - yj[k]), a function of D alone: per lane the chain
 //   fmaf(x[e], yi[e] - yj[e], acc) over e = 0, 1, 2, 3 from acc = 0; then the butterfly over the G lanes with strides
 //   1, 2, 4, ... G / 2 (v + value of lane ^ stride), which leaves the same bits in every lane of the group.
@@ -19,11 +18,10 @@
 // and no grid-wide pass; the step's loss is summed from loss_t by the caller.
 #include "esr_bpr_sample.h"
 #include "esr_common.h"
+#include "esr_row4.h"
 
 namespace esr {
 
-constexpr int kBprMaxRank = 128;       // 32 lanes x one float4
-constexpr int kBprRankMultiple = 4;
 constexpr int kBprFailBadPosition = 1 << 30;  // as FAIL_BAD_POSITION of esr_als.hip
 constexpr int64_t kBprMaxSampleBlocks = (int64_t)kMaxGrid * 16;
 
@@ -60,12 +58,11 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_bwd_kernel(const float* __rest
                                                              int64_t B, float reg, float* __restrict__ loss_t,
                                                              float* __restrict__ diff_t, float* __restrict__ grads,
                                                              int32_t* __restrict__ failed) {
-  constexpr int kGroups = kBlock / G;
-  const int lig = threadIdx.x % G, nvec = D >> 2;
-  const bool holds = lig < nvec;  // (D = 100: 25 of the 32 lanes hold a chunk)
-  const int64_t ngroups = (int64_t)gridDim.x * kGroups;
-  for (int64_t t = (int64_t)blockIdx.x * kGroups + threadIdx.x / G; t < B; t += ngroups) {  // (uniform per group)
-    float4 gu = make_float4(0.f, 0.f, 0.f, 0.f), gi = gu, gj = gu;
+  const int lig = row4_lig<G>();
+  const bool holds = row4_holds(lig, D);
+  const int64_t ngroups = row4_stride<G>();
+  for (int64_t t = row4_first<G>(); t < B; t += ngroups) {  // (uniform per group)
+    float4 gu = row4_zero(), gi = gu, gj = gu;
     float loss = 0.f, d = 0.f;
     if (!valid || valid[t] != 0) {
       const int64_t u = us[t], i = is[t], j = js[t];
@@ -74,9 +71,9 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_bwd_kernel(const float* __rest
       } else {
         float4 x = gu, yi = gu, yj = gu;
         if (holds) {
-          x = *reinterpret_cast<const float4*>(user_table + u * D + 4 * lig);
-          yi = *reinterpret_cast<const float4*>(item_table + i * D + 4 * lig);
-          yj = *reinterpret_cast<const float4*>(item_table + j * D + 4 * lig);
+          x = *row4_ptr(user_table, u, D, lig);
+          yi = *row4_ptr(item_table, i, D, lig);
+          yj = *row4_ptr(item_table, j, D, lig);
         }
         const float4 df = make_float4(yi.x - yj.x, yi.y - yj.y, yi.z - yj.z, yi.w - yj.w);
         float acc = __fmaf_rn(x.x, df.x, 0.f);
@@ -87,20 +84,14 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_bwd_kernel(const float* __rest
         const float e = expf(-fabsf(d));
         loss = fmaxf(-d, 0.f) + log1pf(e);
         const float g = __fdiv_rn(d >= 0.f ? e : 1.0f, 1.0f + e);  // sigmoid(-d)
-        gu = make_float4(reg * x.x - g * df.x, reg * x.y - g * df.y, reg * x.z - g * df.z, reg * x.w - g * df.w);
-        gi = make_float4(reg * yi.x - g * x.x, reg * yi.y - g * x.y, reg * yi.z - g * x.z, reg * yi.w - g * x.w);
-        gj = make_float4(reg * yj.x + g * x.x, reg * yj.y + g * x.y, reg * yj.z + g * x.z, reg * yj.w + g * x.w);
+        triple_grads(x, yi, yj, g, reg, gu, gi, gj);
       }
     }
     if (lig == 0) {
       loss_t[t] = loss;
       if (diff_t) diff_t[t] = d;
     }
-    if (grads && holds) {  // [user rows ; positive rows ; negative rows], one row per occurrence
-      *reinterpret_cast<float4*>(grads + t * D + 4 * lig) = gu;
-      *reinterpret_cast<float4*>(grads + (B + t) * D + 4 * lig) = gi;
-      *reinterpret_cast<float4*>(grads + (2 * B + t) * D + 4 * lig) = gj;
-    }
+    triple_store(grads, t, B, D, lig, holds, gu, gi, gj);
   }
 }
 
@@ -113,8 +104,8 @@ extern "C" {
 int esr_bpr_geometry(int* max_tries, int* max_rank, int* rank_multiple) {
   ESR_REQUIRE(max_tries && max_rank && rank_multiple, "esr_bpr_geometry: null pointer");
   *max_tries = kBprMaxTries;
-  *max_rank = kBprMaxRank;
-  *rank_multiple = kBprRankMultiple;
+  *max_rank = kRow4MaxRank;
+  *rank_multiple = kRow4RankMultiple;
   return ESR_OK;
 }
 
@@ -151,8 +142,8 @@ int esr_bpr_fwd_bwd(const float* user_table, int64_t nu, const float* item_table
                     float* diff_t, float* grads, int32_t* failed, esr_stream_t stream) {
   TraceScope trace_scope_("esr_bpr_fwd_bwd");
   const char* who = "esr_bpr_fwd_bwd";
-  ESR_REQUIRE(D >= kBprRankMultiple && D <= kBprMaxRank && D % kBprRankMultiple == 0,
-              "%s: D=%d is not a multiple of %d in [%d, %d]", who, D, kBprRankMultiple, kBprRankMultiple, kBprMaxRank);
+  ESR_REQUIRE(D >= kRow4RankMultiple && D <= kRow4MaxRank && D % kRow4RankMultiple == 0,
+              "%s: D=%d is not a multiple of %d in [%d, %d]", who, D, kRow4RankMultiple, kRow4RankMultiple, kRow4MaxRank);
   ESR_REQUIRE(nu >= 1 && nu <= (int64_t)INT32_MAX && ni >= 1 && ni <= (int64_t)INT32_MAX && B >= 1 && B <= (int64_t)INT32_MAX,
               "%s: bad sizes nu=%lld ni=%lld B=%lld (each in [1, 2^31 - 1])", who, (long long)nu, (long long)ni, (long long)B);
   ESR_REQUIRE(reg >= 0.f && reg <= 3.0e38f, "%s: reg=%g must be finite and not negative", who, (double)reg);
@@ -162,22 +153,10 @@ int esr_bpr_fwd_bwd(const float* user_table, int64_t nu, const float* item_table
                     (uintptr_t)failed) & 3) == 0,
               "%s: misaligned pointer (tables and grads: 16 bytes)", who);
   hipStream_t st = as_stream(stream);
-  int G = 1;
-  while (G < D / 4) G <<= 1;
-  const int grid = grid_for_groups(B, G);
-#define ESR_BPR_LAUNCH(GG)                                                                                                  \
-  ESR_KT("bpr_fwd_bwd", st,                                                                                                 \
-         hipLaunchKernelGGL(bpr_fwd_bwd_kernel<GG>, dim3(grid), dim3(kBlock), 0, st, user_table, nu, item_table, ni, D, u, i, \
-                            j, valid, B, reg, loss_t, diff_t, grads, failed))
-  switch (G) {
-    case 1: ESR_BPR_LAUNCH(1); break;
-    case 2: ESR_BPR_LAUNCH(2); break;
-    case 4: ESR_BPR_LAUNCH(4); break;
-    case 8: ESR_BPR_LAUNCH(8); break;
-    case 16: ESR_BPR_LAUNCH(16); break;
-    default: ESR_BPR_LAUNCH(32); break;
-  }
-#undef ESR_BPR_LAUNCH
+  const int G = row4_lanes(D), grid = grid_for_groups(B, G);
+  ESR_DISPATCH_G(G, ESR_KT("bpr_fwd_bwd", st,
+                           hipLaunchKernelGGL(bpr_fwd_bwd_kernel<GG>, dim3(grid), dim3(kBlock), 0, st, user_table, nu, item_table,
+                                              ni, D, u, i, j, valid, B, reg, loss_t, diff_t, grads, failed)));
   return check_launch(who);
 }
 

@@ -35,12 +35,12 @@
 
 #include "esr_bpr_sample.h"
 #include "esr_philox.h"
+#include "esr_row4.h"
 
 namespace esr {
 
 constexpr int kWarpMaxTrials = 255;  // candidate c is word c + 1 of the slot's stream: blocks 0 .. 63
-constexpr int kWarpMaxRank = 128;    // 32 lanes x one float4
-constexpr int kWarpRankMultiple = 4;
+constexpr int kWarpMaxRank = kRow4MaxRank, kWarpRankMultiple = kRow4RankMultiple;  // (tests/host name these)
 
 struct WarpPair {
   int32_t u, i;
@@ -91,16 +91,9 @@ ESR_HD inline int64_t warp_rank(uint32_t ni, int64_t row_len, int32_t N) {
   return r < 1 ? 1 : r;
 }
 
-// The power of two >= D / 4: the lanes of one slot.
-ESR_HD inline int warp_lanes(int D) {
-  int G = 1;
-  while (G < D / 4) G <<= 1;
-  return G;
-}
-
 // Step 2 whole, as the kernel's lanes compute it: x and y hold D floats.
 ESR_HD inline float warp_row_dot(const float* x, const float* y, int D) {
-  const int G = warp_lanes(D), nvec = D >> 2;
+  const int G = row4_lanes(D), nvec = D >> 2;
   float v[32], n[32];
   for (int l = 0; l < G; ++l)
     v[l] = l < nvec ? warp_lane_dot(x[4 * l], x[4 * l + 1], x[4 * l + 2], x[4 * l + 3], y[4 * l], y[4 * l + 1], y[4 * l + 2],

@@ -32,6 +32,9 @@ that is trained on the ranking itself: Bayesian Personalised Ranking over triple
 by the row-sparse engine; ``WARP`` (last) is BPR's model trained with the rank-weighted margin loss, its negatives searched
 for on the device by one fused call (esr_warp.hip).  ``HybridBPR`` is BPR over users and items that are weighted sums of
 feature embeddings (esr_bag.hip): side information and cold start.
+
+All five derive from ``_Factorization`` (device, indexed pairs, ``score`` / ``recommend`` / ``from_documents``); ``_ALS`` holds
+what the two alternating models share, ``BPR`` the step tail and the update of the three triple models.
 """
 import math
 
@@ -44,7 +47,8 @@ from .wikipedia.neighbours import MAX_K
 
 CENTERS = ("user", "global", "none")
 RETRIEVE_LIMIT = 1024        # the k of ops.retrieve_topk
-FAIL_BAD_POSITION = 1 << 30  # esr_als.hip: a column outside the other side's table
+FAIL_BAD_POSITION = 1 << 30  # esr_als.hip, esr_bpr.hip, esr_warp.hip, esr_bag.hip: a position outside its table
+FAIL_BAD_WEIGHT = 1 << 29    # esr_als.hip: a weight that is negative or not finite
 
 
 class FactorizationError(RuntimeError):
@@ -57,120 +61,89 @@ def max_rank():
     return ops.als_max_rank()
 
 
+def _raise_failed(word, side):
+    """The failure word of a row solve as a ``FactorizationError``: bit 30, bit 29, else the count of unsolved rows."""
+    if word & FAIL_BAD_POSITION:
+        raise FactorizationError("the %s half-sweep met a position outside the other side's table" % side)
+    if word & FAIL_BAD_WEIGHT:
+        raise FactorizationError("the %s half-sweep met a weight that is negative or not finite (bit 29)" % side)
+    if word:
+        raise FactorizationError("the %s half-sweep could not solve %d row(s): a pivot that is not finite and positive "
+                                 "(are the other side's factors finite?); those rows were left unchanged" % (side, word))
+
+
+def _host_offsets(counts):
+    """Contiguous host int64[n + 1]: 0 and the running sums of `counts` (a tensor or an array)."""
+    if isinstance(counts, torch.Tensor):
+        counts = counts.cpu().numpy()
+    return np.ascontiguousarray(np.concatenate([[0], np.cumsum(counts.astype(np.int64))]).astype(np.int64))
+
+
 def _csr(major, minor, n_major):
     """(host row offsets int64[n_major + 1], order): the rows sorted by (major, minor) -- torch plumbing."""
     key = (major.to(torch.int64) << 32) | minor.to(torch.int64)
     key, order = torch.sort(key)
-    counts = torch.bincount(major.to(torch.int64), minlength=n_major)
-    offsets = np.concatenate([[0], np.cumsum(counts.cpu().numpy().astype(np.int64))]).astype(np.int64)
-    return key, np.ascontiguousarray(offsets), order
+    return key, _host_offsets(torch.bincount(major.to(torch.int64), minlength=n_major)), order
 
 
-class RatingsALS:
-    """See the module text.  ``users`` / ``items``: int32 ascending ids; ``user_factors`` / ``item_factors``: float32
-    [nu, rank] / [ni, rank]; ``user_mean``: float64[nu], the offset c."""
+def _ids_and_offsets(indices, doc_offsets, dev):
+    """(ids int64 on `dev`, host offsets int64[ndocs + 1]) of an id-document CSR given as host arrays or tensors."""
+    ids = _tensor(indices, "indices")
+    if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        raise TypeError("indices must be an integer array")
+    off = doc_offsets.detach().cpu().numpy() if isinstance(doc_offsets, torch.Tensor) else np.asarray(doc_offsets)
+    if off.dtype.kind not in "iu":
+        raise TypeError("doc_offsets must be an integer array")
+    off = np.ascontiguousarray(off.reshape(-1).astype(np.int64))
+    ids = ids.reshape(-1).to(dev).to(torch.int64)
+    if off.size < 1 or int(off[0]) != 0 or int(off[-1]) != ids.numel() or bool((np.diff(off) < 0).any()):
+        raise ValueError("doc_offsets must ascend from 0 to the %d ids of indices" % ids.numel())
+    return ids, off
 
-    def __init__(self, user, item, rating, rank=32, reg=0.1, weighted_reg=True, center="user", seed=0, init_scale=None,
-                 device=None, max_rows_per_launch=None):
-        rank = int(rank)
-        if not 1 <= rank <= max_rank():
-            raise ValueError("rank = %d outside [1, %d]" % (rank, max_rank()))
-        reg = float(reg)
-        if not (math.isfinite(reg) and reg > 0.0 and float(np.float32(reg)) > 0.0 and math.isfinite(float(np.float32(reg)))):
-            raise ValueError("reg = %r must be finite and positive (a row with fewer ratings than rank is singular "
-                             "without it)" % (reg,))
-        if center not in CENTERS:
-            raise ValueError("center must be 'user', 'global' or 'none', got %r" % (center,))
-        if max_rows_per_launch is not None and int(max_rows_per_launch) < 1:
-            raise ValueError("max_rows_per_launch = %r below 1" % (max_rows_per_launch,))
-        user, item, rating = _tensor(user, "user"), _tensor(item, "item"), _tensor(rating, "rating")
-        _same_length("user, item and rating", user, item, rating)
+
+class _Factorization:
+    """What the five models share (the module text).  A subclass provides ``user_factors`` / ``item_factors``."""
+
+    def _set_device(self, user, item, device):
+        """The last two refusals of every constructor that need no device work: integer ids, a CUDA device."""
         if user.dtype.is_floating_point or item.dtype.is_floating_point:
             raise TypeError("user and item must be integer arrays")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise TypeError("device must be a CUDA/ROCm device (no CPU fallback exists)")
-        self.rank, self.reg, self.weighted_reg, self.center, self.seed = rank, reg, bool(weighted_reg), center, int(seed)
-        self.max_rows_per_launch = None if max_rows_per_launch is None else int(max_rows_per_launch)
-        self.init_scale = float(rank) ** -0.5 if init_scale is None else float(init_scale)
-        dev = self.device
-        with torch.cuda.device(dev):
-            user, item = user.to(dev).to(torch.int64), item.to(dev).to(torch.int64)
-            rating64 = rating.to(device=dev, dtype=torch.float64)
-            if user.numel() and (int(user.min()) < 0 or int(item.min()) < 0 or int(user.max()) >= 2 ** 31 - 1
-                                 or int(item.max()) >= 2 ** 31 - 1):
-                raise ValueError("user and item ids must lie in [0, 2^31 - 1)")
-            users, upos = torch.unique(user, return_inverse=True)
-            items, ipos = torch.unique(item, return_inverse=True)
-            nu, ni = int(users.numel()), int(items.numel())
-            self.users, self.items = users.to(torch.int32).contiguous(), items.to(torch.int32).contiguous()
-            if center == "user":
-                _, mean, _ = rating_deviations(user, rating64, frac_bits=0)
-            elif center == "global":
-                # (divided on the host: a tensor divided by a scalar is multiplied by its reciprocal on the device)
-                g = float(rating64.sum()) / rating64.numel() if rating64.numel() else 0.0
-                mean = torch.full((nu,), g, dtype=torch.float64, device=dev)
-            else:
-                mean = torch.zeros(nu, dtype=torch.float64, device=dev)
-            self.user_mean = mean.contiguous()
-            d = (rating64 - self.user_mean[upos]).to(torch.float32)
-            # CSR by user (items ascending) and by item (users ascending)
-            key, self._user_offsets, order = _csr(upos, ipos, nu)
-            if key.numel() > 1 and bool((key[1:] == key[:-1]).any()):
-                raise ValueError("a (user, item) is rated twice: keep one rating per pair (latest_ratings)")
-            self._key = key                                             # upos << 32 | ipos, ascending: the training pairs
-            self._row_upos = (key >> 32).to(torch.int32).contiguous()
-            self._row_ipos = (key & 0xFFFFFFFF).to(torch.int32).contiguous()
-            self._targets = d[order].contiguous()
-            _, self._item_offsets, order_i = _csr(ipos, upos, ni)
-            self._col_upos = upos[order_i].to(torch.int32).contiguous()
-            self._targets_by_item = d[order_i].contiguous()
-            gen = torch.Generator(device="cpu").manual_seed(self.seed)
-            self.item_factors = (torch.randn(ni, rank, generator=gen) * self.init_scale).to(dev).contiguous()
-            self.user_factors = torch.zeros(nu, rank, dtype=torch.float32, device=dev)
-            self._failed = torch.zeros(1, dtype=torch.int32, device=dev)
 
-    nnz = property(lambda self: int(self._targets.numel()))
+    def _index_pairs(self, user, item):
+        """``users`` / ``items`` (int32 ascending) of the raw ids; returns (user int64 on the device, upos, ipos int64)."""
+        user, item = user.to(self.device).to(torch.int64), item.to(self.device).to(torch.int64)
+        if user.numel() and (int(user.min()) < 0 or int(item.min()) < 0 or int(user.max()) >= 2 ** 31 - 1
+                             or int(item.max()) >= 2 ** 31 - 1):
+            raise ValueError("user and item ids must lie in [0, 2^31 - 1)")
+        users, upos = torch.unique(user, return_inverse=True)
+        items, ipos = torch.unique(item, return_inverse=True)
+        self.users, self.items = users.to(torch.int32).contiguous(), items.to(torch.int32).contiguous()
+        return user, upos, ipos
 
-    # ---- the fit --------------------------------------------------------------------------------------------------------
-    def _half_sweep(self, other, offsets, cols, targets, out, side):
-        n_rows = offsets.size - 1
-        step = n_rows if self.max_rows_per_launch is None else self.max_rows_per_launch
-        with torch.cuda.device(self.device):
-            self._failed.zero_()
-            for a in range(0, n_rows, max(step, 1)):
-                ops.als_solve_rows(other, offsets, cols, targets, a, min(a + step, n_rows), self.reg, self.weighted_reg, out,
-                                   self._failed)
-            word = int(self._failed.item())
-        if word & FAIL_BAD_POSITION:
-            raise FactorizationError("the %s half-sweep met a position outside the other side's table" % side)
-        if word:
-            raise FactorizationError("the %s half-sweep could not solve %d row(s): a pivot that is not finite and positive "
-                                     "(are the other side's factors finite?); those rows were left unchanged" % (side, word))
+    def _set_pairs(self, key, user_offsets):
+        """The CSR by user of the distinct pairs: `key` = upos << 32 | ipos ascending, its host row offsets."""
+        self._key, self._user_offsets = key, user_offsets
+        self._row_upos = (key >> 32).to(torch.int32).contiguous()
+        self._row_ipos = (key & 0xFFFFFFFF).to(torch.int32).contiguous()
+        self._failed = torch.zeros(1, dtype=torch.int32, device=self.device)
 
-    def solve_users(self):
-        self._half_sweep(self.item_factors, self._user_offsets, self._row_ipos, self._targets, self.user_factors, "user")
+    def _raise_bad_position(self, what):
+        """Reads the failure word; bit 30 raises ``FactorizationError(what)``."""
+        if int(self._failed.item()) & FAIL_BAD_POSITION:
+            raise FactorizationError(what)
 
-    def solve_items(self):
-        self._half_sweep(self.user_factors, self._item_offsets, self._col_upos, self._targets_by_item, self.item_factors,
-                         "item")
+    @classmethod
+    def from_documents(cls, indices, doc_offsets, **kw):
+        """The model of id documents ``indices[doc_offsets[d]:doc_offsets[d + 1]]``: the user is the document number.  An id
+        repeated within d is a repeated event: ``ImplicitALS`` adds the strengths (without `strength`: the id's occurrence
+        count in d), ``BPR`` and its subclasses keep one seen pair."""
+        ids, off = _ids_and_offsets(indices, doc_offsets, torch.device("cpu"))
+        docs = torch.from_numpy(np.repeat(np.arange(off.size - 1, dtype=np.int64), np.diff(off)))
+        return cls(docs, ids, **kw)
 
-    def sweep(self):
-        """One user half-sweep, then one item half-sweep."""
-        self.solve_users()
-        self.solve_items()
-
-    def fit(self, sweeps=10):
-        """`sweeps` sweeps; returns the objective after every half-sweep (2 per sweep), a list of float."""
-        history = []
-        for _ in range(int(sweeps)):
-            self.solve_users()
-            history.append(self.objective())
-            self.solve_items()
-            history.append(self.objective())
-        return history
-
-    # ---- prediction -----------------------------------------------------------------------------------------------------
     def _positions(self, ids, table):
         """int32 positions of `ids` in the ascending `table`, -1 where absent.  The ids are compared as int64: one that does
         not fit int32 is absent, never wrapped onto a known id."""
@@ -184,64 +157,39 @@ class RatingsALS:
         pos = torch.searchsorted(t, ids).clamp(max=t.numel() - 1)
         return torch.where(t[pos] == ids, pos, torch.full_like(pos, -1)).to(torch.int32).contiguous()
 
-    def predict(self, users, items):
-        """float32[nq]: ``float32(c[u] + x_u . y_i)``; NaN where the user or the item is unknown."""
+    def _score(self, users, items, offset=None):
         users, items = _tensor(users, "users"), _tensor(items, "items")
         _same_length("users and items", users, items)
         with torch.cuda.device(self.device):
             return ops.als_predict(self.user_factors, self.item_factors, self._positions(users, self.users),
-                                   self._positions(items, self.items), offset=self.user_mean)
+                                   self._positions(items, self.items), offset=offset)
 
-    def residuals(self):
-        """float32[nnz]: ``float32(float64(d) - x_u . y_i)`` of the training pairs in CSR-by-user order."""
-        with torch.cuda.device(self.device):
-            return ops.als_predict(self.user_factors, self.item_factors, self._row_upos, self._row_ipos, targets=self._targets)
+    def score(self, users, items):
+        """float32[nq]: ``float32(x_u . y_i)`` (fp64 sum in ascending dimension); NaN where the user or the item is
+        unknown."""
+        return self._score(users, items)
 
-    def objective(self):
-        """J of the module text, an fp64 reduction (python float)."""
-        with torch.cuda.device(self.device):
-            res = self.residuals().to(torch.float64)
-            wu = torch.from_numpy(np.diff(self._user_offsets)).to(self.device).to(torch.float64)
-            wi = torch.from_numpy(np.diff(self._item_offsets)).to(self.device).to(torch.float64)
-            if not self.weighted_reg:
-                wu, wi = torch.ones_like(wu), torch.ones_like(wi)
-            xu = (self.user_factors.to(torch.float64) ** 2).sum(1)
-            yi = (self.item_factors.to(torch.float64) ** 2).sum(1)
-            return float((res * res).sum() + self.reg * (wu * xu).sum() + self.reg * (wi * yi).sum())
-
-    def rmse(self, users, items, ratings):
-        """Root mean squared error of ``predict`` over the pairs both of whose ids are known (NaN when there is none)."""
-        ratings = _tensor(ratings, "ratings").to(device=self.device, dtype=torch.float64)
-        pred = self.predict(users, items).to(torch.float64)
-        known = ~torch.isnan(pred)
-        if not bool(known.any()):
-            return float("nan")
-        e = pred[known] - ratings[known]
-        return float(torch.sqrt((e * e).sum() / e.numel()))
-
-    # ---- recommendation ---------------------------------------------------------------------------------------------------
-    def recommend(self, users, k=500, exclude_rated=True, slack=16):
-        """Per query user the k best items by (score descending, item id ascending), without the user's own items when
-        `exclude_rated`: (rec_ids int32[nq, k] padded with -1, rec_scores float32[nq, k] padded with 0, rec_lengths
-        int32[nq]), the shape ``UserKnn.recommend`` returns.  A score equals ``predict`` of the same pair bit for bit; an
-        unknown user gets an empty list.
-
-        Candidates are ``ops.retrieve_topk(x_u, item_factors, k', mode="exact")`` with ``k' = min(ni, k + r_max + slack)``,
-        r_max the longest rated list among the queried users (0 without `exclude_rated`); they are re-scored by the predict
-        kernel.  A k' above retrieve_topk's limit raises ``ValueError`` naming the query before any launch."""
+    def _recommend(self, users, k, slack, exclude, verb="has seen", flag="exclude_seen", offset=None):
         with torch.cuda.device(self.device):
             upos = self._positions(users, self.users).to(torch.int64)
-            return _recommend_rows(self.user_factors, self.user_mean, upos, self.item_factors, self.items, k, slack,
-                                   self._user_offsets if exclude_rated else None, self._key,
-                                   lambda q: "user %d" % int(_tensor(users, "users")[q]), "rated", "exclude_rated")
+            return _recommend_rows(self.user_factors, offset, upos, self.item_factors, self.items, k, slack,
+                                   self._user_offsets if exclude else None, self._key,
+                                   lambda q: "user %d" % int(_tensor(users, "users")[q]), verb, flag)
+
+    def recommend(self, users, k=500, exclude_seen=True, slack=16):
+        """Per query user the k best items by (score descending, item id ascending), without the user's seen items when
+        `exclude_seen`: (rec_ids int32[nq, k] padded with -1, rec_scores float32[nq, k] padded with 0, rec_lengths
+        int32[nq]) as ``RatingsALS.recommend``, by the same candidate scheme; a score equals ``score`` of the pair bit for
+        bit, an unknown user gets an empty list."""
+        return self._recommend(users, k, slack, exclude_seen)
 
 
 def _recommend_rows(factors, offset, upos, item_factors, items, k, slack, seen_offsets, seen_key, name, verb, flag):
-    """The body ``RatingsALS.recommend`` and ``ImplicitALS.recommend`` / ``recommend_documents`` share.  Query q is row
-    ``upos[q]`` (int64, -1: unknown, an empty list) of ``factors``; its score of item position i is ``ops.als_predict`` of
-    that pair with ``offset`` (float64 per row, or None).  With ``seen_offsets`` (host CSR offsets of the rows' own items)
-    the pairs of ``seen_key`` (``row << 32 | item position``, ascending) are left out.  ``name(q)``, ``verb`` and ``flag``
-    word the refusal of a query with too many candidates."""
+    """The body every ``recommend`` and ``ImplicitALS.recommend_documents`` share.  Query q is row ``upos[q]`` (int64, -1:
+    unknown, an empty list) of ``factors``; its score of item position i is ``ops.als_predict`` of that pair with ``offset``
+    (float64 per row, or None).  With ``seen_offsets`` (host CSR offsets of the rows' own items) the pairs of ``seen_key``
+    (``row << 32 | item position``, ascending) are left out.  ``name(q)``, ``verb`` and ``flag`` word the refusal of a query
+    with too many candidates."""
     k, slack = int(k), int(slack)
     if not 1 <= k <= MAX_K:
         raise ValueError("k = %d outside [1, %d]" % (k, MAX_K))
@@ -296,25 +244,174 @@ def _recommend_rows(factors, offset, upos, item_factors, items, k, slack, seen_o
     return ids, scores, lengths
 
 
+# ---- the two alternating models --------------------------------------------------------------------------------------------
+class _ALS(_Factorization):
+    """What ``RatingsALS`` and ``ImplicitALS`` share.  A subclass provides ``_solve_slice``, ``solve_users`` / ``solve_items``
+    and ``objective``."""
+
+    @staticmethod
+    def _check_rank_reg(rank, reg, why=""):
+        rank = int(rank)
+        if not 1 <= rank <= max_rank():
+            raise ValueError("rank = %d outside [1, %d]" % (rank, max_rank()))
+        reg = float(reg)
+        if not (math.isfinite(reg) and reg > 0.0 and float(np.float32(reg)) > 0.0 and math.isfinite(float(np.float32(reg)))):
+            raise ValueError("reg = %r must be finite and positive%s" % (reg, why))
+        return rank, reg
+
+    @staticmethod
+    def _check_rows_per_launch(max_rows_per_launch):
+        if max_rows_per_launch is not None and int(max_rows_per_launch) < 1:
+            raise ValueError("max_rows_per_launch = %r below 1" % (max_rows_per_launch,))
+        return None if max_rows_per_launch is None else int(max_rows_per_launch)
+
+    def _configure(self, user, item, device, rank, reg, weighted_reg, seed, init_scale, max_rows_per_launch):
+        self._set_device(user, item, device)
+        self.rank, self.reg, self.weighted_reg, self.seed = rank, reg, bool(weighted_reg), int(seed)
+        self.max_rows_per_launch = max_rows_per_launch
+        self.init_scale = float(rank) ** -0.5 if init_scale is None else float(init_scale)
+
+    def _by_item(self, values):
+        """The transposed CSR (``_item_offsets``, ``_col_upos``: users ascending within an item); returns `values` (one
+        per pair, in CSR-by-user order) in its order."""
+        _, self._item_offsets, order_i = _csr(self._row_ipos, self._row_upos, int(self.items.numel()))
+        self._col_upos = self._row_upos[order_i].contiguous()
+        return values[order_i].contiguous()
+
+    def _init_factors(self):
+        """``item_factors = randn * init_scale`` from the seeded CPU generator (the only draw), ``user_factors = 0``."""
+        gen = torch.Generator(device="cpu").manual_seed(self.seed)
+        self.item_factors = (torch.randn(int(self.items.numel()), self.rank, generator=gen)
+                             * self.init_scale).to(self.device).contiguous()
+        self.user_factors = torch.zeros(int(self.users.numel()), self.rank, dtype=torch.float32, device=self.device)
+
+    def _half_sweep(self, side, other, offsets, cols, values, out, gram=None):
+        """``_solve_slice`` (the subclass's one kernel call) per ``max_rows_per_launch`` slice, then the failure word."""
+        n_rows = offsets.size - 1
+        step = n_rows if self.max_rows_per_launch is None else self.max_rows_per_launch
+        with torch.cuda.device(self.device):
+            self._failed.zero_()
+            for a in range(0, n_rows, max(step, 1)):
+                self._solve_slice(other, gram, offsets, cols, values, a, min(a + step, n_rows), out)
+            word = int(self._failed.item())
+        _raise_failed(word, side)
+
+    def sweep(self):
+        """One user half-sweep, then one item half-sweep."""
+        self.solve_users()
+        self.solve_items()
+
+    def fit(self, sweeps=10):
+        """`sweeps` sweeps; returns the objective after every half-sweep (2 per sweep), a list of float."""
+        history = []
+        for _ in range(int(sweeps)):
+            self.solve_users()
+            history.append(self.objective())
+            self.solve_items()
+            history.append(self.objective())
+        return history
+
+    def _reg_terms(self, X, Y):
+        """(reg sum_u w_u |x_u|^2, reg sum_i w_i |y_i|^2) of the fp64 tables X, Y: w the row's pair count or 1."""
+        wu = torch.from_numpy(np.diff(self._user_offsets)).to(self.device).to(torch.float64)
+        wi = torch.from_numpy(np.diff(self._item_offsets)).to(self.device).to(torch.float64)
+        if not self.weighted_reg:
+            wu, wi = torch.ones_like(wu), torch.ones_like(wi)
+        return self.reg * (wu * (X ** 2).sum(1)).sum(), self.reg * (wi * (Y ** 2).sum(1)).sum()
+
+
+class RatingsALS(_ALS):
+    """See the module text.  ``users`` / ``items``: int32 ascending ids; ``user_factors`` / ``item_factors``: float32
+    [nu, rank] / [ni, rank]; ``user_mean``: float64[nu], the offset c."""
+
+    def __init__(self, user, item, rating, rank=32, reg=0.1, weighted_reg=True, center="user", seed=0, init_scale=None,
+                 device=None, max_rows_per_launch=None):
+        rank, reg = self._check_rank_reg(rank, reg, " (a row with fewer ratings than rank is singular without it)")
+        if center not in CENTERS:
+            raise ValueError("center must be 'user', 'global' or 'none', got %r" % (center,))
+        max_rows_per_launch = self._check_rows_per_launch(max_rows_per_launch)
+        user, item, rating = _tensor(user, "user"), _tensor(item, "item"), _tensor(rating, "rating")
+        _same_length("user, item and rating", user, item, rating)
+        self._configure(user, item, device, rank, reg, weighted_reg, seed, init_scale, max_rows_per_launch)
+        self.center = center
+        dev = self.device
+        with torch.cuda.device(dev):
+            rating64 = rating.to(device=dev, dtype=torch.float64)
+            user, upos, ipos = self._index_pairs(user, item)
+            nu = int(self.users.numel())
+            if center == "user":
+                _, mean, _ = rating_deviations(user, rating64, frac_bits=0)
+            elif center == "global":
+                # (divided on the host: a tensor divided by a scalar is multiplied by its reciprocal on the device)
+                g = float(rating64.sum()) / rating64.numel() if rating64.numel() else 0.0
+                mean = torch.full((nu,), g, dtype=torch.float64, device=dev)
+            else:
+                mean = torch.zeros(nu, dtype=torch.float64, device=dev)
+            self.user_mean = mean.contiguous()
+            d = (rating64 - self.user_mean[upos]).to(torch.float32)
+            # CSR by user (items ascending) and by item (users ascending)
+            key, user_offsets, order = _csr(upos, ipos, nu)
+            if key.numel() > 1 and bool((key[1:] == key[:-1]).any()):
+                raise ValueError("a (user, item) is rated twice: keep one rating per pair (latest_ratings)")
+            self._set_pairs(key, user_offsets)                          # the training pairs
+            self._targets = d[order].contiguous()
+            self._targets_by_item = self._by_item(self._targets)
+            self._init_factors()
+
+    nnz = property(lambda self: int(self._targets.numel()))
+
+    # ---- the fit --------------------------------------------------------------------------------------------------------
+    def _solve_slice(self, other, gram, offsets, cols, targets, a, b, out):
+        ops.als_solve_rows(other, offsets, cols, targets, a, b, self.reg, self.weighted_reg, out, self._failed)
+
+    def solve_users(self):
+        self._half_sweep("user", self.item_factors, self._user_offsets, self._row_ipos, self._targets, self.user_factors)
+
+    def solve_items(self):
+        self._half_sweep("item", self.user_factors, self._item_offsets, self._col_upos, self._targets_by_item,
+                         self.item_factors)
+
+    # ---- prediction -----------------------------------------------------------------------------------------------------
+    def predict(self, users, items):
+        """float32[nq]: ``float32(c[u] + x_u . y_i)``; NaN where the user or the item is unknown."""
+        return self._score(users, items, offset=self.user_mean)
+
+    def residuals(self):
+        """float32[nnz]: ``float32(float64(d) - x_u . y_i)`` of the training pairs in CSR-by-user order."""
+        with torch.cuda.device(self.device):
+            return ops.als_predict(self.user_factors, self.item_factors, self._row_upos, self._row_ipos, targets=self._targets)
+
+    def objective(self):
+        """J of the module text, an fp64 reduction (python float)."""
+        with torch.cuda.device(self.device):
+            res = self.residuals().to(torch.float64)
+            reg_u, reg_i = self._reg_terms(self.user_factors.to(torch.float64), self.item_factors.to(torch.float64))
+            return float((res * res).sum() + reg_u + reg_i)
+
+    def rmse(self, users, items, ratings):
+        """Root mean squared error of ``predict`` over the pairs both of whose ids are known (NaN when there is none)."""
+        ratings = _tensor(ratings, "ratings").to(device=self.device, dtype=torch.float64)
+        pred = self.predict(users, items).to(torch.float64)
+        known = ~torch.isnan(pred)
+        if not bool(known.any()):
+            return float("nan")
+        e = pred[known] - ratings[known]
+        return float(torch.sqrt((e * e).sum() / e.numel()))
+
+    # ---- recommendation ---------------------------------------------------------------------------------------------------
+    def recommend(self, users, k=500, exclude_rated=True, slack=16):
+        """Per query user the k best items by (score descending, item id ascending), without the user's own items when
+        `exclude_rated`: (rec_ids int32[nq, k] padded with -1, rec_scores float32[nq, k] padded with 0, rec_lengths
+        int32[nq]), the shape ``UserKnn.recommend`` returns.  A score equals ``predict`` of the same pair bit for bit; an
+        unknown user gets an empty list.
+
+        Candidates are ``ops.retrieve_topk(x_u, item_factors, k', mode="exact")`` with ``k' = min(ni, k + r_max + slack)``,
+        r_max the longest rated list among the queried users (0 without `exclude_rated`); they are re-scored by the predict
+        kernel.  A k' above retrieve_topk's limit raises ``ValueError`` naming the query before any launch."""
+        return self._recommend(users, k, slack, exclude_rated, "rated", "exclude_rated", offset=self.user_mean)
+
+
 # ---- implicit feedback ---------------------------------------------------------------------------------------------------
-FAIL_BAD_WEIGHT = 1 << 29    # esr_als.hip: a weight that is negative or not finite
-
-
-def _ids_and_offsets(indices, doc_offsets, dev):
-    """(ids int64 on `dev`, host offsets int64[ndocs + 1]) of an id-document CSR given as host arrays or tensors."""
-    ids = _tensor(indices, "indices")
-    if ids.dtype.is_floating_point or ids.dtype == torch.bool:
-        raise TypeError("indices must be an integer array")
-    off = doc_offsets.detach().cpu().numpy() if isinstance(doc_offsets, torch.Tensor) else np.asarray(doc_offsets)
-    if off.dtype.kind not in "iu":
-        raise TypeError("doc_offsets must be an integer array")
-    off = np.ascontiguousarray(off.reshape(-1).astype(np.int64))
-    ids = ids.reshape(-1).to(dev).to(torch.int64)
-    if off.size < 1 or int(off[0]) != 0 or int(off[-1]) != ids.numel() or bool((np.diff(off) < 0).any()):
-        raise ValueError("doc_offsets must ascend from 0 to the %d ids of indices" % ids.numel())
-    return ids, off
-
-
 def _sum_events(major, minor, strength, n_major, alpha):
     """Events (major, minor, strength float64) with repeats -> (key int64 ascending and distinct, major << 32 | minor; host
     row offsets int64[n_major + 1]; w float32 = float32(alpha * the pair's strengths summed in fp64 in the events' order)).
@@ -330,12 +427,10 @@ def _sum_events(major, minor, strength, n_major, alpha):
     else:
         sums = np.zeros(0, np.float64)
     w = (np.float64(alpha) * sums).astype(np.float32)
-    rows = torch.bincount(ukey >> 32, minlength=n_major)
-    offsets = np.concatenate([[0], np.cumsum(rows.cpu().numpy().astype(np.int64))]).astype(np.int64)
-    return ukey, np.ascontiguousarray(offsets), torch.from_numpy(w).to(dev)
+    return ukey, _host_offsets(torch.bincount(ukey >> 32, minlength=n_major)), torch.from_numpy(w).to(dev)
 
 
-class ImplicitALS:
+class ImplicitALS(_ALS):
     """Confidence-weighted matrix factorisation of implicit feedback (Hu, Koren, Volinsky 2008) by ALS on the GPU.
 
         model = ImplicitALS.from_documents(indices, doc_offsets, rank=32, alpha=40.0)   # user = document, strength = count
@@ -358,57 +453,30 @@ class ImplicitALS:
 
     def __init__(self, user, item, strength=None, rank=32, reg=0.01, alpha=40.0, weighted_reg=False, seed=0, init_scale=None,
                  device=None, max_rows_per_launch=None):
-        rank = int(rank)
-        if not 1 <= rank <= max_rank():
-            raise ValueError("rank = %d outside [1, %d]" % (rank, max_rank()))
-        reg = float(reg)
-        if not (math.isfinite(reg) and reg > 0.0 and float(np.float32(reg)) > 0.0 and math.isfinite(float(np.float32(reg)))):
-            raise ValueError("reg = %r must be finite and positive" % (reg,))
+        rank, reg = self._check_rank_reg(rank, reg)
         alpha = float(alpha)
         if not (math.isfinite(alpha) and alpha > 0.0):
             raise ValueError("alpha = %r must be finite and positive" % (alpha,))
-        if max_rows_per_launch is not None and int(max_rows_per_launch) < 1:
-            raise ValueError("max_rows_per_launch = %r below 1" % (max_rows_per_launch,))
+        max_rows_per_launch = self._check_rows_per_launch(max_rows_per_launch)
         user, item = _tensor(user, "user"), _tensor(item, "item")
         if strength is None:
             _same_length("user and item", user, item)
         else:
             strength = _tensor(strength, "strength")
             _same_length("user, item and strength", user, item, strength)
-        if user.dtype.is_floating_point or item.dtype.is_floating_point:
-            raise TypeError("user and item must be integer arrays")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise TypeError("device must be a CUDA/ROCm device (no CPU fallback exists)")
-        self.rank, self.reg, self.alpha, self.weighted_reg, self.seed = rank, reg, alpha, bool(weighted_reg), int(seed)
-        self.max_rows_per_launch = None if max_rows_per_launch is None else int(max_rows_per_launch)
-        self.init_scale = float(rank) ** -0.5 if init_scale is None else float(init_scale)
-        dev = self.device
-        with torch.cuda.device(dev):
-            user, item = user.to(dev).to(torch.int64), item.to(dev).to(torch.int64)
-            if user.numel() and (int(user.min()) < 0 or int(item.min()) < 0 or int(user.max()) >= 2 ** 31 - 1
-                                 or int(item.max()) >= 2 ** 31 - 1):
-                raise ValueError("user and item ids must lie in [0, 2^31 - 1)")
+        self._configure(user, item, device, rank, reg, weighted_reg, seed, init_scale, max_rows_per_launch)
+        self.alpha = alpha
+        with torch.cuda.device(self.device):
+            user, upos, ipos = self._index_pairs(user, item)
             s64 = self._strengths(strength, user.numel())
-            users, upos = torch.unique(user, return_inverse=True)
-            items, ipos = torch.unique(item, return_inverse=True)
-            nu, ni = int(users.numel()), int(items.numel())
-            self.users, self.items = users.to(torch.int32).contiguous(), items.to(torch.int32).contiguous()
             # CSR by user (items ascending) and its transpose (users ascending); one weight per distinct pair
-            key, self._user_offsets, w = _sum_events(upos, ipos, s64, nu, alpha)
+            key, user_offsets, w = _sum_events(upos, ipos, s64, int(self.users.numel()), alpha)
             if w.numel() and not bool(torch.isfinite(w).all()):
                 raise ValueError("alpha * strength does not fit a float32")
-            self._key = key                                             # upos << 32 | ipos, ascending: the seen pairs
-            self._row_upos = (key >> 32).to(torch.int32).contiguous()
-            self._row_ipos = (key & 0xFFFFFFFF).to(torch.int32).contiguous()
+            self._set_pairs(key, user_offsets)                          # the seen pairs
             self._weights = w.contiguous()
-            _, self._item_offsets, order_i = _csr(self._row_ipos, self._row_upos, ni)
-            self._col_upos = self._row_upos[order_i].contiguous()
-            self._weights_by_item = self._weights[order_i].contiguous()
-            gen = torch.Generator(device="cpu").manual_seed(self.seed)
-            self.item_factors = (torch.randn(ni, rank, generator=gen) * self.init_scale).to(dev).contiguous()
-            self.user_factors = torch.zeros(nu, rank, dtype=torch.float32, device=dev)
-            self._failed = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._weights_by_item = self._by_item(self._weights)
+            self._init_factors()
             self._item_gram = None      # (Y^T Y, the version of item_factors it was made from): fold_in's cache
 
     def _strengths(self, strength, n):
@@ -420,36 +488,11 @@ class ImplicitALS:
             raise ValueError("every strength must be finite and positive")
         return s64
 
-    @classmethod
-    def from_documents(cls, indices, doc_offsets, **kw):
-        """The model of id documents ``indices[doc_offsets[d]:doc_offsets[d + 1]]``: the user is the document number, the
-        strength of (d, id) the id's occurrence count in d."""
-        ids, off = _ids_and_offsets(indices, doc_offsets, torch.device("cpu"))
-        docs = torch.from_numpy(np.repeat(np.arange(off.size - 1, dtype=np.int64), np.diff(off)))
-        return cls(docs, ids, None, **kw)
-
     nnz = property(lambda self: int(self._weights.numel()))
 
     # ---- the fit --------------------------------------------------------------------------------------------------------
-    def _raise(self, word, side):
-        if word & FAIL_BAD_POSITION:
-            raise FactorizationError("the %s half-sweep met a position outside the other side's table" % side)
-        if word & FAIL_BAD_WEIGHT:
-            raise FactorizationError("the %s half-sweep met a weight that is negative or not finite (bit 29)" % side)
-        if word:
-            raise FactorizationError("the %s half-sweep could not solve %d row(s): a pivot that is not finite and positive "
-                                     "(are the other side's factors finite?); those rows were left unchanged" % (side, word))
-
-    def _half_sweep(self, other, gram, offsets, cols, weights, out, side):
-        n_rows = offsets.size - 1
-        step = n_rows if self.max_rows_per_launch is None else self.max_rows_per_launch
-        with torch.cuda.device(self.device):
-            self._failed.zero_()
-            for a in range(0, n_rows, max(step, 1)):
-                ops.als_solve_rows_implicit(other, gram, offsets, cols, weights, a, min(a + step, n_rows), self.reg,
-                                            self.weighted_reg, out, self._failed)
-            word = int(self._failed.item())
-        self._raise(word, side)
+    def _solve_slice(self, other, gram, offsets, cols, weights, a, b, out):
+        ops.als_solve_rows_implicit(other, gram, offsets, cols, weights, a, b, self.reg, self.weighted_reg, out, self._failed)
 
     def _gram_of_items(self):
         """Y^T Y of the item factors, kept until they next change (solve_items, or an in-place torch write)."""
@@ -460,30 +503,15 @@ class ImplicitALS:
         return self._item_gram[0]
 
     def solve_users(self):
-        self._half_sweep(self.item_factors, self._gram_of_items(), self._user_offsets, self._row_ipos, self._weights,
-                         self.user_factors, "user")
+        self._half_sweep("user", self.item_factors, self._user_offsets, self._row_ipos, self._weights, self.user_factors,
+                         gram=self._gram_of_items())
 
     def solve_items(self):
         with torch.cuda.device(self.device):
             gram = ops.als_gram(self.user_factors)
         self._item_gram = None
-        self._half_sweep(self.user_factors, gram, self._item_offsets, self._col_upos, self._weights_by_item, self.item_factors,
-                         "item")
-
-    def sweep(self):
-        """One user half-sweep, then one item half-sweep."""
-        self.solve_users()
-        self.solve_items()
-
-    def fit(self, sweeps=10):
-        """`sweeps` sweeps; returns the objective after every half-sweep (2 per sweep), a list of float."""
-        history = []
-        for _ in range(int(sweeps)):
-            self.solve_users()
-            history.append(self.objective())
-            self.solve_items()
-            history.append(self.objective())
-        return history
+        self._half_sweep("item", self.user_factors, self._item_offsets, self._col_upos, self._weights_by_item,
+                         self.item_factors, gram=gram)
 
     def objective(self):
         """J of the class text in fp64 torch (python float), without the matrix: the cells at confidence 1 and preference 0
@@ -495,34 +523,8 @@ class ImplicitALS:
             s = (X[u] * Y[i]).sum(1)
             c = 1.0 + self._weights.to(torch.float64)
             seen = (c * (1.0 - s) ** 2 - s * s).sum()
-            wu = torch.from_numpy(np.diff(self._user_offsets)).to(self.device).to(torch.float64)
-            wi = torch.from_numpy(np.diff(self._item_offsets)).to(self.device).to(torch.float64)
-            if not self.weighted_reg:
-                wu, wi = torch.ones_like(wu), torch.ones_like(wi)
-            return float(everything + seen + self.reg * (wu * (X * X).sum(1)).sum() + self.reg * (wi * (Y * Y).sum(1)).sum())
-
-    # ---- scores and recommendation ----------------------------------------------------------------------------------------
-    _positions = RatingsALS._positions
-
-    def score(self, users, items):
-        """float32[nq]: ``float32(x_u . y_i)`` (fp64 sum in ascending dimension); NaN where the user or the item is
-        unknown."""
-        users, items = _tensor(users, "users"), _tensor(items, "items")
-        _same_length("users and items", users, items)
-        with torch.cuda.device(self.device):
-            return ops.als_predict(self.user_factors, self.item_factors, self._positions(users, self.users),
-                                   self._positions(items, self.items))
-
-    def recommend(self, users, k=500, exclude_seen=True, slack=16):
-        """Per query user the k best items by (score descending, item id ascending), without the user's seen items when
-        `exclude_seen`: (rec_ids int32[nq, k] padded with -1, rec_scores float32[nq, k] padded with 0, rec_lengths
-        int32[nq]) as ``RatingsALS.recommend``, by the same candidate scheme; a score equals ``score`` of the pair bit for
-        bit, an unknown user gets an empty list."""
-        with torch.cuda.device(self.device):
-            upos = self._positions(users, self.users).to(torch.int64)
-            return _recommend_rows(self.user_factors, None, upos, self.item_factors, self.items, k, slack,
-                                   self._user_offsets if exclude_seen else None, self._key,
-                                   lambda q: "user %d" % int(_tensor(users, "users")[q]), "has seen", "exclude_seen")
+            reg_u, reg_i = self._reg_terms(X, Y)
+            return float(everything + seen + reg_u + reg_i)
 
     # ---- new documents ------------------------------------------------------------------------------------------------------
     def _fold_in(self, indices, doc_offsets, strengths):
@@ -546,7 +548,7 @@ class ImplicitALS:
                 ops.als_solve_rows_implicit(self.item_factors, self._gram_of_items(), offsets,
                                             (key & 0xFFFFFFFF).to(torch.int32).contiguous(), w.contiguous(), 0, ndocs,
                                             self.reg, self.weighted_reg, out, self._failed)
-                self._raise(int(self._failed.item()), "fold-in")
+                _raise_failed(int(self._failed.item()), "fold-in")
             return out, key, offsets
 
     def fold_in(self, indices, doc_offsets, strengths=None):
@@ -573,7 +575,12 @@ ADAGRAD_INIT = 0.1           # optax.adagrad's initial accumulator value, as eve
 FIT_GROUP = 64               # steps per sampler launch of BPR.fit
 
 
-class BPR:
+def _step_means(sums, counts):
+    """Per step the fp64 sum divided by its count on the host; NaN for a step that counted nothing."""
+    return [float(s) / int(n) if n else float("nan") for s, n in zip(sums, counts)]
+
+
+class BPR(_Factorization):
     """Matrix factorisation trained on the ranking itself (Rendle, Freudenthaler, Gantner, Schmidt-Thieme, UAI 2009).
 
         model = BPR.from_documents(indices, doc_offsets, rank=64)       # user = document, a repeated id is one seen pair
@@ -595,7 +602,7 @@ class BPR:
                  device=None):
         user, item = self._configure(user, item, rank, reg, lr, optimizer, batch, seed, init_scale, device)
         with torch.cuda.device(self.device):
-            nu, ni = self._index_pairs(user, item)
+            nu, ni = self._index_seen(user, item)
             self._init_tables(nu, ni)
 
     def _configure(self, user, item, rank, reg, lr, optimizer, batch, seed, init_scale, device):
@@ -619,36 +626,20 @@ class BPR:
         _same_length("user and item", user, item)
         if user.numel() == 0:
             raise ValueError("no (user, item) pair: BPR needs at least one seen pair")
-        if user.dtype.is_floating_point or item.dtype.is_floating_point:
-            raise TypeError("user and item must be integer arrays")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise TypeError("device must be a CUDA/ROCm device (no CPU fallback exists)")
+        self._set_device(user, item, device)
         self.rank, self.reg, self.lr, self.optimizer, self.batch, self.seed = rank, reg, lr, optimizer, batch, int(seed)
         self.init_scale = float(rank) ** -0.5 if init_scale is None else float(init_scale)
         self.step = 0
         return user, item
 
-    def _index_pairs(self, user, item):
+    def _index_seen(self, user, item):
         """users / items, the CSR of the seen pairs on the host and on the device; returns (nu, ni)."""
-        dev = self.device
-        user, item = user.to(dev).to(torch.int64), item.to(dev).to(torch.int64)
-        if int(user.min()) < 0 or int(item.min()) < 0 or int(user.max()) >= 2 ** 31 - 1 or int(item.max()) >= 2 ** 31 - 1:
-            raise ValueError("user and item ids must lie in [0, 2^31 - 1)")
-        users, upos = torch.unique(user, return_inverse=True)
-        items, ipos = torch.unique(item, return_inverse=True)
-        nu, ni = int(users.numel()), int(items.numel())
-        self.users, self.items = users.to(torch.int32).contiguous(), items.to(torch.int32).contiguous()
+        _, upos, ipos = self._index_pairs(user, item)
+        nu = int(self.users.numel())
         key = torch.unique((upos << 32) | ipos)                     # repeated events collapse to one seen pair
-        rows = torch.bincount(key >> 32, minlength=nu)
-        self._user_offsets = np.ascontiguousarray(
-            np.concatenate([[0], np.cumsum(rows.cpu().numpy().astype(np.int64))]).astype(np.int64))
-        self._key = key                                             # upos << 32 | ipos, ascending: the seen pairs
-        self._row_upos = (key >> 32).to(torch.int32).contiguous()
-        self._row_ipos = (key & 0xFFFFFFFF).to(torch.int32).contiguous()
-        self._offsets_dev = torch.from_numpy(self._user_offsets).to(dev)    # the sampler reads the CSR on the device
-        self._failed = torch.zeros(1, dtype=torch.int32, device=dev)
-        return nu, ni
+        self._set_pairs(key, _host_offsets(torch.bincount(key >> 32, minlength=nu)))
+        self._offsets_dev = torch.from_numpy(self._user_offsets).to(self.device)    # the sampler reads the CSR on the device
+        return nu, int(self.items.numel())
 
     def _new_tables(self, nu, ni):
         """(user table [nu, rank], item table [ni, rank], their Adagrad accumulators): ``randn * init_scale`` from the seeded
@@ -663,14 +654,6 @@ class BPR:
     def _init_tables(self, nu, ni):
         self.user_factors, self.item_factors, self.user_accum, self.item_accum = self._new_tables(nu, ni)
 
-    @classmethod
-    def from_documents(cls, indices, doc_offsets, **kw):
-        """The model of id documents ``indices[doc_offsets[d]:doc_offsets[d + 1]]``: the user is the document number, every
-        distinct id of d one seen pair."""
-        ids, off = _ids_and_offsets(indices, doc_offsets, torch.device("cpu"))
-        docs = torch.from_numpy(np.repeat(np.arange(off.size - 1, dtype=np.int64), np.diff(off)))
-        return cls(docs, ids, **kw)
-
     nnz = property(lambda self: int(self._key.numel()))
 
     # ---- training -------------------------------------------------------------------------------------------------------
@@ -682,40 +665,61 @@ class BPR:
                                   self.seed if seed is None else int(seed), self.step if step0 is None else int(step0),
                                   int(K), self.batch)
 
-    def _update(self, u, i, j, grads):
-        nu, ni, B = int(self.users.numel()), int(self.items.numel()), u.numel()
+    def _apply(self, tables, accums, ids, bounds, grads):
+        """One update of the user and the item table (rows [bounds[n], bounds[n + 1]) of the stacked row space) through the
+        row-sparse engine: ``ids[0]`` index the first table, the other id tensors the second, `grads` holds one row per id
+        in that order.  Adagrad sorts and updates both at once, SGD one table after the other; no id, no launch."""
         if self.optimizer == "adagrad":
-            sorted_ids, perm = ops.segment_sort_multi([u, i, j], [0, nu, nu], nu + ni)
-            ops.sparse_adagrad_multi([self.user_factors, self.item_factors], [self.user_accum, self.item_accum],
-                                     [0, nu, nu + ni], sorted_ids, perm, grads, self.lr)
-        else:
-            sorted_ids, perm = ops.segment_sort(u, nu)
-            ops.sparse_sgd(self.user_factors, sorted_ids, perm, grads[:B], self.lr)
-            sorted_ids, perm = ops.segment_sort(ops.concat_offset_ids([i, j], [0, 0]), ni)
-            ops.sparse_sgd(self.item_factors, sorted_ids, perm, grads[B:], self.lr)
+            if grads.shape[0]:
+                sorted_ids, perm = ops.segment_sort_multi(ids, [0] + [bounds[1]] * (len(ids) - 1), bounds[2])
+                ops.sparse_adagrad_multi(tables, accums, bounds, sorted_ids, perm, grads, self.lr)
+            return
+        n0 = ids[0].numel()
+        for n, g in ((0, grads[:n0]), (1, grads[n0:])):
+            if g.shape[0]:
+                own = ids[n] if len(ids) == 2 or n == 0 else ops.concat_offset_ids(ids[1:], [0] * (len(ids) - 1))
+                sorted_ids, perm = ops.segment_sort(own, bounds[n + 1] - bounds[n])
+                ops.sparse_sgd(tables[n], sorted_ids, perm, g, self.lr)
+
+    def _update(self, u, i, j, grads):
+        nu, ni = int(self.users.numel()), int(self.items.numel())
+        self._apply([self.user_factors, self.item_factors], [self.user_accum, self.item_accum], [u, i, j], [0, nu, nu + ni],
+                    grads)
+
+    def _run_steps(self, K, what, one_step, rows=1):
+        """The tail every ``train_steps`` shares: the failure word zeroed, ``one_step(k)`` = the `rows` fp64 device scalars
+        of step k for k < K, ``step += K``, the word read (`what` words its refusal).  Returns float64[rows, K] on the host."""
+        self._failed.zero_()
+        sums = torch.empty((rows, K), dtype=torch.float64, device=self.device)
+        for k in range(K):
+            for r, value in enumerate(one_step(k)):
+                sums[r, k] = value
+        self.step += K
+        self._raise_bad_position(what)
+        return sums.cpu().numpy()
+
+    @staticmethod
+    def _check_K(K):
+        K = int(K)
+        if K < 1:
+            raise ValueError("K = %d below 1" % K)
+        return K
 
     def train_steps(self, K):
         """K steps: one sampler launch, then per step the forward / backward, the sort and the update.  Returns the mean
         loss over the valid triples of every step (an fp64 sum of the per-triple losses divided on the host; NaN for a step
         without a valid triple).  Raises ``FactorizationError`` when a kernel met a position outside its table."""
-        K = int(K)
-        if K < 1:
-            raise ValueError("K = %d below 1" % K)
+        K = self._check_K(K)
         with torch.cuda.device(self.device):
             u, i, j, valid, dropped = self.sample(K)
-            self._failed.zero_()
-            sums = torch.empty(K, dtype=torch.float64, device=self.device)
-            for k in range(K):
+
+            def one_step(k):
                 loss_t, _, grads = ops.bpr_fwd_bwd(self.user_factors, self.item_factors, u[k], i[k], j[k], valid[k], self.reg,
                                                    failed=self._failed)
                 self._update(u[k], i[k], j[k], grads)
-                sums[k] = loss_t.to(torch.float64).sum()
-            self.step += K
-            word = int(self._failed.item())
-            sums, kept = sums.cpu().numpy(), self.batch - dropped.cpu().numpy().astype(np.int64)
-        if word & FAIL_BAD_POSITION:
-            raise FactorizationError("a BPR step met a position outside its table (bit 30)")
-        return [float(s) / int(n) if n else float("nan") for s, n in zip(sums, kept)]
+                return (loss_t.to(torch.float64).sum(),)
+            sums = self._run_steps(K, "a BPR step met a position outside its table (bit 30)", one_step)
+            return _step_means(sums[0], self.batch - dropped.cpu().numpy().astype(np.int64))
 
     def fit(self, steps):
         """`steps` steps in groups of 64 (one sampler launch per group); returns every step's mean loss."""
@@ -733,18 +737,11 @@ class BPR:
             self._failed.zero_()
             _, d, _ = ops.bpr_fwd_bwd(self.user_factors, self.item_factors, u.reshape(-1), i.reshape(-1), j.reshape(-1),
                                       valid.reshape(-1), self.reg, want_grads=False, want_diff=True, failed=self._failed)
+            self._raise_bad_position("auc met a position outside its table (bit 30)")
             ok = valid.reshape(-1) != 0
             n = int(ok.sum())
             wins, ties = int(((d > 0) & ok).sum()), int(((d == 0) & ok).sum())
-            word = int(self._failed.item())
-        if word & FAIL_BAD_POSITION:
-            raise FactorizationError("auc met a position outside its table (bit 30)")
         return (wins + 0.5 * ties) / n if n else float("nan")
-
-    # ---- scores and recommendation ----------------------------------------------------------------------------------------
-    _positions = RatingsALS._positions
-    score = ImplicitALS.score
-    recommend = ImplicitALS.recommend
 
 
 # ---- WARP ---------------------------------------------------------------------------------------------------------------
@@ -817,8 +814,7 @@ class WARP(BPR):
         with torch.cuda.device(self.device):
             self._failed.zero_()
             out = self._warp_step(self.step if step is None else int(step), False)
-            if int(self._failed.item()) & FAIL_BAD_POSITION:
-                raise FactorizationError("a WARP step met a position outside its table (bit 30)")
+            self._raise_bad_position("a WARP step met a position outside its table (bit 30)")
         return out[:5]
 
     def train_steps(self, K):
@@ -826,23 +822,17 @@ class WARP(BPR):
         of every step (an fp64 sum of the per-slot losses divided on the host; NaN for a step without a valid slot) and
         appends every step's mean ``trials`` to ``mean_trials``.  Raises ``FactorizationError`` when the kernel met a
         position outside its table."""
-        K = int(K)
-        if K < 1:
-            raise ValueError("K = %d below 1" % K)
+        K = self._check_K(K)
         with torch.cuda.device(self.device):
-            self._failed.zero_()
-            sums = torch.empty((3, K), dtype=torch.float64, device=self.device)      # loss, valid slots, trials
-            for k in range(K):
-                u, i, j, valid, trials, loss_t, _, grads = self._warp_step(self.step + k, True)
+            step0 = self.step
+
+            def one_step(k):
+                u, i, j, valid, trials, loss_t, _, grads = self._warp_step(step0 + k, True)
                 self._update(u, i, j, grads)
-                sums[0, k], sums[1, k], sums[2, k] = loss_t.to(torch.float64).sum(), valid.sum(), trials.sum()
-            self.step += K
-            word = int(self._failed.item())
-            sums = sums.cpu().numpy()
-        if word & FAIL_BAD_POSITION:
-            raise FactorizationError("a WARP step met a position outside its table (bit 30)")
+                return loss_t.to(torch.float64).sum(), valid.sum(), trials.sum()
+            sums = self._run_steps(K, "a WARP step met a position outside its table (bit 30)", one_step, rows=3)
         self.mean_trials += [float(n) / self.batch for n in sums[2]]
-        return [float(s) / int(n) if n else float("nan") for s, n in zip(sums[0], sums[1])]
+        return _step_means(sums[0], sums[1])
 
 
 # ---- hybrid BPR: entities as sums of feature embeddings -----------------------------------------------------------------
@@ -880,14 +870,14 @@ def _bag_table(epos, fpos, weight, n, identity, side):
                          % (side, key[at] >> 32, key[at] & 0xFFFFFFFF))
     lead = 1 if identity else 0
     counts = np.bincount(epos, minlength=n).astype(np.int64)
-    offsets = np.concatenate([[0], np.cumsum(counts + lead)]).astype(np.int64)
+    offsets = _host_offsets(counts + lead)
     nnz = int(offsets[-1])
     if nnz < 1:
         raise ValueError("%s side: no entity has a feature" % side)
     if nnz > 2 ** 31 - 1:
         raise ValueError("%s side: %d feature occurrences exceed 2^31 - 1" % (side, nnz))
     e_sorted = key >> 32
-    starts = np.concatenate([[0], np.cumsum(counts)])[:-1]
+    starts = _host_offsets(counts)[:-1]
     at = offsets[e_sorted] + lead + (np.arange(key.size) - starts[e_sorted])
     feat = np.empty(nnz, np.int32)
     feat[at] = (key & 0xFFFFFFFF) + (n if identity else 0)
@@ -897,7 +887,7 @@ def _bag_table(epos, fpos, weight, n, identity, side):
         w[at] = weight[order]
     if identity:
         feat[offsets[:-1]] = np.arange(n, dtype=np.int32)
-    return np.ascontiguousarray(offsets), feat, w
+    return offsets, feat, w
 
 
 class _Bags:
@@ -959,7 +949,7 @@ class HybridBPR(BPR):
         user, item = self._configure(user, item, rank, reg, lr, optimizer, batch, seed, init_scale, device)
         self.identity = identity
         with torch.cuda.device(self.device):
-            nu, ni = self._index_pairs(user, item)
+            nu, ni = self._index_seen(user, item)
             (ubag, ufeat), (ibag, ifeat) = tables
             self._user_bags, self._item_bags = _Bags(*ubag, self.device), _Bags(*ibag, self.device)
             self.user_feature_ids = torch.from_numpy(ufeat).to(self.device)
@@ -999,8 +989,7 @@ class HybridBPR(BPR):
                 self._failed.zero_()
                 rows = (ops.bag_sum(self.user_embeddings, *self._user_bags.args(), failed=self._failed),
                         ops.bag_sum(self.item_embeddings, *self._item_bags.args(), failed=self._failed))
-                if int(self._failed.item()) & FAIL_BAD_POSITION:
-                    raise FactorizationError("a bag names a feature position outside its table (bit 30)")
+                self._raise_bad_position("a bag names a feature position outside its table (bit 30)")
             self._composed = (key,) + rows
         return self._composed[1:]
 
@@ -1029,16 +1018,7 @@ class HybridBPR(BPR):
         ops.bag_expand(ue, *ub.args(), u, grads[:B], valid, oo_u, Mu, self.reg, out=(fu, gu), failed=self._failed)
         ops.bag_expand(ie, *ib.args(), ij, grads[B:], valid2, oo_i, Mi, self.reg, out=(fi, gi), failed=self._failed)
         nfu, nfi = ue.shape[0], ie.shape[0]
-        if self.optimizer == "adagrad":
-            if Mu + Mi:
-                sorted_ids, perm = ops.segment_sort_multi([fu, fi], [0, nfu], nfu + nfi)
-                ops.sparse_adagrad_multi([ue, ie], [self.user_accum, self.item_accum], [0, nfu, nfu + nfi], sorted_ids, perm,
-                                         out_grads, self.lr)
-        else:
-            for table, f, g, nf in ((ue, fu, gu, nfu), (ie, fi, gi, nfi)):
-                if f.numel():
-                    sorted_ids, perm = ops.segment_sort(f, nf)
-                    ops.sparse_sgd(table, sorted_ids, perm, g, self.lr)
+        self._apply([ue, ie], [self.user_accum, self.item_accum], [fu, fi], [0, nfu, nfu + nfi], out_grads)
         return loss_t
 
     def train_steps(self, K):
@@ -1046,9 +1026,7 @@ class HybridBPR(BPR):
         per step the two compositions, the forward / backward, the two expansions, the sort and the update.  Returns
         BPR's per-step mean loss.  Raises ``ValueError`` when a step's expanded occurrences exceed 2^31 - 1 and
         ``FactorizationError`` when a kernel met a position outside its table."""
-        K = int(K)
-        if K < 1:
-            raise ValueError("K = %d below 1" % K)
+        K = self._check_K(K)
         dev, B = self.device, self.batch
         with torch.cuda.device(dev):
             u, i, j, valid, dropped = self.sample(K)
@@ -1062,19 +1040,14 @@ class HybridBPR(BPR):
                 raise ValueError("a step expands to %d feature occurrences, above 2^31 - 1: lower batch"
                                  % int((sizes[0] + sizes[1]).max()))
             ar = torch.arange(2 * B, dtype=torch.int32, device=dev)
-            self._failed.zero_()
-            sums = torch.empty(K, dtype=torch.float64, device=dev)
-            for k in range(K):
+
+            def one_step(k):
                 loss_t = self._step(u[k], ij[k], valid[k], valid2[k], oo_u[k], oo_i[k], int(sizes[0, k]), int(sizes[1, k]),
                                     ar[:B], ar[B:])
-                sums[k] = loss_t.to(torch.float64).sum()
-            self.step += K
+                return (loss_t.to(torch.float64).sum(),)
+            sums = self._run_steps(K, "a hybrid BPR step met a position outside its table (bit 30)", one_step)
             self._composed = None
-            word = int(self._failed.item())
-            sums, kept = sums.cpu().numpy(), self.batch - dropped.cpu().numpy().astype(np.int64)
-        if word & FAIL_BAD_POSITION:
-            raise FactorizationError("a hybrid BPR step met a position outside its table (bit 30)")
-        return [float(s) / int(n) if n else float("nan") for s, n in zip(sums, kept)]
+            return _step_means(sums[0], self.batch - dropped.cpu().numpy().astype(np.int64))
 
     # ---- cold start -------------------------------------------------------------------------------------------------------
     def _compose_new(self, side, entity_id, feature_id, weight):
@@ -1101,8 +1074,7 @@ class HybridBPR(BPR):
             bags = _Bags(offsets, bag_feat, w, self.device)
             self._failed.zero_()
             rows = ops.bag_sum(table, *bags.args(), failed=self._failed)
-            if int(self._failed.item()) & FAIL_BAD_POSITION:
-                raise FactorizationError("compose_%ss met a feature position outside the table (bit 30)" % side)
+            self._raise_bad_position("compose_%ss met a feature position outside the table (bit 30)" % side)
             return torch.from_numpy(ids.astype(np.int32)).to(self.device), rows
 
     def compose_items(self, entity_id, feature_id, weight=None):
@@ -1118,26 +1090,27 @@ class HybridBPR(BPR):
         """``BPR.recommend`` on the composed tables.  ``extra_items`` = the ``(ids, rows)`` of ``compose_items``: those items
         are ranked together with the known ones by the same (score descending, item id ascending) order and are never
         "seen"."""
+        if extra_items is None:
+            return self._recommend(users, k, slack, exclude_seen)
         with torch.cuda.device(self.device):
             upos = self._positions(users, self.users).to(torch.int64)
             rows, items, key = self.item_factors, self.items, self._key
-            if extra_items is not None:
-                ids, extra = extra_items
-                ids = _tensor(ids, "extra ids").to(self.device).to(torch.int64)
-                if not isinstance(extra, torch.Tensor) or extra.dtype != torch.float32 or extra.dim() != 2 or \
-                        tuple(extra.shape) != (ids.numel(), self.rank):
-                    raise ValueError("extra_items must be (ids[n], float32 rows[n, rank])")
-                both = torch.cat([items.to(torch.int64), ids])
-                if torch.unique(both).numel() != both.numel():
-                    raise ValueError("extra_items repeats an item id or names a known item")
-                if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= 2 ** 31 - 1):
-                    raise ValueError("item ids must lie in [0, 2^31 - 1)")
-                order = torch.argsort(both)
-                place = torch.empty_like(order)
-                place[order] = torch.arange(order.numel(), device=self.device)      # old position -> position by id
-                rows = torch.cat([rows, extra.to(self.device)])[order].contiguous()
-                items = both[order].to(torch.int32).contiguous()
-                key = ((key >> 32) << 32) | place[key & 0xFFFFFFFF]                 # (monotone per user: still ascending)
+            ids, extra = extra_items
+            ids = _tensor(ids, "extra ids").to(self.device).to(torch.int64)
+            if not isinstance(extra, torch.Tensor) or extra.dtype != torch.float32 or extra.dim() != 2 or \
+                    tuple(extra.shape) != (ids.numel(), self.rank):
+                raise ValueError("extra_items must be (ids[n], float32 rows[n, rank])")
+            both = torch.cat([items.to(torch.int64), ids])
+            if torch.unique(both).numel() != both.numel():
+                raise ValueError("extra_items repeats an item id or names a known item")
+            if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= 2 ** 31 - 1):
+                raise ValueError("item ids must lie in [0, 2^31 - 1)")
+            order = torch.argsort(both)
+            place = torch.empty_like(order)
+            place[order] = torch.arange(order.numel(), device=self.device)      # old position -> position by id
+            rows = torch.cat([rows, extra.to(self.device)])[order].contiguous()
+            items = both[order].to(torch.int32).contiguous()
+            key = ((key >> 32) << 32) | place[key & 0xFFFFFFFF]                 # (monotone per user: still ascending)
             return _recommend_rows(self.user_factors, None, upos, rows, items, k, slack,
                                    self._user_offsets if exclude_seen else None, key,
                                    lambda q: "user %d" % int(_tensor(users, "users")[q]), "has seen", "exclude_seen")

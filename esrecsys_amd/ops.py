@@ -1913,13 +1913,15 @@ def als_geometry():
     return int(chunk.value), int(per_wg.value)
 
 
-def als_solve_rows(other_factors, row_offsets, cols, targets, row_begin, row_end, reg, weighted, out_factors, failed):
-    """One half-sweep over the rows [row_begin, row_end): out_factors[r] = the regularised least-squares solution of row r's
-    ratings against other_factors.  row_offsets is a HOST array (numpy int64[n_rows + 1]): the library sorts the rows into
-    its three classes from it.  `failed` (int32[1], device) collects the failure word; the caller zeroes and reads it."""
+def _als_solve(name, other_factors, row_offsets, cols, values, what, row_begin, row_end, reg, weighted, out_factors,
+               failed, gram=None):
+    """What als_solve_rows and als_solve_rows_implicit share: the checks, the workspace and the one library call
+    (`gram` goes in after the rank when given)."""
     lib = _lib.load()
     _req(other_factors, torch.float32, "other_factors"), _req(out_factors, torch.float32, "out_factors")
-    _req(cols, torch.int32, "cols"), _req(targets, torch.float32, "targets"), _req(failed, torch.int32, "failed")
+    if gram is not None:
+        _req(gram, torch.float32, "gram")
+    _req(cols, torch.int32, "cols"), _req(values, torch.float32, what), _req(failed, torch.int32, "failed")
     if not isinstance(row_offsets, np.ndarray) or row_offsets.dtype != np.int64 or not row_offsets.flags.c_contiguous:
         raise TypeError("row_offsets must be a contiguous numpy int64 array (host memory)")
     row_begin, row_end = int(row_begin), int(row_end)
@@ -1928,15 +1930,25 @@ def als_solve_rows(other_factors, row_offsets, cols, targets, row_begin, row_end
     if out_factors.shape[0] < row_end or out_factors.shape[1] != other_factors.shape[1]:
         raise ValueError("out_factors %s does not hold rows up to %d of rank %d"
                          % (tuple(out_factors.shape), row_end, other_factors.shape[1]))
-    if int(row_offsets[row_end]) > cols.numel() or cols.numel() != targets.numel():
-        raise ValueError("row_offsets end at %d but there are %d cols and %d targets"
-                         % (int(row_offsets[row_end]), cols.numel(), targets.numel()))
     n_other, rank = other_factors.shape
+    if gram is not None and tuple(gram.shape) != (rank, rank):
+        raise ValueError("gram %s is not [%d, %d]" % (tuple(gram.shape), rank, rank))
+    if int(row_offsets[row_end]) > cols.numel() or cols.numel() != values.numel():
+        raise ValueError("row_offsets end at %d but there are %d cols and %d %s"
+                         % (int(row_offsets[row_end]), cols.numel(), values.numel(), what))
     nnz = int(row_offsets[row_end] - row_offsets[row_begin])
     ws = _ws(int(lib.esr_als_solve_workspace_bytes(row_end - row_begin, nnz, int(rank))), out_factors.device)
-    check(lib.esr_als_solve_rows(_p(other_factors), int(n_other), int(rank), row_offsets.ctypes.data, _p(cols), _p(targets),
-                                 row_begin, row_end, float(reg), int(bool(weighted)), _p(out_factors), _p(failed), _p(ws),
-                                 ws.numel(), _stream()), "esr_als_solve_rows")
+    check(getattr(lib, name)(_p(other_factors), int(n_other), int(rank), *(() if gram is None else (_p(gram),)), row_offsets.ctypes.data,
+                      _p(cols), _p(values), row_begin, row_end, float(reg), int(bool(weighted)), _p(out_factors), _p(failed),
+                      _p(ws), ws.numel(), _stream()), name)
+
+
+def als_solve_rows(other_factors, row_offsets, cols, targets, row_begin, row_end, reg, weighted, out_factors, failed):
+    """One half-sweep over the rows [row_begin, row_end): out_factors[r] = the regularised least-squares solution of row r's
+    ratings against other_factors.  row_offsets is a HOST array (numpy int64[n_rows + 1]): the library sorts the rows into
+    its three classes from it.  `failed` (int32[1], device) collects the failure word; the caller zeroes and reads it."""
+    _als_solve("esr_als_solve_rows", other_factors, row_offsets, cols, targets, "targets", row_begin, row_end, reg, weighted,
+               out_factors, failed)
 
 
 def als_predict(user_factors, item_factors, user_pos, item_pos, offset=None, targets=None):
@@ -1995,34 +2007,39 @@ def als_solve_rows_implicit(other_factors, gram, row_offsets, cols, weights, row
     (gram + sum_k w_k y_k y_k^T + lam I) x = sum_k (1 + w_k) y_k over row r's entries.  `gram` is als_gram(other_factors);
     row_offsets is a HOST array (numpy int64[n_rows + 1]) as in als_solve_rows; `failed` (int32[1], device) collects the
     failure word (bit 30: a column outside the table, bit 29: a weight that is negative or not finite)."""
-    lib = _lib.load()
-    _req(other_factors, torch.float32, "other_factors"), _req(out_factors, torch.float32, "out_factors")
-    _req(gram, torch.float32, "gram")
-    _req(cols, torch.int32, "cols"), _req(weights, torch.float32, "weights"), _req(failed, torch.int32, "failed")
-    if not isinstance(row_offsets, np.ndarray) or row_offsets.dtype != np.int64 or not row_offsets.flags.c_contiguous:
-        raise TypeError("row_offsets must be a contiguous numpy int64 array (host memory)")
-    row_begin, row_end = int(row_begin), int(row_end)
-    if not 0 <= row_begin <= row_end < row_offsets.size:
-        raise ValueError("rows [%d, %d) not inside the %d rows of row_offsets" % (row_begin, row_end, row_offsets.size - 1))
-    if out_factors.shape[0] < row_end or out_factors.shape[1] != other_factors.shape[1]:
-        raise ValueError("out_factors %s does not hold rows up to %d of rank %d"
-                         % (tuple(out_factors.shape), row_end, other_factors.shape[1]))
-    n_other, rank = other_factors.shape
-    if tuple(gram.shape) != (rank, rank):
-        raise ValueError("gram %s is not [%d, %d]" % (tuple(gram.shape), rank, rank))
-    if int(row_offsets[row_end]) > cols.numel() or cols.numel() != weights.numel():
-        raise ValueError("row_offsets end at %d but there are %d cols and %d weights"
-                         % (int(row_offsets[row_end]), cols.numel(), weights.numel()))
-    nnz = int(row_offsets[row_end] - row_offsets[row_begin])
-    ws = _ws(int(lib.esr_als_solve_workspace_bytes(row_end - row_begin, nnz, int(rank))), out_factors.device)
-    check(lib.esr_als_solve_rows_implicit(_p(other_factors), int(n_other), int(rank), _p(gram), row_offsets.ctypes.data,
-                                          _p(cols), _p(weights), row_begin, row_end, float(reg), int(bool(weighted)),
-                                          _p(out_factors), _p(failed), _p(ws), ws.numel(), _stream()),
-          "esr_als_solve_rows_implicit")
+    _als_solve("esr_als_solve_rows_implicit", other_factors, row_offsets, cols, weights, "weights", row_begin, row_end, reg,
+               weighted, out_factors, failed, gram=gram)
 
 
 # ---------------------------------------------------------------------------------------------
 # Bayesian Personalised Ranking (esr_bpr.hip): the triple sampler and the fused logistic forward / backward
+def _failed_word(failed, device):
+    """`failed`, or a fresh scratch word on `device` when None."""
+    if failed is None:
+        failed = torch.zeros(1, dtype=torch.int32, device=device)
+    _req(failed, torch.int32, "failed")
+    return failed
+
+
+def _check_rank4(D, top, mult):
+    if D % mult or not mult <= D <= top:
+        raise ValueError("rank = %d is not a multiple of %d in [%d, %d]" % (D, mult, mult, top))
+
+
+def _check_device_csr(who, name, offsets, row_upos, row_ipos, nu, **sizes):
+    """The CSR of seen pairs by user on the device, as bpr_sample and warp_step take it; every one of nu, nnz and `sizes` in
+    [1, 2^31 - 1].  Returns nnz."""
+    _req(offsets, torch.int64, name), _req(row_upos, torch.int32, "row_upos"), _req(row_ipos, torch.int32, "row_ipos")
+    nnz = row_upos.numel()
+    if row_ipos.numel() != nnz or offsets.numel() != nu + 1:
+        raise ValueError("%s: %s holds %d entries for nu = %d, row_upos %d and row_ipos %d pairs"
+                         % (who, name, offsets.numel(), nu, nnz, row_ipos.numel()))
+    sizes = dict(nu=nu, nnz=nnz, **sizes)
+    if not all(1 <= v <= 2 ** 31 - 1 for v in sizes.values()):
+        raise ValueError("%s: %s (each in [1, 2^31 - 1])" % (who, " ".join("%s=%d" % kv for kv in sizes.items())))
+    return nnz
+
+
 def bpr_geometry():
     """(max_tries, max_rank, rank_multiple): the negative candidates the sampler tries per triple; bpr_fwd_bwd takes a rank
     that is a multiple of rank_multiple and at most max_rank."""
@@ -2038,15 +2055,8 @@ def bpr_sample(row_offsets, row_upos, row_ipos, nu, ni, seed, step0, K, B):
     The rule is esr_bpr_sample.h's: a triple is a function of (seed, step, slot, CSR) alone; the multiply-high draws are
     biased by at most nnz / 2^32 (the pair) and ni / 2^32 (a candidate) relative."""
     lib = _lib.load()
-    _req(row_offsets, torch.int64, "row_offsets"), _req(row_upos, torch.int32, "row_upos")
-    _req(row_ipos, torch.int32, "row_ipos")
-    nu, ni, K, B, nnz = int(nu), int(ni), int(K), int(B), row_upos.numel()
-    if row_ipos.numel() != nnz or row_offsets.numel() != nu + 1:
-        raise ValueError("bpr_sample: row_offsets holds %d entries for nu = %d, row_upos %d and row_ipos %d pairs"
-                         % (row_offsets.numel(), nu, nnz, row_ipos.numel()))
-    lim = 2 ** 31 - 1
-    if not (1 <= nnz <= lim and 1 <= ni <= lim and 1 <= nu <= lim and 1 <= K <= lim and 1 <= B <= lim):
-        raise ValueError("bpr_sample: nu=%d ni=%d nnz=%d K=%d B=%d (each in [1, 2^31 - 1])" % (nu, ni, nnz, K, B))
+    nu, ni, K, B = int(nu), int(ni), int(K), int(B)
+    nnz = _check_device_csr("bpr_sample", "row_offsets", row_offsets, row_upos, row_ipos, nu, ni=ni, K=K, B=B)
     out = torch.empty((4, K, B), dtype=torch.int32, device=row_upos.device)
     dropped = torch.empty(K, dtype=torch.int32, device=row_upos.device)
     check(lib.esr_bpr_sample(_p(row_offsets), _p(row_upos), _p(row_ipos), nu, ni, nnz, int(seed) & (2 ** 64 - 1),
@@ -2073,13 +2083,9 @@ def bpr_fwd_bwd(user_table, item_table, u, i, j, valid, reg, want_grads=True, wa
         _req(valid, torch.int32, "valid")
         if valid.numel() != B:
             raise ValueError("valid must hold one entry per triple")
-    _, max_rank, mult = bpr_geometry()
-    if D % mult or not mult <= D <= max_rank:
-        raise ValueError("rank = %d is not a multiple of %d in [%d, %d]" % (D, mult, mult, max_rank))
+    _check_rank4(D, *bpr_geometry()[1:])
     dev = user_table.device
-    if failed is None:
-        failed = torch.zeros(1, dtype=torch.int32, device=dev)
-    _req(failed, torch.int32, "failed")
+    failed = _failed_word(failed, dev)
     loss_t = torch.empty(B, dtype=torch.float32, device=dev)
     diff_t = torch.empty(B, dtype=torch.float32, device=dev) if want_diff else None
     grads = torch.empty((3 * B, D), dtype=torch.float32, device=dev) if want_grads else None
@@ -2112,27 +2118,20 @@ def warp_step(user_factors, item_factors, offsets, row_upos, row_ipos, rank_weig
     bit 30 when an item position lies outside the table; the caller zeroes and reads it."""
     lib = _lib.load()
     _req(user_factors, torch.float32, "user_factors"), _req(item_factors, torch.float32, "item_factors")
-    _req(offsets, torch.int64, "offsets"), _req(row_upos, torch.int32, "row_upos"), _req(row_ipos, torch.int32, "row_ipos")
     _req(rank_weight, torch.float32, "rank_weight")
     if user_factors.dim() != 2 or item_factors.dim() != 2 or user_factors.shape[1] != item_factors.shape[1]:
         raise ValueError("user_factors and item_factors must be [n, rank] of one rank")
-    nu, ni, D, nnz, B = int(user_factors.shape[0]), int(item_factors.shape[0]), int(user_factors.shape[1]), row_upos.numel(), int(B)
-    if row_ipos.numel() != nnz or offsets.numel() != nu + 1 or rank_weight.numel() != ni + 1:
-        raise ValueError("warp_step: offsets holds %d entries for nu = %d, row_upos %d and row_ipos %d pairs, rank_weight %d "
-                         "entries for ni = %d" % (offsets.numel(), nu, nnz, row_ipos.numel(), rank_weight.numel(), ni))
-    lim = 2 ** 31 - 1
-    if not (1 <= nnz <= lim and 1 <= ni <= lim and 1 <= nu <= lim and 1 <= B <= lim):
-        raise ValueError("warp_step: nu=%d ni=%d nnz=%d B=%d (each in [1, 2^31 - 1])" % (nu, ni, nnz, B))
+    nu, ni, D, B = int(user_factors.shape[0]), int(item_factors.shape[0]), int(user_factors.shape[1]), int(B)
+    if rank_weight.numel() != ni + 1:
+        raise ValueError("warp_step: rank_weight holds %d entries for ni = %d" % (rank_weight.numel(), ni))
+    nnz = _check_device_csr("warp_step", "offsets", offsets, row_upos, row_ipos, nu, ni=ni, B=B)
     top_trials, max_rank, mult = warp_geometry()
-    if D % mult or not mult <= D <= max_rank:
-        raise ValueError("rank = %d is not a multiple of %d in [%d, %d]" % (D, mult, mult, max_rank))
+    _check_rank4(D, max_rank, mult)
     max_trials = int(max_trials)
     if not 1 <= max_trials <= top_trials:
         raise ValueError("max_trials = %d outside [1, %d]" % (max_trials, top_trials))
     dev = user_factors.device
-    if failed is None:
-        failed = torch.zeros(1, dtype=torch.int32, device=dev)
-    _req(failed, torch.int32, "failed")
+    failed = _failed_word(failed, dev)
     ids = torch.empty((5, B), dtype=torch.int32, device=dev)
     loss_t = torch.empty(B, dtype=torch.float32, device=dev)
     diff = torch.empty(B, dtype=torch.float32, device=dev) if want_diff else None
@@ -2160,9 +2159,7 @@ def _bag_args(who, table, offsets, feat, weight, rows):
     if table.dim() != 2:
         raise ValueError("%s: table must be [nf, rank]" % who)
     nf, D, nnz, n_bags = int(table.shape[0]), int(table.shape[1]), feat.numel(), offsets.numel() - 1
-    max_rank, mult = bag_geometry()
-    if D % mult or not mult <= D <= max_rank:
-        raise ValueError("rank = %d is not a multiple of %d in [%d, %d]" % (D, mult, mult, max_rank))
+    _check_rank4(D, *bag_geometry())
     if weight is not None:
         _req(weight, torch.float32, "weight")
         if weight.numel() != nnz:
@@ -2193,9 +2190,7 @@ def bag_sum(table, offsets, feat, weight, rows=None, out=None, failed=None):
     _req(out, torch.float32, "out")
     if out.numel() != n * D:
         raise ValueError("bag_sum: out must be [n, rank]")
-    if failed is None:
-        failed = torch.zeros(1, dtype=torch.int32, device=dev)
-    _req(failed, torch.int32, "failed")
+    failed = _failed_word(failed, dev)
     if n:
         check(lib.esr_bag_sum(_p(table), nf, D, _p(offsets), _p(feat), _p(weight), nnz, n_bags, _p(rows), n, _p(out),
                               _p(failed), _stream()), "esr_bag_sum")
@@ -2228,9 +2223,7 @@ def bag_expand(table, offsets, feat, weight, rows, grad_rows, valid, out_offsets
     _req(out_feat, torch.int32, "out[0]"), _req(out_grads, torch.float32, "out[1]")
     if out_feat.numel() != M or out_grads.numel() != M * D:
         raise ValueError("bag_expand: out must be (int32[M], float32[M, rank])")
-    if failed is None:
-        failed = torch.zeros(1, dtype=torch.int32, device=dev)
-    _req(failed, torch.int32, "failed")
+    failed = _failed_word(failed, dev)
     if n:
         check(lib.esr_bag_expand(_p(table), nf, D, _p(offsets), _p(feat), _p(weight), nnz, n_bags, _p(rows), _p(grad_rows),
                                  _p(valid), _p(out_offsets), n, M, float(reg), _p(out_feat), _p(out_grads), _p(failed),
