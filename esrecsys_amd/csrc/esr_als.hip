@@ -218,7 +218,9 @@ __device__ __forceinline__ void als_finish_row(const AlsIn& in, float* __restric
       ok = false;
       break;
     }
-    const float dj = __fsqrt_rn(piv);
+    // the correctly rounded square root: sqrtf is (v_sqrt_f32 and a correction); __fsqrt_rn is the bare 1-ulp v_sqrt_f32
+    // here, which test_gpu_als_exact.py::test_exact_rows_bit_for_bit tells apart
+    const float dj = sqrtf(piv);
     if (lane == j) A[j * S + j] = dj;
     else if (live && lane > j) A[lane * S + j] = __fdiv_rn(s, dj);
     als_wave_sync();

@@ -5,7 +5,9 @@ Two row solvers.  ``solve_row64`` is the reference: ``numpy.linalg.solve`` on th
 ``solve_row32`` restates the kernel's arithmetic in float32 -- chunked k-ordered accumulation, Cholesky, two triangular
 solves, in the kernel's stated order -- to measure what float32 itself costs on a given row.  A float32 fma is emulated as
 ``float32(float64(a) * float64(b) + float64(c))``: the product is exact in a double, the sum rounds twice (to 53, then to 24
-bits), which differs from a true fma in rare last-bit cases only.
+bits), which differs from a true fma in rare last-bit cases only.  That is the default (``fma32``), and what the bound tests
+measure with.  ``fma32_exact`` is the correctly rounded float32 fma; every float32 function here takes it as ``fma=`` and
+the bit-for-bit tests (test_gpu_als_exact.py) run on it.
 
 lam: the C ABI takes ``reg`` as a float, so both solvers use ``float64(float32(reg))``; the float32 one multiplies by the
 row's count in float32 as the kernel does."""
@@ -16,6 +18,22 @@ F32, F64 = np.float32, np.float64
 
 def fma32(a, b, c):
     return (np.asarray(a, F64) * np.asarray(b, F64) + np.asarray(c, F64)).astype(F32)
+
+
+def fma32_exact(a, b, c):
+    """The correctly rounded float32 fma, vectorised.  The product of two float32 is exact in fp64; TwoSum of it and c gives
+    the fp64 sum s and its exact error e; s is rounded to odd (where e != 0 and the last bit of s is even, one fp64 ulp
+    toward e's sign), and a sum rounded to odd at 53 >= 24 + 2 bits rounds to float32 as the exact sum does."""
+    p = np.asarray(a, F32).astype(F64) * np.asarray(b, F32).astype(F64)
+    c = np.asarray(c, F32).astype(F64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = p + c
+        v = s - p
+        e = (p - (s - v)) + (c - v)
+        even = (np.ascontiguousarray(s).view(np.uint64) & np.uint64(1)) == 0
+        step = np.isfinite(s) & np.isfinite(e) & (e != 0) & even
+        s = np.where(step, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+        return s.astype(F32)
 
 
 def lam_of(reg, n, weighted):
@@ -32,7 +50,7 @@ def solve_row64(Y, cols, d, reg, weighted):
     return np.linalg.solve(A, y.T @ np.asarray(d, F64))
 
 
-def gram_rhs32(Y, cols, d, chunk):
+def gram_rhs32(Y, cols, d, chunk, fma=fma32):
     """(G float32[rank, rank], b float32[rank]) in the kernel's order: per chunk of `chunk` consecutive ratings the Gram
     entries are a k-ordered fma chain from 0 and the right-hand side is the chain over the chunk's even ratings plus the
     chain over its odd ones; chunk partials are added in ascending chunk order."""
@@ -43,23 +61,23 @@ def gram_rhs32(Y, cols, d, chunk):
         r = [np.zeros(rank, F32), np.zeros(rank, F32)]
         for k in range(c0, min(c0 + chunk, len(cols))):
             y = Y[cols[k]]
-            g = fma32(y[:, None], y[None, :], g)
-            r[(k - c0) & 1] = fma32(F32(d[k]), y, r[(k - c0) & 1])
+            g = fma(y[:, None], y[None, :], g)
+            r[(k - c0) & 1] = fma(F32(d[k]), y, r[(k - c0) & 1])
         p = (r[0] + r[1]).astype(F32)
         G, b = (g, p) if G is None else ((G + g).astype(F32), (b + p).astype(F32))
     return G, b
 
 
-def cholesky_solve32(G, b, lam):
+def cholesky_solve32(G, b, lam, fma=fma32):
     """x float32 of (G + lam I) x = b: left-looking float32 Cholesky and two column-oriented solves; None where a pivot is
-    not finite and positive."""
+    not finite and positive.  Only the lower triangle of G is read."""
     n = G.shape[0]
     L = G.astype(F32).copy()
     L[np.arange(n), np.arange(n)] = (np.diag(L) + F32(lam)).astype(F32)
     for j in range(n):
         s = L[j:, j].copy()
         for k in range(j):
-            s = fma32(-L[j:, k], L[j, k], s)
+            s = fma(-L[j:, k], L[j, k], s)
         if not (s[0] > 0 and np.isfinite(s[0])):
             return None
         dj = np.sqrt(s[0], dtype=F32)
@@ -68,10 +86,10 @@ def cholesky_solve32(G, b, lam):
     x = np.asarray(b, F32).copy()
     for j in range(n):
         x[j] = F32(x[j] / L[j, j])
-        x[j + 1:] = fma32(-L[j + 1:, j], x[j], x[j + 1:])
+        x[j + 1:] = fma(-L[j + 1:, j], x[j], x[j + 1:])
     for j in range(n - 1, -1, -1):
         x[j] = F32(x[j] / L[j, j])
-        x[:j] = fma32(-L[j, :j], x[j], x[:j])
+        x[:j] = fma(-L[j, :j], x[j], x[:j])
     return x
 
 
@@ -79,12 +97,12 @@ def lam32(reg, n, weighted):
     return F32(F32(reg) * F32(n)) if weighted else F32(reg)
 
 
-def solve_row32(Y, cols, d, reg, weighted, chunk, gram=None):
+def solve_row32(Y, cols, d, reg, weighted, chunk, gram=None, fma=fma32):
     """The float32 restatement of one row (``gram``: a cached gram_rhs32 of the same row)."""
     if len(cols) == 0:
         return np.zeros(Y.shape[1], F32)
-    G, b = gram_rhs32(Y, cols, d, chunk) if gram is None else gram
-    return cholesky_solve32(G, b, lam32(reg, len(cols), weighted))
+    G, b = gram_rhs32(Y, cols, d, chunk, fma) if gram is None else gram
+    return cholesky_solve32(G, b, lam32(reg, len(cols), weighted), fma)
 
 
 def half_sweep(Y, offsets, cols, d, reg, weighted, chunk=None):

@@ -14,6 +14,8 @@ Arithmetic order of the float32 restatement, as esr_als.hip states it:
                triangle i >= j is read afterwards); (3) the right-hand side is fma32(c_k, y_k[d], acc), c_k = fl32(1 + w_k),
                over the chunk's even entries plus the same chain over its odd ones; (4) chunk partials are added in ascending
                order in float32; (5) then G[i][j] is added; (6) then lam on the diagonal; (7) then _als_ref.cholesky_solve32.
+fma32 is _als_ref's double-rounded emulation, the default; ``fma=_als_ref.fma32_exact`` runs the same steps on the correctly
+rounded float32 fma (the bit-for-bit tests do).
 """
 import numpy as np
 
@@ -26,14 +28,14 @@ def gram64(Y):
     return y.T @ y
 
 
-def gram32(Y, segment):
+def gram32(Y, segment, fma=fma32):
     Y = np.asarray(Y, F32)
     rank = Y.shape[1]
     total = np.zeros((rank, rank), F64)
     for s0 in range(0, len(Y), segment):
         g = np.zeros((rank, rank), F32)
         for k in range(s0, min(s0 + segment, len(Y))):
-            g = fma32(Y[k][:, None], Y[k][None, :], g)
+            g = fma(Y[k][:, None], Y[k][None, :], g)
         total = total + g.astype(F64)
     return total.astype(F32)
 
@@ -50,7 +52,7 @@ def solve_row64(Y, cols, w, G64, reg, weighted):
     return np.linalg.solve(A, y.T @ (1.0 + w))
 
 
-def gram_rhs32(Y, cols, w, chunk):
+def gram_rhs32(Y, cols, w, chunk, fma=fma32):
     """(sum_k w_k y_k y_k^T float32[rank, rank], sum_k c_k y_k float32[rank]): steps (1) to (4) of the module text."""
     rank = Y.shape[1]
     A = b = None
@@ -60,20 +62,20 @@ def gram_rhs32(Y, cols, w, chunk):
         for k in range(c0, min(c0 + chunk, len(cols))):
             y = Y[cols[k]]
             wk = F32(w[k])
-            g = fma32((wk * y).astype(F32)[:, None], y[None, :], g)
-            r[(k - c0) & 1] = fma32(F32(F32(1.0) + wk), y, r[(k - c0) & 1])
+            g = fma((wk * y).astype(F32)[:, None], y[None, :], g)
+            r[(k - c0) & 1] = fma(F32(F32(1.0) + wk), y, r[(k - c0) & 1])
         p = (r[0] + r[1]).astype(F32)
         A, b = (g, p) if A is None else ((A + g).astype(F32), (b + p).astype(F32))
     return A, b
 
 
-def solve_row32(Y, cols, w, G32, reg, weighted, chunk, partial=None):
+def solve_row32(Y, cols, w, G32, reg, weighted, chunk, partial=None, fma=fma32):
     """The float32 restatement of one row (``partial``: a cached gram_rhs32 of the same row); None where a pivot fails."""
     if len(cols) == 0:
         return np.zeros(Y.shape[1], F32)
-    A, b = gram_rhs32(Y, cols, w, chunk) if partial is None else partial
+    A, b = gram_rhs32(Y, cols, w, chunk, fma) if partial is None else partial
     A = (A + np.asarray(G32, F32)).astype(F32)
-    return ref.cholesky_solve32(A, b, ref.lam32(reg, len(cols), weighted))
+    return ref.cholesky_solve32(A, b, ref.lam32(reg, len(cols), weighted), fma)
 
 
 def half_sweep(Y, offsets, cols, w, reg, weighted, chunk=None, segment=None):

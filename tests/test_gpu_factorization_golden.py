@@ -2,7 +2,10 @@
 base class.  tests/golden/make_factorization_golden.py trains small models (every rank layout, row-length class, optimiser
 and launch slicing) and digests every table, loss list and a few outputs with SHA-256; tests/golden/factorization_parent.json
 holds those digests as written at the parent commit (stable between two runs there).  The models are functions of their
-inputs and the seed, so equality is the assertion: a reordered generator draw or ops call shows as a different table."""
+inputs and the seed, so equality is the assertion: a reordered generator draw or ops call shows as a different table.
+(The digests of the two ALS models were written again when the pivot's square root in esr_als.hip became the correctly
+rounded one, which tests/test_gpu_als_exact.py demands: last bits of every solved row moved; the other twelve models kept
+theirs.)"""
 import importlib.util
 import json
 import os

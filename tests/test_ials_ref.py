@@ -66,6 +66,35 @@ def test_gram32_is_close_to_gram64_and_ignores_trailing_zero_rows():
     assert not iref.gram32(np.zeros((0, 4), np.float32), 8).any()
 
 
+def test_the_fma_argument_reaches_every_chain():
+    # _als_ref's witness: fma(x, x, 2^-60), x = 1 + 2^-12, is 0x3F801001 correctly rounded and 0x3F801000 rounded twice.
+    # As a chain: the row y_0 = 2^-30 leaves 2^-60, the row y_1 = x lands on the tie.
+    def bits(a):
+        return np.asarray(a, np.float32).view(np.uint32)
+    x = np.float32(1 + 2.0 ** -12)
+    Y = np.array([[2.0 ** -30], [x]], np.float32)
+    one = np.ones(3, np.float32)
+    for fma, want in ((ref.fma32_exact, 0x3F801001), (ref.fma32, 0x3F801000), (None, 0x3F801000)):
+        kw = {} if fma is None else {"fma": fma}                               # the default is the double-rounded one
+        assert bits(iref.gram32(Y, 2, **kw))[0, 0] == want
+        assert bits(iref.gram32(Y, 1, **kw))[0, 0] == 0x3F801000               # two segments: the fp64 sum, rounded once
+        A, b = iref.gram_rhs32(Y, [0, 1], one, 2, **kw)                        # w = 1: fl32(w y) = y
+        assert bits(A)[0, 0] == want
+        # right-hand side, c = 1 + w: the even chain is 1 * 2^-60, then (after an odd entry on a zero row) x * x, w = x - 1
+        w = np.float32([0.0, 0.0, x - 1])
+        assert np.float32(1) + w[2] == x
+        A, b = iref.gram_rhs32(np.array([[2.0 ** -60], [x], [0.0]], np.float32), [0, 2, 1], w, 4, **kw)
+        assert bits(b)[0] == want
+    # solve_row32 hands the argument on to both halves: the explicit witness matrix of test_als_ref through G32
+    G = np.array([[1.0, 0.0], [-x, 4.0]], np.float32)
+    Yz = np.zeros((1, 2), np.float32)                                          # a zero factor row: A = 0, b = 0
+    part = (np.zeros((2, 2), np.float32), np.float32([x, 2.0 ** -60]))
+    xe = iref.solve_row32(Yz, [0], one[:1], G, 1e-30, False, 4, partial=part, fma=ref.fma32_exact)
+    xd = iref.solve_row32(Yz, [0], one[:1], G, 1e-30, False, 4, partial=part)
+    assert np.array_equal(bits(xe), bits(ref.cholesky_solve32(G, part[1], np.float32(1e-30), ref.fma32_exact)))
+    assert bits(xe)[1] != bits(xd)[1]
+
+
 def test_float32_row_solve_is_close_to_fp64():
     rng = np.random.default_rng(3)
     for rank, n_other, n in ((3, 9, 4), (8, 60, 37), (33, 97, 300)):
