@@ -276,6 +276,11 @@ SIGNATURES = {
     "esr_bag_sum": (c_int, [c_f32p, c_i64, c_int, c_vp, c_i32p, c_f32p, c_i64, c_i64, c_i32p, c_i64, c_f32p, c_i32p, c_vp]),
     "esr_bag_expand": (c_int, [c_f32p, c_i64, c_int, c_vp, c_i32p, c_f32p, c_i64, c_i64, c_i32p, c_f32p, c_i32p, c_vp, c_i64,
                                c_i64, c_f32, c_i32p, c_f32p, c_i32p, c_vp]),
+    "esr_rerank_geometry": (c_int, [c_int, c_int] + [ctypes.POINTER(c_int)] * 8),
+    "esr_rerank_mmr": (c_int, [c_f32p, c_i64, c_int, c_i32p, c_f32p, c_i32p, c_i64, c_int, c_int, c_f32, c_i32p, c_i32p, c_f32p,
+                               c_f32p, c_i32p, c_i32p, c_vp]),
+    "esr_rerank_ils": (c_int, [c_f32p, c_i64, c_int, c_i32p, c_i32p, c_i64, c_int, ctypes.POINTER(c_int32), c_int, c_f32p,
+                               c_i32p, c_i32p, c_vp]),
 }
 
 

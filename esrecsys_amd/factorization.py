@@ -33,7 +33,8 @@ by the row-sparse engine; ``WARP`` (last) is BPR's model trained with the rank-w
 for on the device by one fused call (esr_warp.hip).  ``HybridBPR`` is BPR over users and items that are weighted sums of
 feature embeddings (esr_bag.hip): side information and cold start.
 
-All five derive from ``_Factorization`` (device, indexed pairs, ``score`` / ``recommend`` / ``from_documents``); ``_ALS`` holds
+All five derive from ``_Factorization`` (device, indexed pairs, ``score`` / ``recommend`` / ``from_documents`` and
+``diversify``, the MMR re-ranking of ``rerank.py`` applied to ``recommend``'s lists); ``_ALS`` holds
 what the two alternating models share, ``BPR`` the step tail and the update of the three triple models.
 """
 import math
@@ -182,6 +183,33 @@ class _Factorization:
         int32[nq]) as ``RatingsALS.recommend``, by the same candidate scheme; a score equals ``score`` of the pair bit for
         bit, an unknown user gets an empty list."""
         return self._recommend(users, k, slack, exclude_seen)
+
+    def diversify(self, rec_ids, rec_scores, rec_lengths, lam=0.7, n=None, normalize=True):
+        """The lists of ``recommend`` (device tensors) re-ranked by Maximal Marginal Relevance (``rerank.mmr``): per query
+        the n (default: the lists' width) picks that trade a candidate's score (weight lam) against its greatest similarity
+        to the items picked before it (weight 1 - lam).  The similarity is the dot product of the items' factor rows
+        (``item_rows()`` for ``HybridBPR``), of unit length when `normalize`: the cosine.  Returns (rec_ids, rec_scores,
+        rec_lengths) in ``recommend``'s shape and padding, in pick order; ``lam = 1`` keeps ``recommend``'s order.  An id
+        inside a list's length that is no item of the model raises ``ValueError``."""
+        from . import rerank
+        ops._req(rec_ids, torch.int32, "rec_ids"), ops._req(rec_scores, torch.float32, "rec_scores")
+        if rec_ids.dim() != 2 or rec_scores.shape != rec_ids.shape:
+            raise ValueError("rec_ids and rec_scores must be [nq, width] alike")
+        nq, width = rec_ids.shape
+        with torch.cuda.device(self.device):
+            pos = self._positions(rec_ids.reshape(-1), self.items).reshape(nq, width)
+            inside = torch.arange(width, device=self.device)[None, :] < \
+                (rec_lengths.to(torch.int64)[:, None] if rec_lengths is not None else width)
+            unknown = inside & (pos < 0)
+            if bool(unknown.any()):
+                q, c = (int(v) for v in unknown.nonzero()[0])
+                raise ValueError("query %d: id %d at place %d of its list is not an item of the model"
+                                 % (q, int(rec_ids[q, c]), c))
+            rows = self.item_factors
+            rows = rerank.unit_rows(rows) if normalize else rows.contiguous()
+            items, rel, lengths, _, _ = rerank.mmr(pos, rec_scores, rec_lengths, rows, lam, n)
+            ids = torch.where(items >= 0, self.items[items.clamp(min=0).to(torch.int64)], torch.full_like(items, -1))
+        return ids, rel, lengths
 
 
 def _recommend_rows(factors, offset, upos, item_factors, items, k, slack, seen_offsets, seen_key, name, verb, flag):

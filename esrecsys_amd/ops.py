@@ -2229,3 +2229,88 @@ def bag_expand(table, offsets, feat, weight, rows, grad_rows, valid, out_offsets
                                  _p(valid), _p(out_offsets), n, M, float(reg), _p(out_feat), _p(out_grads), _p(failed),
                                  _stream()), "esr_bag_expand")
     return out_feat, out_grads
+
+
+# ---------------------------------------------------------------------------------------------
+# Diversity re-ranking (esr_rerank.hip): MMR over candidate lists, intra-list similarity
+def rerank_geometry(D, width):
+    """A dict for lists of `width` candidates over rows of rank `D`: the limits (max_rank, rank_multiple, max_width,
+    max_cutoffs), the staging budget stage_bytes, the grid_cap, whether this shape stages a query's rows in LDS (staged)
+    and the dynamic LDS of its launch (lds_bytes)."""
+    names = ("max_rank", "rank_multiple", "max_width", "max_cutoffs", "stage_bytes", "grid_cap", "staged", "lds_bytes")
+    vals = [ctypes.c_int(0) for _ in names]
+    check(_lib.load().esr_rerank_geometry(int(D), int(width), *[ctypes.byref(v) for v in vals]), "esr_rerank_geometry")
+    return {n: int(v.value) for n, v in zip(names, vals)}
+
+
+def _rerank_args(who, rows, cand, lengths):
+    """The checks rerank_mmr and rerank_ils share.  Returns (ni, D, nq, width)."""
+    _req(rows, torch.float32, "rows"), _req(cand, torch.int32, "cand")
+    if rows.dim() != 2 or cand.dim() != 2:
+        raise ValueError("%s: rows must be [ni, rank] and cand [nq, width]" % who)
+    ni, D, nq, width = int(rows.shape[0]), int(rows.shape[1]), int(cand.shape[0]), int(cand.shape[1])
+    _check_rank4(D, 128, 4)
+    if not 1 <= width <= 1024:
+        raise ValueError("%s: list width = %d outside [1, 1024]" % (who, width))
+    if not (1 <= ni <= 2 ** 31 - 1 and nq <= 2 ** 31 - 1):
+        raise ValueError("%s: ni=%d nq=%d (ni in [1, 2^31 - 1], nq at most 2^31 - 1)" % (who, ni, nq))
+    if lengths is not None:
+        _req(lengths, torch.int32, "lengths")
+        if lengths.numel() != nq:
+            raise ValueError("%s: lengths must hold one entry per query" % who)
+    return ni, D, nq, width
+
+
+def rerank_mmr(rows, cand, rel, lengths, lam, n_out, failed=None):
+    """(out_pos int32, out_item int32, out_rel float32, out_value float32 [nq, n_out], out_length int32[nq]): n_out greedy
+    rounds of Maximal Marginal Relevance per query by the rule of esr_rerank_rule.h over cand int32[nq, width] (item
+    positions into rows float32[ni, D]), rel float32[nq, width] and lengths int32[nq] or None (full rows): round t picks
+    the candidate with the greatest fmaf(lam, rel, -((1 - lam) * m)), m its greatest dot product with a row picked before,
+    ties to the smallest list position.  `failed` (int32[1], device; a scratch word when None) gets bit 30 for a position
+    outside rows and bit 29 for a rel that is not finite -- such a candidate is never picked; the caller zeroes and reads
+    it."""
+    lib = _lib.load()
+    ni, D, nq, width = _rerank_args("rerank_mmr", rows, cand, lengths)
+    _req(rel, torch.float32, "rel")
+    if rel.shape != cand.shape:
+        raise ValueError("rerank_mmr: rel must have cand's shape")
+    n_out, lam = int(n_out), float(lam)
+    if not 1 <= n_out <= width:
+        raise ValueError("rerank_mmr: n_out = %d outside [1, width = %d]" % (n_out, width))
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("rerank_mmr: lam = %r outside [0, 1]" % lam)
+    dev = rows.device
+    out_pos = torch.empty((nq, n_out), dtype=torch.int32, device=dev)
+    out_item, out_rel = torch.empty_like(out_pos), torch.empty((nq, n_out), dtype=torch.float32, device=dev)
+    out_value, out_length = torch.empty_like(out_rel), torch.empty(nq, dtype=torch.int32, device=dev)
+    failed = _failed_word(failed, dev)
+    if nq:
+        check(lib.esr_rerank_mmr(_p(rows), ni, D, _p(cand), _p(rel), _p(lengths), nq, width, n_out, lam, _p(out_pos),
+                                 _p(out_item), _p(out_rel), _p(out_value), _p(out_length), _p(failed), _stream()),
+              "esr_rerank_mmr")
+    return out_pos, out_item, out_rel, out_value, out_length
+
+
+def rerank_ils(rows, cand, lengths, ks, failed=None):
+    """(ils float32[nq, nk], valid int32[nq, nk]): the intra-list similarity of the lists cand int32[nq, width] (item
+    positions into rows float32[ni, D]; lengths int32[nq] or None) at the strictly ascending cutoffs `ks` (1 to 8 ints):
+    the mean dot product over the pairs among a list's first min(k, length) candidates, summed in fp64 in a fixed order;
+    0 with valid = 0 for fewer than two candidates.  `failed` as rerank_mmr's (bit 30 only)."""
+    lib = _lib.load()
+    ni, D, nq, width = _rerank_args("rerank_ils", rows, cand, lengths)
+    try:
+        ks = tuple(int(k) for k in ks)
+    except TypeError:
+        raise TypeError("ks must be a sequence of ints, got %r" % (ks,))
+    if not 1 <= len(ks) <= 8:
+        raise ValueError("ks holds %d cutoffs, outside [1, 8]" % len(ks))
+    if any(k < 1 or k > 2 ** 31 - 1 or (j and k <= ks[j - 1]) for j, k in enumerate(ks)):
+        raise ValueError("ks must be strictly ascending cutoffs >= 1, got %r" % (ks,))
+    dev = rows.device
+    ils = torch.empty((nq, len(ks)), dtype=torch.float32, device=dev)
+    valid = torch.empty((nq, len(ks)), dtype=torch.int32, device=dev)
+    failed = _failed_word(failed, dev)
+    if nq:
+        check(lib.esr_rerank_ils(_p(rows), ni, D, _p(cand), _p(lengths), nq, width, (ctypes.c_int32 * len(ks))(*ks), len(ks),
+                                 _p(ils), _p(valid), _p(failed), _stream()), "esr_rerank_ils")
+    return ils, valid

@@ -1246,6 +1246,33 @@ int esr_bag_expand(const float* table, int64_t nf, int D, const int64_t* bag_off
                    const int32_t* valid, const int64_t* out_offsets, int64_t n, int64_t M, float reg, int32_t* out_feat,
                    float* out_grads, int32_t* failed, esr_stream_t stream);
 
+/* ---- Diversity re-ranking (MMR, Carbonell and Goldstein 1998; intra-list similarity, Ziegler et al. 2005; esr_rerank.hip) ----
+ * rows float[ni, D] are the items' rows (D a multiple of 4 in [4, 128]), cand int32[nq, width] item POSITIONS into rows,
+ * rel float[nq, width], lengths int32[nq] or null (full rows), 1 <= width <= 1024.  The rule of both calls is stated in
+ * esrecsys_amd/csrc/esr_rerank_rule.h, the text the kernels and a stand-alone host program compile.  sim(a, b) is the dot
+ * product of two rows in the summation order of esr_bpr_fwd_bwd.  No workspace; the calls never synchronise.
+ *   geometry    for (D, width): the limits (max_rank 128, rank_multiple 4, max_width 1024, max_cutoffs 8), the staging budget
+ *               stage_bytes, the grid cap, whether this shape stages the query's rows in LDS (width * D * 4 <= stage_bytes)
+ *               and the dynamic LDS of its launch.  Both forms give the same bits.
+ *   mmr         per query n_out (1 .. width) greedy rounds over the candidates c < L = clamp(lengths[q], 0, width): the pick of
+ *               round t maximises v[c] = fmaf(lam, rel[c], -((1.0f - lam) * m[c])), m[c] = the greatest sim of c to a row
+ *               picked before (0.0f in round 0), ties to the smallest c; out_pos / out_item / out_rel / out_value [nq, n_out]
+ *               receive c, cand[c], rel[c] and v[c], out_length[q] the picks, and the slots behind -1 / -1 / 0 / 0.  lam in
+ *               [0, 1]; lam = 1 is the stable sort by rel descending.
+ *   ils         at nk (1 .. 8) strictly ascending cutoffs ks (HOST array): ils float[nq, nk] = the mean sim over the pairs of
+ *               present candidates among the first min(k, L), summed in fp64 in ascending (i, j < i) order and rounded once;
+ *               valid int32[nq, nk] = 0 (and ils = 0) with fewer than two present candidates.
+ * Refusals on the device: a position outside [0, ni) sets bit 30 of *failed, a rel that is not finite bit 29 (the caller zeroes
+ * and reads the word); such a candidate is absent: never picked, never counted, its row never read.
+ * 1 <= ni <= 2^31 - 1; 0 <= nq <= 2^31 - 1 (nq = 0: nothing is launched).  rows 16-byte aligned. */
+int esr_rerank_geometry(int D, int width, int* max_rank, int* rank_multiple, int* max_width, int* max_cutoffs,
+                        int* stage_bytes, int* grid_cap, int* staged, int* lds_bytes);
+int esr_rerank_mmr(const float* rows, int64_t ni, int D, const int32_t* cand, const float* rel, const int32_t* lengths,
+                   int64_t nq, int width, int n_out, float lam, int32_t* out_pos, int32_t* out_item, float* out_rel,
+                   float* out_value, int32_t* out_length, int32_t* failed, esr_stream_t stream);
+int esr_rerank_ils(const float* rows, int64_t ni, int D, const int32_t* cand, const int32_t* lengths, int64_t nq, int width,
+                   const int32_t* ks, int nk, float* ils, int32_t* valid, int32_t* failed, esr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
