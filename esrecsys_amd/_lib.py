@@ -276,6 +276,12 @@ SIGNATURES = {
     "esr_bag_sum": (c_int, [c_f32p, c_i64, c_int, c_vp, c_i32p, c_f32p, c_i64, c_i64, c_i32p, c_i64, c_f32p, c_i32p, c_vp]),
     "esr_bag_expand": (c_int, [c_f32p, c_i64, c_int, c_vp, c_i32p, c_f32p, c_i64, c_i64, c_i32p, c_f32p, c_i32p, c_vp, c_i64,
                                c_i64, c_f32, c_i32p, c_f32p, c_i32p, c_vp]),
+    "esr_fpmc_geometry": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "esr_fpmc_sample": (c_int, [c_vp, c_i32p, c_i32p, c_i64, c_vp, c_i32p, c_i64, c_i64, c_i64, c_int, c_uint64, c_uint32,
+                                c_i64, c_i64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_vp]),
+    "esr_fpmc_fwd_bwd": (c_int, [c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_i32p, c_i64, c_i32p, c_i32p, c_i32p,
+                                 c_i32p, c_i32p, c_i32p, c_i64, c_vp, c_i64, c_f32, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p,
+                                 c_vp]),
     "esr_rerank_geometry": (c_int, [c_int, c_int] + [ctypes.POINTER(c_int)] * 8),
     "esr_rerank_mmr": (c_int, [c_f32p, c_i64, c_int, c_i32p, c_f32p, c_i32p, c_i64, c_int, c_int, c_f32, c_i32p, c_i32p, c_f32p,
                                c_f32p, c_i32p, c_i32p, c_vp]),

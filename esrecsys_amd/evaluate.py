@@ -201,3 +201,14 @@ def split_holdout(indices, doc_offsets, context=5, min_length=10, mode="first"):
         at = torch.repeat_interleave(begin - o[:-1], n) + torch.arange(total, dtype=torch.int64, device=dev)
         out += [ids[at], o]
     return out[0], out[1], out[2], out[3], kept
+
+
+def split_last(indices, doc_offsets, n_last=1, min_length=3):
+    """The leave-last-out protocol of next-item evaluation: of every document of at least `min_length` ids the last `n_last`
+    are the truth and everything before them, in order, the training sequence (``factorization.FPMC.from_documents`` takes
+    it as it is).  Returns what ``split_holdout`` returns -- ``(context, context_offsets, truth, truth_offsets, kept)`` --
+    so the truth goes straight into ``ranking_metrics``; `min_length` must exceed `n_last`."""
+    n_last, min_length = int(n_last), int(min_length)
+    if n_last < 1 or min_length <= n_last:
+        raise ValueError("need 1 <= n_last < min_length, got n_last=%d min_length=%d" % (n_last, min_length))
+    return split_holdout(indices, doc_offsets, context=n_last, min_length=min_length, mode="last")

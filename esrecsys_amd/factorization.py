@@ -31,9 +31,11 @@ folded in by the same call (``fold_in``, ``recommend_documents``).  ``BPR`` (fur
 that is trained on the ranking itself: Bayesian Personalised Ranking over triples sampled on the device (esr_bpr.hip), updated
 by the row-sparse engine; ``WARP`` (last) is BPR's model trained with the rank-weighted margin loss, its negatives searched
 for on the device by one fused call (esr_warp.hip).  ``HybridBPR`` is BPR over users and items that are weighted sums of
-feature embeddings (esr_bag.hip): side information and cold start.
+feature embeddings (esr_bag.hip): side information and cold start.  ``FPMC`` (at the end) is the sequential member: BPR's
+user-item term plus a factorised transition term from the items just consumed (esr_fpmc.hip), which also serves sessions of
+users the model never saw.
 
-All five derive from ``_Factorization`` (device, indexed pairs, ``score`` / ``recommend`` / ``from_documents`` and
+All six derive from ``_Factorization`` (device, indexed pairs, ``score`` / ``recommend`` / ``from_documents`` and
 ``diversify``, the MMR re-ranking of ``rerank.py`` applied to ``recommend``'s lists); ``_ALS`` holds
 what the two alternating models share, ``BPR`` the step tail and the update of the three triple models.
 """
@@ -103,7 +105,7 @@ def _ids_and_offsets(indices, doc_offsets, dev):
 
 
 class _Factorization:
-    """What the five models share (the module text).  A subclass provides ``user_factors`` / ``item_factors``."""
+    """What the six models share (the module text).  A subclass provides ``user_factors`` / ``item_factors``."""
 
     def _set_device(self, user, item, device):
         """The last two refusals of every constructor that need no device work: integer ids, a CUDA device."""
@@ -140,7 +142,7 @@ class _Factorization:
     def from_documents(cls, indices, doc_offsets, **kw):
         """The model of id documents ``indices[doc_offsets[d]:doc_offsets[d + 1]]``: the user is the document number.  An id
         repeated within d is a repeated event: ``ImplicitALS`` adds the strengths (without `strength`: the id's occurrence
-        count in d), ``BPR`` and its subclasses keep one seen pair."""
+        count in d), ``BPR`` and its subclasses keep one seen pair; ``FPMC`` also keeps d's ids as a sequence in order."""
         ids, off = _ids_and_offsets(indices, doc_offsets, torch.device("cpu"))
         docs = torch.from_numpy(np.repeat(np.arange(off.size - 1, dtype=np.int64), np.diff(off)))
         return cls(docs, ids, **kw)
@@ -158,12 +160,18 @@ class _Factorization:
         pos = torch.searchsorted(t, ids).clamp(max=t.numel() - 1)
         return torch.where(t[pos] == ids, pos, torch.full_like(pos, -1)).to(torch.int32).contiguous()
 
+    def _rows(self):
+        """(query table [nu, width], item table [ni, width]): the rows whose dot product is the model's score -- what
+        ``score``, ``recommend`` and ``diversify`` read."""
+        return self.user_factors, self.item_factors
+
     def _score(self, users, items, offset=None):
         users, items = _tensor(users, "users"), _tensor(items, "items")
         _same_length("users and items", users, items)
         with torch.cuda.device(self.device):
-            return ops.als_predict(self.user_factors, self.item_factors, self._positions(users, self.users),
-                                   self._positions(items, self.items), offset=offset)
+            queries, rows = self._rows()
+            return ops.als_predict(queries, rows, self._positions(users, self.users), self._positions(items, self.items),
+                                   offset=offset)
 
     def score(self, users, items):
         """float32[nq]: ``float32(x_u . y_i)`` (fp64 sum in ascending dimension); NaN where the user or the item is
@@ -173,7 +181,8 @@ class _Factorization:
     def _recommend(self, users, k, slack, exclude, verb="has seen", flag="exclude_seen", offset=None):
         with torch.cuda.device(self.device):
             upos = self._positions(users, self.users).to(torch.int64)
-            return _recommend_rows(self.user_factors, offset, upos, self.item_factors, self.items, k, slack,
+            queries, rows = self._rows()
+            return _recommend_rows(queries, offset, upos, rows, self.items, k, slack,
                                    self._user_offsets if exclude else None, self._key,
                                    lambda q: "user %d" % int(_tensor(users, "users")[q]), verb, flag)
 
@@ -205,7 +214,7 @@ class _Factorization:
                 q, c = (int(v) for v in unknown.nonzero()[0])
                 raise ValueError("query %d: id %d at place %d of its list is not an item of the model"
                                  % (q, int(rec_ids[q, c]), c))
-            rows = self.item_factors
+            rows = self._rows()[1]
             rows = rerank.unit_rows(rows) if normalize else rows.contiguous()
             items, rel, lengths, _, _ = rerank.mmr(pos, rec_scores, rec_lengths, rows, lam, n)
             ids = torch.where(items >= 0, self.items[items.clamp(min=0).to(torch.int64)], torch.full_like(items, -1))
@@ -663,21 +672,23 @@ class BPR(_Factorization):
     def _index_seen(self, user, item):
         """users / items, the CSR of the seen pairs on the host and on the device; returns (nu, ni)."""
         _, upos, ipos = self._index_pairs(user, item)
+        return self._set_seen(upos, ipos)
+
+    def _set_seen(self, upos, ipos):
+        """The CSR of the seen pairs of the events (upos, ipos) on the host and on the device; returns (nu, ni)."""
         nu = int(self.users.numel())
         key = torch.unique((upos << 32) | ipos)                     # repeated events collapse to one seen pair
         self._set_pairs(key, _host_offsets(torch.bincount(key >> 32, minlength=nu)))
         self._offsets_dev = torch.from_numpy(self._user_offsets).to(self.device)    # the sampler reads the CSR on the device
         return nu, int(self.items.numel())
 
-    def _new_tables(self, nu, ni):
-        """(user table [nu, rank], item table [ni, rank], their Adagrad accumulators): ``randn * init_scale`` from the seeded
-        CPU generator, users first."""
+    def _new_tables(self, *rows):
+        """(a table [n, rank] per entry of `rows`, then their Adagrad accumulators): ``randn * init_scale`` from the seeded
+        CPU generator in the order given (users first)."""
         dev, rank = self.device, self.rank
         gen = torch.Generator(device="cpu").manual_seed(self.seed)
-        user = (torch.randn(nu, rank, generator=gen) * self.init_scale).to(dev).contiguous()
-        item = (torch.randn(ni, rank, generator=gen) * self.init_scale).to(dev).contiguous()
-        return (user, item, torch.full((nu, rank), ADAGRAD_INIT, dtype=torch.float32, device=dev),
-                torch.full((ni, rank), ADAGRAD_INIT, dtype=torch.float32, device=dev))
+        tables = [(torch.randn(n, rank, generator=gen) * self.init_scale).to(dev).contiguous() for n in rows]
+        return tuple(tables) + tuple(torch.full((n, rank), ADAGRAD_INIT, dtype=torch.float32, device=dev) for n in rows)
 
     def _init_tables(self, nu, ni):
         self.user_factors, self.item_factors, self.user_accum, self.item_accum = self._new_tables(nu, ni)
@@ -693,21 +704,26 @@ class BPR(_Factorization):
                                   self.seed if seed is None else int(seed), self.step if step0 is None else int(step0),
                                   int(K), self.batch)
 
-    def _apply(self, tables, accums, ids, bounds, grads):
-        """One update of the user and the item table (rows [bounds[n], bounds[n + 1]) of the stacked row space) through the
-        row-sparse engine: ``ids[0]`` index the first table, the other id tensors the second, `grads` holds one row per id
-        in that order.  Adagrad sorts and updates both at once, SGD one table after the other; no id, no launch."""
+    def _apply(self, tables, accums, ids, bounds, grads, table_of=None):
+        """One update of the tables (rows [bounds[n], bounds[n + 1]) of the stacked row space) through the row-sparse engine:
+        id tensor k indexes table ``table_of[k]`` (ascending; by default ``ids[0]`` the first table and the others the
+        second), `grads` holds one row per id in that order.  Adagrad sorts and updates all tables at once, SGD one table
+        after the other; no id, no launch."""
+        table_of = [0] + [1] * (len(ids) - 1) if table_of is None else table_of
         if self.optimizer == "adagrad":
             if grads.shape[0]:
-                sorted_ids, perm = ops.segment_sort_multi(ids, [0] + [bounds[1]] * (len(ids) - 1), bounds[2])
+                sorted_ids, perm = ops.segment_sort_multi(ids, [bounds[n] for n in table_of], bounds[-1])
                 ops.sparse_adagrad_multi(tables, accums, bounds, sorted_ids, perm, grads, self.lr)
             return
-        n0 = ids[0].numel()
-        for n, g in ((0, grads[:n0]), (1, grads[n0:])):
-            if g.shape[0]:
-                own = ids[n] if len(ids) == 2 or n == 0 else ops.concat_offset_ids(ids[1:], [0] * (len(ids) - 1))
+        at = 0
+        for n, table in enumerate(tables):
+            own = [t for t, owner in zip(ids, table_of) if owner == n]
+            count = sum(t.numel() for t in own)
+            if count:
+                own = own[0] if len(own) == 1 else ops.concat_offset_ids(own, [0] * len(own))
                 sorted_ids, perm = ops.segment_sort(own, bounds[n + 1] - bounds[n])
-                ops.sparse_sgd(tables[n], sorted_ids, perm, g, self.lr)
+                ops.sparse_sgd(table, sorted_ids, perm, grads[at:at + count], self.lr)
+            at += count
 
     def _update(self, u, i, j, grads):
         nu, ni = int(self.users.numel()), int(self.items.numel())
@@ -1142,3 +1158,212 @@ class HybridBPR(BPR):
             return _recommend_rows(self.user_factors, None, upos, rows, items, k, slack,
                                    self._user_offsets if exclude_seen else None, key,
                                    lambda q: "user %d" % int(_tensor(users, "users")[q]), "has seen", "exclude_seen")
+
+
+# ---- sequential recommendation: the factorised personalised Markov chain -------------------------------------------------
+def _tail_bags(ipos, offsets, window, dev):
+    """The bag table (``_Bags``) whose bag d is the last ``c = min(length, window)`` entries of row d of the CSR (ipos int64
+    on the device, host offsets), oldest first, every weight ``float32(1) / float32(c)``; None when no row has an entry."""
+    lens = np.diff(offsets)
+    c = np.minimum(lens, window)
+    bag_offsets = _host_offsets(c)
+    if int(bag_offsets[-1]) == 0:
+        return None
+    at = np.repeat(offsets[1:] - c - bag_offsets[:-1], c) + np.arange(int(bag_offsets[-1]), dtype=np.int64)
+    weight = np.repeat(np.float32(1.0) / np.maximum(c, 1).astype(np.float32), c)
+    feat = ipos[torch.from_numpy(at).to(dev)].to(torch.int32).cpu().numpy()
+    return _Bags(bag_offsets, feat, weight, dev)
+
+
+class FPMC(BPR):
+    """The Factorised Personalised Markov Chain (Rendle, Freudenthaler, Schmidt-Thieme, WWW 2010) trained with the BPR step:
+    BPR's user-item term plus a factorised transition term from the items just consumed -- "what comes next".
+
+        model = FPMC.from_documents(indices, doc_offsets, window=3, rank=32)      # a document is a sequence in order
+        losses = model.fit(steps=2000)
+        rec_ids, rec_scores, rec_lengths = model.recommend(users, k=10)           # after each user's training sequence
+        rec_ids, rec_scores, rec_lengths = model.recommend_sequences(ids, offsets, k=10)      # sessions of unseen users
+
+    Model.  Four tables of one rank: ``user_factors`` U [nu, rank], ``item_factors`` A [ni, rank] (the item as the user term
+    sees it), ``next_factors`` Bn [ni, rank] (the item as a successor) and ``prev_factors`` P [ni, rank] (the item as a
+    predecessor).  An event is place t of user u's sequence -- the events in the order given, or by a stable sort on
+    (user, time) with `time`; repeats are kept.  Its context is the ``c = min(t, window)`` items just before it and
+    ``m = sum_l P_l / c`` over them (``ops.bag_sum``'s chain, oldest first).  ``score(u, t, i) = U_u . A_i + m . Bn_i``.
+
+    Step.  ``batch`` slots (event, unseen item j) are drawn on the device (``ops.fpmc_sample``: BPR's Philox stream and
+    BPR's negatives against the user's seen set).  The objective of a step is the sum over its valid slots of
+    ``softplus(-d) + (reg / 2)(|U_u|^2 + |A_i|^2 + |A_j|^2 + |Bn_i|^2 + |Bn_j|^2 + sum_ctx |P_l|^2)``,
+    ``d = score(i) - score(j)``.  ``ops.fpmc_fwd_bwd`` writes one gradient row per occurrence and the row-sparse engine
+    updates the four tables: Adagrad in one sort and one launch, SGD table by table.  The fit is a function of the inputs
+    and the seed.
+
+    Serving.  A query is the row ``[U_u ; m]`` and an item the row ``[A_i ; Bn_i]``, both 2 rank wide, so ``score``,
+    ``recommend`` and ``diversify`` are the base class's on those rows (``query_rows`` / ``item_rows``): for a known user m
+    is built from the tail of the training sequence, the prediction of the NEXT event.  They re-score by the ALS predict
+    kernel, which takes rows of at most ``max_rank()``: serving needs ``2 rank <= max_rank()``.
+
+    The tables are ``randn * init_scale`` from the seeded CPU generator in the order U, A, Bn, P; the other constructor
+    arguments, ``users`` / ``items`` and ``step`` are ``BPR``'s."""
+
+    def __init__(self, user, item, time=None, window=1, rank=64, reg=0.01, lr=0.05, optimizer="adagrad", batch=65536, seed=0,
+                 init_scale=None, device=None):
+        top, _, _ = ops.fpmc_geometry()
+        window = int(window)
+        if not 1 <= window <= top:
+            raise ValueError("window = %d outside [1, %d]" % (window, top))
+        user, item = self._configure(user, item, rank, reg, lr, optimizer, batch, seed, init_scale, device)
+        if time is not None:
+            time = _tensor(time, "time")
+            _same_length("user, item and time", user, item, time)
+        self.window = window
+        dev = self.device
+        with torch.cuda.device(dev):
+            _, upos, ipos = self._index_pairs(user, item)
+            nu, ni = self._set_seen(upos, ipos)
+            if nu + 3 * ni > 2 ** 31 - 1:
+                raise ValueError("nu + 3 ni = %d rows exceed 2^31 - 1 (the row space of the update)" % (nu + 3 * ni))
+            if upos.numel() > 2 ** 31 - 1:
+                raise ValueError("%d events exceed 2^31 - 1" % upos.numel())
+            # the sequences: a CSR by user, the events of a user in the order given or by (time, order given)
+            order = torch.arange(upos.numel(), device=dev) if time is None else torch.sort(time.to(dev), stable=True).indices
+            order = order[torch.sort(upos[order], stable=True).indices]
+            self._seq_offsets = _host_offsets(torch.bincount(upos, minlength=nu))
+            self._seq_offsets_dev = torch.from_numpy(self._seq_offsets).to(dev)
+            self._seq_upos = upos[order].to(torch.int32).contiguous()
+            self._seq_ipos = ipos[order].to(torch.int32).contiguous()
+            self._tails = _tail_bags(ipos[order], self._seq_offsets, window, dev)
+            self._init_tables(nu, ni)
+
+    def _init_tables(self, nu, ni):
+        (self.user_factors, self.item_factors, self.next_factors, self.prev_factors, self.user_accum, self.item_accum,
+         self.next_accum, self.prev_accum) = self._new_tables(nu, ni, ni, ni)
+        self._served = None
+
+    n_events = property(lambda self: int(self._seq_ipos.numel()))
+
+    # ---- training -------------------------------------------------------------------------------------------------------
+    def sample(self, K, step0=None, seed=None):
+        """(u, e, c, i, j, valid) int32 [K, batch] and dropped int32[K]: the slots of the global steps step0 .. step0 + K - 1
+        (``step0`` = the next step to take when None) -- u, i, j positions into ``users`` / ``items``, e the event's number
+        in the sequence CSR and c its context length."""
+        with torch.cuda.device(self.device):
+            return ops.fpmc_sample(self._seq_offsets_dev, self._seq_upos, self._seq_ipos, self._offsets_dev, self._row_ipos,
+                                   self.users.numel(), self.items.numel(), self.window,
+                                   self.seed if seed is None else int(seed), self.step if step0 is None else int(step0),
+                                   int(K), self.batch)
+
+    def _tables(self):
+        return [self.user_factors, self.item_factors, self.next_factors, self.prev_factors]
+
+    def _update(self, u, ij, ctx_ids, grads):
+        """The engine over the four tables: the id list [u ; i ; j ; i ; j ; ctx_ids] of the gradient rows as the four
+        segments u, ij = [i ; j] (for A), ij again (for Bn) and ctx_ids (the sort takes at most four)."""
+        nu, ni = int(self.users.numel()), int(self.items.numel())
+        ids, table_of = [u, ij, ij], [0, 1, 2]
+        if ctx_ids.numel():
+            ids, table_of = ids + [ctx_ids], table_of + [3]
+        self._apply(self._tables(), [self.user_accum, self.item_accum, self.next_accum, self.prev_accum], ids,
+                    [0, nu, nu + ni, nu + 2 * ni, nu + 3 * ni], grads, table_of)
+
+    def train_steps(self, K):
+        """K steps: one sampler launch, one scan of c over [K, batch] and ONE host read of the K totals; then per step the
+        forward / backward, the sort and the update over the four tables.  Returns BPR's per-step mean loss.  Raises
+        ``FactorizationError`` when a kernel met a position outside its table."""
+        K = self._check_K(K)
+        dev, B = self.device, self.batch
+        with torch.cuda.device(dev):
+            u, e, c, i, j, valid, dropped = self.sample(K)
+            oo = torch.zeros((K, B + 1), dtype=torch.int64, device=dev)
+            oo[:, 1:] = torch.cumsum(c, 1)
+            host = torch.stack([oo[:, -1], dropped.to(torch.int64)]).cpu().numpy()       # the one read: totals and dropped
+            tables, ij = self._tables(), torch.cat([i, j], dim=1)
+
+            def one_step(k):
+                loss_t, _, grads, ctx_ids = ops.fpmc_fwd_bwd(*tables, self._seq_ipos, u[k], e[k], c[k], i[k], j[k], valid[k],
+                                                             self.reg, ctx_offsets=oo[k], M=int(host[0, k]),
+                                                             failed=self._failed)
+                self._update(u[k], ij[k], ctx_ids, grads)
+                return (loss_t.to(torch.float64).sum(),)
+            sums = self._run_steps(K, "an FPMC step met a position outside its table (bit 30)", one_step)
+            self._served = None
+            return _step_means(sums[0], B - host[1])
+
+    def auc(self, K=1, seed=None):
+        """``BPR.auc`` over FPMC's own slots: the fraction of K * batch sampled (event, unseen item) slots whose next item
+        the model scores above the unseen one."""
+        with torch.cuda.device(self.device):
+            u, e, c, i, j, valid, _ = (t.reshape(-1) for t in
+                                       self.sample(int(K), step0=0, seed=self.seed + 1 if seed is None else seed)[:7])
+            self._failed.zero_()
+            _, d, _, _ = ops.fpmc_fwd_bwd(*self._tables(), self._seq_ipos, u, e, c, i, j, valid, self.reg, want_grads=False,
+                                          want_diff=True, failed=self._failed)
+            self._raise_bad_position("auc met a position outside its table (bit 30)")
+            ok = valid != 0
+            n = int(ok.sum())
+            wins, ties = int(((d > 0) & ok).sum()), int(((d == 0) & ok).sum())
+        return (wins + 0.5 * ties) / n if n else float("nan")
+
+    # ---- serving --------------------------------------------------------------------------------------------------------
+    def _context_rows(self, bags, n):
+        """float32[n, rank]: ``ops.bag_sum`` of every bag of `bags` over ``prev_factors`` (zeros without bags)."""
+        if bags is None:
+            return torch.zeros((n, self.rank), dtype=torch.float32, device=self.device)
+        self._failed.zero_()
+        m = ops.bag_sum(self.prev_factors, *bags.args(), failed=self._failed)
+        self._raise_bad_position("a context names an item position outside the table (bit 30)")
+        return m
+
+    def _rows(self):
+        if 2 * self.rank > max_rank():
+            raise ValueError("rank = %d: score, recommend and diversify re-score rows of 2 rank by the ALS predict kernel, "
+                             "which takes at most %d: serving needs rank <= %d" % (self.rank, max_rank(), max_rank() // 2))
+        key = (self.step,) + tuple(t._version for t in self._tables())
+        if self._served is None or self._served[0] != key:
+            self._served = (key, self.query_rows(), self.item_rows())
+        return self._served[1:]
+
+    def query_rows(self, users=None):
+        """float32[n, 2 rank]: the rows ``[U_u ; m_u]`` of `users` (every known user in ``users``' order when None), m_u
+        the context of the event that would follow u's training sequence: its last ``min(length, window)`` items by
+        ``ops.bag_sum`` with the weights ``float32(1 / c)``, the chain the step kernel walks.  An unknown user gets NaN."""
+        with torch.cuda.device(self.device):
+            m = self._context_rows(self._tails, int(self.users.numel()))
+            rows = torch.cat([self.user_factors, m], 1)
+            if users is None:
+                return rows.contiguous()
+            upos = self._positions(users, self.users).to(torch.int64)
+            nan = torch.full((), float("nan"), device=self.device)
+            return torch.where((upos >= 0)[:, None], rows[upos.clamp(min=0)], nan).contiguous()
+
+    def item_rows(self):
+        """float32[ni, 2 rank]: the rows ``[A_i ; Bn_i]`` of every item in ``items``' order."""
+        return torch.cat([self.item_factors, self.next_factors], 1).contiguous()
+
+    def recommend_sequences(self, indices, doc_offsets, k=500, users=None, exclude_seen=True, slack=16):
+        """``recommend``'s lists for GIVEN sequences ``indices[doc_offsets[d]:doc_offsets[d + 1]]`` (ids in order): the query
+        of sequence d is ``[U_u ; m]`` with m built from its last ``window`` items that the model knows (unknown ids are
+        skipped) and u = ``users[d]``; with ``users=None``, or for a user the model does not know, the user half is zero:
+        pure session-based recommendation by the transition term.  `exclude_seen` leaves out the sequence's own items.
+        Returns (rec_ids, rec_scores, rec_lengths), what ``evaluate.ranking_metrics`` takes; with a known user's training
+        sequence the lists are ``recommend``'s."""
+        ids, off = _ids_and_offsets(indices, doc_offsets, self.device)
+        ndocs, dev = off.size - 1, self.device
+        with torch.cuda.device(dev):
+            item_rows = self._rows()[1]
+            docs = torch.from_numpy(np.repeat(np.arange(ndocs, dtype=np.int64), np.diff(off))).to(dev)
+            ipos = self._positions(ids, self.items).to(torch.int64)
+            known = ipos >= 0
+            docs, ipos = docs[known], ipos[known]
+            offsets = _host_offsets(torch.bincount(docs, minlength=ndocs))
+            m = self._context_rows(_tail_bags(ipos, offsets, self.window, dev), ndocs)
+            half = torch.zeros_like(m)
+            if users is not None:
+                upos = self._positions(users, self.users).to(torch.int64)
+                if upos.numel() != ndocs:
+                    raise ValueError("users must name one user per sequence")
+                half = torch.where((upos >= 0)[:, None], self.user_factors[upos.clamp(min=0)], half)
+            key = torch.unique((docs << 32) | ipos)
+            seen_offsets = _host_offsets(torch.bincount(key >> 32, minlength=ndocs)) if exclude_seen else None
+            return _recommend_rows(torch.cat([half, m], 1).contiguous(), None, torch.arange(ndocs, dtype=torch.int64, device=dev),
+                                   item_rows, self.items, k, slack, seen_offsets, key, lambda q: "sequence %d" % q, "holds",
+                                   "exclude_seen")

@@ -2232,6 +2232,96 @@ def bag_expand(table, offsets, feat, weight, rows, grad_rows, valid, out_offsets
 
 
 # ---------------------------------------------------------------------------------------------
+# Factorised Personalised Markov Chain (esr_fpmc.hip): the slot sampler and the fused forward / backward over 5 + c rows
+def fpmc_geometry():
+    """(max_window, max_rank, rank_multiple): the most context items an event takes; fpmc_fwd_bwd takes a rank that is a
+    multiple of rank_multiple and at most max_rank."""
+    window, rank, mult = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.load().esr_fpmc_geometry(ctypes.byref(window), ctypes.byref(rank), ctypes.byref(mult)), "esr_fpmc_geometry")
+    return int(window.value), int(rank.value), int(mult.value)
+
+
+def fpmc_sample(seq_offsets, seq_upos, seq_ipos, row_offsets, row_ipos, nu, ni, window, seed, step0, K, B):
+    """K steps of B slots drawn on the device: (u, e, c, i, j, valid) int32 [K, B] -- row k is global step step0 + k (mod
+    2^32) -- and dropped int32[K], the count of valid == 0 per step.  The sequences are a CSR by user in time order on the
+    DEVICE (seq_offsets int64[nu + 1], seq_upos / seq_ipos int32[nnz_seq], repeats kept), the seen pairs bpr_sample's CSR
+    (row_offsets int64[nu + 1], row_ipos int32[nnz_seen]).  The rule is esr_fpmc_sample.h's: e is the event, i its item,
+    c = min(place in u's sequence, window) its context length, j bpr_sample's negative."""
+    lib = _lib.load()
+    nu, ni, K, B, window = int(nu), int(ni), int(K), int(B), int(window)
+    nnz_seq = _check_device_csr("fpmc_sample", "seq_offsets", seq_offsets, seq_upos, seq_ipos, nu, ni=ni, K=K, B=B)
+    _req(row_offsets, torch.int64, "row_offsets"), _req(row_ipos, torch.int32, "row_ipos")
+    nnz_seen = row_ipos.numel()
+    if row_offsets.numel() != nu + 1 or not 1 <= nnz_seen <= 2 ** 31 - 1:
+        raise ValueError("fpmc_sample: row_offsets holds %d entries for nu = %d, row_ipos %d pairs (in [1, 2^31 - 1])"
+                         % (row_offsets.numel(), nu, nnz_seen))
+    if not 1 <= window <= fpmc_geometry()[0]:
+        raise ValueError("fpmc_sample: window = %d outside [1, %d]" % (window, fpmc_geometry()[0]))
+    out = torch.empty((6, K, B), dtype=torch.int32, device=seq_upos.device)
+    dropped = torch.empty(K, dtype=torch.int32, device=seq_upos.device)
+    check(lib.esr_fpmc_sample(_p(seq_offsets), _p(seq_upos), _p(seq_ipos), nnz_seq, _p(row_offsets), _p(row_ipos), nnz_seen,
+                              nu, ni, window, int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF, K, B, _p(out[0]),
+                              _p(out[1]), _p(out[2]), _p(out[3]), _p(out[4]), _p(out[5]), _p(dropped), _stream()),
+          "esr_fpmc_sample")
+    return out[0], out[1], out[2], out[3], out[4], out[5], dropped
+
+
+def fpmc_fwd_bwd(user_table, item_table, next_table, prev_table, seq_ipos, u, e, c, i, j, valid, reg, ctx_offsets=None,
+                 M=None, want_grads=True, want_diff=False, failed=None):
+    """(loss_t float32[B], diff_t float32[B] or None, grads float32[5 B + M, D] or None, ctx_ids int32[M] or None) of the
+    slots (u, e, c, i, j) int32[B] of fpmc_sample over the tables U [nu, D] and A, Bn, P [ni, D]:
+    d = U_u . (A_i - A_j) + m . (Bn_i - Bn_j), m the bag of the c items before event e (seq_ipos[e - c .. e - 1], weight
+    1 / c each), loss_t = softplus(-d), diff_t = d, and the gradient rows [U ; A_i ; A_j ; Bn_i ; Bn_j ; context
+    occurrences] in occurrence order with the L2 term reg * row (include/esr_hip.h); ctx_ids names the P row of every
+    context occurrence.  ctx_offsets int64[B + 1] is the exclusive scan of c and M its last entry (both computed here,
+    with one host read, when None).  valid int32[B] or None (all valid): valid = 0 gives zeros under the real ctx_ids.
+    `failed` (int32[1], device; a scratch word when None) gets bit 30 when a position lies outside its table or a slot's
+    (e, c) does not stand -- that slot gives zeros; the caller zeroes and reads it."""
+    lib = _lib.load()
+    tables = (user_table, item_table, next_table, prev_table)
+    for t, name in zip(tables, ("user_table", "item_table", "next_table", "prev_table")):
+        _req(t, torch.float32, name)
+    if any(t.dim() != 2 for t in tables) or len({int(t.shape[1]) for t in tables}) != 1 or \
+            not item_table.shape == next_table.shape == prev_table.shape:
+        raise ValueError("user_table [nu, rank] and item_table, next_table, prev_table [ni, rank] must share one rank")
+    _req(seq_ipos, torch.int32, "seq_ipos")
+    ids = (u, e, c, i, j)
+    for t, name in zip(ids, "uecij"):
+        _req(t, torch.int32, name)
+    B, D = u.numel(), int(user_table.shape[1])
+    if any(t.numel() != B for t in ids):
+        raise ValueError("u, e, c, i and j must have one length")
+    if valid is not None:
+        _req(valid, torch.int32, "valid")
+        if valid.numel() != B:
+            raise ValueError("valid must hold one entry per slot")
+    _check_rank4(D, *fpmc_geometry()[1:])
+    dev = user_table.device
+    failed = _failed_word(failed, dev)
+    loss_t = torch.empty(B, dtype=torch.float32, device=dev)
+    diff_t = torch.empty(B, dtype=torch.float32, device=dev) if want_diff else None
+    grads = ctx_ids = None
+    if want_grads:
+        if ctx_offsets is None:
+            ctx_offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(c.reshape(-1), 0, out=ctx_offsets[1:])
+            M = int(ctx_offsets[-1]) if B else 0
+        _req(ctx_offsets, torch.int64, "ctx_offsets")
+        M = int(M)
+        if ctx_offsets.numel() != B + 1 or not 0 <= M <= 2 ** 31 - 1:
+            raise ValueError("fpmc_fwd_bwd: ctx_offsets must hold B + 1 entries and M = %d lie in [0, 2^31 - 1]" % M)
+        grads = torch.empty((5 * B + M, D), dtype=torch.float32, device=dev)
+        ctx_ids = torch.empty(M, dtype=torch.int32, device=dev)
+    if B:
+        check(lib.esr_fpmc_fwd_bwd(_p(user_table), user_table.shape[0], _p(item_table), _p(next_table), _p(prev_table),
+                                   item_table.shape[0], D, _p(seq_ipos), seq_ipos.numel(), _p(u), _p(e), _p(c), _p(i), _p(j),
+                                   _p(valid), B, _p(ctx_offsets) if want_grads else 0, M if want_grads else 0, float(reg),
+                                   _p(loss_t), _p(diff_t), _p(grads), _p(ctx_ids) if want_grads and M else 0, _p(failed),
+                                   _stream()), "esr_fpmc_fwd_bwd")
+    return loss_t, diff_t, grads, ctx_ids
+
+
+# ---------------------------------------------------------------------------------------------
 # Diversity re-ranking (esr_rerank.hip): MMR over candidate lists, intra-list similarity
 def rerank_geometry(D, width):
     """A dict for lists of `width` candidates over rows of rank `D`: the limits (max_rank, rank_multiple, max_width,

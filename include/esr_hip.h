@@ -1246,6 +1246,51 @@ int esr_bag_expand(const float* table, int64_t nf, int D, const int64_t* bag_off
                    const int32_t* valid, const int64_t* out_offsets, int64_t n, int64_t M, float reg, int32_t* out_feat,
                    float* out_grads, int32_t* failed, esr_stream_t stream);
 
+/* ---- Factorised Personalised Markov Chain (Rendle, Freudenthaler, Schmidt-Thieme, WWW 2010; esr_fpmc.hip) ----
+ * Next-item ranking trained with the BPR step: score(u, event, i) = U_u . A_i + m . Bn_i over four f32 tables of one rank D,
+ * user_table [nu, D] and item_table (A), next_table (Bn), prev_table (P) [ni, D].  The users' sequences are a CSR in time
+ * order with repeats kept: seq_offsets int64[nu + 1], seq_upos / seq_ipos int32[nnz_seq].  The context of event e is the
+ * c <= window <= 8 events e - c .. e - 1 of the same user, oldest first, and m their bag by the rule of esr_bag_rule.h with
+ * every weight w = 1.0f / c:  m = fmaf(w, P[l], m) from +0.0f in that order (c = 0: zeros).  No workspace; the calls
+ * never synchronise.
+ *   geometry    max_window (8); D is a multiple of rank_multiple (4) and at most max_rank (128).
+ *   sample      K steps of B slots in one launch, outputs int32 [K, B] row-major, row k = global step step0 + k (mod 2^32).
+ *               The rule is esr_fpmc_sample.h's fpmc_sample_slot: esr_bpr_sample's Philox stream; word 0 of block 0 picks
+ *               the event e by multiply-high over nnz_seq, u = seq_upos[e], i = seq_ipos[e], c = min(e - seq_offsets[u],
+ *               window); the next 15 words are esr_bpr_sample's negative candidates, tested against u's row of the seen
+ *               CSR (row_offsets int64[nu + 1], row_ipos int32[nnz_seen], ascending and distinct within a row); if all are
+ *               seen the last one is written with valid = 0.  A slot is a function of (seed, step, slot, the CSRs, window)
+ *               alone.  dropped int32[K] = the exact count of valid == 0 per step (zeroed by the call; integer atomics).
+ *   fwd_bwd     per slot t (u, e, c, i, j int32[B]; valid int32[B] or null = all valid) with x = U[u], the context ids
+ *               l_n = seq_ipos[e - c + n] and m as above:  d = x . (A_i - A_j) + m . (Bn_i - Bn_j) in f32 in the order
+ *               esr_fpmc.hip states (a function of D alone), loss_t[t] = max(-d, 0) + log1pf(expf(-|d|)), diff_t[t] = d
+ *               (may be null), g = sigmoid(-d), and into grads float[5 B + M, D] = [U rows ; A_i rows ; A_j rows ; Bn_i rows ;
+ *               Bn_j rows ; context occurrences]
+ *                 g_u = reg x - g (A_i - A_j),  g_ai = reg A_i - g x,  g_aj = reg A_j + g x,
+ *                 g_bi = reg Bn_i - g m,  g_bj = reg Bn_j + g m,  g_m = -g (Bn_i - Bn_j),
+ *                 occurrence n: fmaf(w, g_m, reg * P[l_n]) per element, at row 5 B + ctx_offsets[t] + n,
+ *               with ctx_ids[ctx_offsets[t] + n] = l_n.  ctx_offsets int64[B + 1] is the exclusive scan of c and M =
+ *               ctx_offsets[B], both computed by the caller (esr_bag_expand's convention).  grads null: forward only,
+ *               ctx_offsets and ctx_ids are not read.  valid[t] == 0 writes zero rows, loss_t = 0 and diff_t = 0 and
+ *               reads no table row, but its c occurrences keep their ids: the layout depends on the draw alone.  A u, i,
+ *               j or context id outside its table, an e outside [0, nnz_seq), a c outside [0, min(8, e)] or a range of
+ *               ctx_offsets that is not c rows long sets bit 30 of *failed (the caller zeroes and reads it) whatever valid
+ *               says; that slot reads no table row and writes zeros, and every row of its (clamped) range gets ctx_ids = 0
+ *               where the id was refused.  No reduction across slots: an output depends on its own slot, reg and D only.
+ * 1 <= nu, ni, nnz_seq, nnz_seen, K, B <= 2^31 - 1; nu + 3 ni <= 2^31 - 1 (the virtual row space of the update over the four
+ * tables); 0 <= M <= 2^31 - 1; 1 <= window <= 8; reg finite and not negative.  Tables and grads 16-byte aligned, the int64
+ * arrays 8-byte aligned. */
+int esr_fpmc_geometry(int* max_window, int* max_rank, int* rank_multiple);
+int esr_fpmc_sample(const int64_t* seq_offsets, const int32_t* seq_upos, const int32_t* seq_ipos, int64_t nnz_seq,
+                    const int64_t* row_offsets, const int32_t* row_ipos, int64_t nnz_seen, int64_t nu, int64_t ni, int window,
+                    uint64_t seed, uint32_t step0, int64_t K, int64_t B, int32_t* out_u, int32_t* out_e, int32_t* out_c,
+                    int32_t* out_i, int32_t* out_j, int32_t* out_valid, int32_t* dropped, esr_stream_t stream);
+int esr_fpmc_fwd_bwd(const float* user_table, int64_t nu, const float* item_table, const float* next_table,
+                     const float* prev_table, int64_t ni, int D, const int32_t* seq_ipos, int64_t nnz_seq, const int32_t* u,
+                     const int32_t* e, const int32_t* c, const int32_t* i, const int32_t* j, const int32_t* valid, int64_t B,
+                     const int64_t* ctx_offsets, int64_t M, float reg, float* loss_t, float* diff_t, float* grads,
+                     int32_t* ctx_ids, int32_t* failed, esr_stream_t stream);
+
 /* ---- Diversity re-ranking (MMR, Carbonell and Goldstein 1998; intra-list similarity, Ziegler et al. 2005; esr_rerank.hip) ----
  * rows float[ni, D] are the items' rows (D a multiple of 4 in [4, 128]), cand int32[nq, width] item POSITIONS into rows,
  * rel float[nq, width], lengths int32[nq] or null (full rows), 1 <= width <= 1024.  The rule of both calls is stated in
