@@ -7,7 +7,7 @@ second, and the forward / backward kernel against the time its own bytes -- ``(5
 plus ``4 (6 + 2 c)`` of ids per slot, c the mean context length -- take at the HBM peak.  BPR's step on the same corpus
 stands beside it, and the same FPMC step restated in plain torch runs in the same session on the same slots.  Hold-out
 next-item recall and nDCG at 10 under ``split_last`` for FPMC against BPR trained as long, both at `quality_rank` (serving
-re-scores rows of 2 rank by the ALS predict kernel: rank <= 32).  Prints JSON lines.
+re-scores rows of 2 rank by the ALS predict kernel: rank <= 64).  Prints JSON lines.
 
     python benchmarks/fpmc_bench.py [--reps 3] [--steps 32] [--train_steps 1500] [--skip_torch] [--skip_quality]
 """

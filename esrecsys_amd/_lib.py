@@ -253,6 +253,7 @@ SIGNATURES = {
                                       c_i64, c_vp, c_i32p, c_i64, c_int, c_int, c_int, c_int, c_int, c_i32p, c_f32p, c_i32p,
                                       c_vp]),
     "esr_als_max_rank": (c_int, []),
+    "esr_als_predict_max_rank": (c_int, []),
     "esr_als_geometry": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "esr_als_solve_workspace_bytes": (c_size, [c_i64, c_i64, c_int]),
     "esr_als_solve_rows": (c_int, [c_f32p, c_i64, c_int, c_vp, c_i32p, c_f32p, c_i64, c_i64, c_f32, c_int, c_f32p, c_i32p, c_vp,

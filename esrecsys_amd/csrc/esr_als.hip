@@ -46,12 +46,14 @@
 #include <vector>
 
 #include "esr_common.h"
+#include "esr_row4.h"
 
 namespace esr {
 
 typedef float als_f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kAlsMaxRank = 64;
+constexpr int kAlsMaxRank = 64;                 // the solves and the Gram: one wave holds a rank x rank f32 matrix in LDS
+constexpr int kAlsPredictMaxRank = kRow4MaxRank;  // predict is a per-pair loop over the row: the widest row-group table
 constexpr int kAlsChunk = 256;                  // ratings per chunk (even: an MFMA step takes two)
 constexpr int kAlsWaves = kBlock / kWave;
 constexpr int kAlsChunksPerWg = kAlsWaves;      // one chunk per wave of the workgroup
@@ -596,6 +598,8 @@ extern "C" {
 
 int esr_als_max_rank(void) { return kAlsMaxRank; }
 
+int esr_als_predict_max_rank(void) { return kAlsPredictMaxRank; }
+
 int esr_als_geometry(int* chunk, int* chunks_per_workgroup) {
   ESR_REQUIRE(chunk && chunks_per_workgroup, "esr_als_geometry: null pointer");
   *chunk = kAlsChunk;
@@ -666,7 +670,7 @@ int esr_als_predict(const float* user_factors, int64_t nu, const float* item_fac
                     const int32_t* user_pos, const int32_t* item_pos, const double* offset, const float* targets, int64_t nq,
                     float* out, esr_stream_t stream) {
   TraceScope trace_scope_("esr_als_predict");
-  ESR_REQUIRE(rank >= 1 && rank <= kAlsMaxRank, "esr_als_predict: rank=%d not in [1, %d]", rank, kAlsMaxRank);
+  ESR_REQUIRE(rank >= 1 && rank <= kAlsPredictMaxRank, "esr_als_predict: rank=%d not in [1, %d]", rank, kAlsPredictMaxRank);
   ESR_REQUIRE(nu >= 0 && nu <= (int64_t)INT32_MAX && ni >= 0 && ni <= (int64_t)INT32_MAX && nq >= 0,
               "esr_als_predict: bad sizes nu=%lld ni=%lld nq=%lld", (long long)nu, (long long)ni, (long long)nq);
   if (nq == 0) return ESR_OK;

@@ -64,6 +64,12 @@ def max_rank():
     return ops.als_max_rank()
 
 
+def predict_max_rank():
+    """The widest row ``score``, ``recommend`` and ``diversify`` take (esr_als_predict_max_rank(): the predict kernel is a
+    per-pair loop, so its cap is the row-group cap of ``ops.bpr_geometry()``, above ``max_rank()``)."""
+    return ops.als_predict_max_rank()
+
+
 def _raise_failed(word, side):
     """The failure word of a row solve as a ``FactorizationError``: bit 30, bit 29, else the count of unsolved rows."""
     if word & FAIL_BAD_POSITION:
@@ -1200,7 +1206,7 @@ class FPMC(BPR):
     Serving.  A query is the row ``[U_u ; m]`` and an item the row ``[A_i ; Bn_i]``, both 2 rank wide, so ``score``,
     ``recommend`` and ``diversify`` are the base class's on those rows (``query_rows`` / ``item_rows``): for a known user m
     is built from the tail of the training sequence, the prediction of the NEXT event.  They re-score by the ALS predict
-    kernel, which takes rows of at most ``max_rank()``: serving needs ``2 rank <= max_rank()``.
+    kernel, which takes rows of at most ``predict_max_rank()``: serving needs ``2 rank <= predict_max_rank()``.
 
     The tables are ``randn * init_scale`` from the seeded CPU generator in the order U, A, Bn, P; the other constructor
     arguments, ``users`` / ``items`` and ``step`` are ``BPR``'s."""
@@ -1314,9 +1320,10 @@ class FPMC(BPR):
         return m
 
     def _rows(self):
-        if 2 * self.rank > max_rank():
+        top = predict_max_rank()
+        if 2 * self.rank > top:
             raise ValueError("rank = %d: score, recommend and diversify re-score rows of 2 rank by the ALS predict kernel, "
-                             "which takes at most %d: serving needs rank <= %d" % (self.rank, max_rank(), max_rank() // 2))
+                             "which takes at most %d: serving needs rank <= %d" % (self.rank, top, top // 2))
         key = (self.step,) + tuple(t._version for t in self._tables())
         if self._served is None or self._served[0] != key:
             self._served = (key, self.query_rows(), self.item_rows())

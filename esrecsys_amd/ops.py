@@ -1901,8 +1901,13 @@ def userknn_recommend(table_ids, table_neighbours, table_scores, table_lengths, 
 # ---------------------------------------------------------------------------------------------
 # matrix factorisation of explicit ratings by alternating least squares (esr_als.hip)
 def als_max_rank():
-    """The largest rank esr_als_solve_rows and esr_als_predict take."""
+    """The largest rank esr_als_solve_rows and esr_als_gram take."""
     return int(_lib.load().esr_als_max_rank())
+
+
+def als_predict_max_rank():
+    """The widest row esr_als_predict takes: a per-pair loop, so the row-group cap of bpr_geometry() and not als_max_rank()."""
+    return int(_lib.load().esr_als_predict_max_rank())
 
 
 def als_geometry():

@@ -1118,8 +1118,11 @@ int esr_userknn_recommend(const int32_t* table_ids, const int32_t* table_neighbo
  *               rank), 16-byte aligned; the call waits for the stream once (its row lists are copied from host memory).
  *   predict     out[q] = float(offset[u] + sum_d double(x_u[d]) * double(y_i[d])), the sum in fp64 in ascending d from 0,
  *               u = user_pos[q], i = item_pos[q] (positions; NaN where either is outside its table); offset double[nu] or
- *               null (0).  With targets float[nq] (residual mode): out[q] = float(double(targets[q]) - that value). */
+ *               null (0).  With targets float[nq] (residual mode): out[q] = float(double(targets[q]) - that value).
+ *               predict is a per-pair loop that needs no rank x rank matrix: it takes rank in [1, the predict-max-rank
+ *               query] (128, the widest row of the float4 row-group models), above what the solves and the Gram take. */
 int esr_als_max_rank(void);
+int esr_als_predict_max_rank(void);
 int esr_als_geometry(int* chunk, int* chunks_per_workgroup);
 size_t esr_als_solve_workspace_bytes(int64_t n_rows, int64_t nnz, int rank);
 int esr_als_solve_rows(const float* other_factors, int64_t n_other, int rank, const int64_t* row_offsets, const int32_t* cols,
