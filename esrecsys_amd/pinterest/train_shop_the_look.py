@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..loop_plan import Group, GroupPlanner, hint_long_runs, screen_group
 from ..train_state import FusedScatter, RowGrads, SegmentIndex
 
 # Flags with the reference's names and defaults (pinterest/train_shop_the_look.py:46-69).
@@ -113,10 +114,7 @@ class PresortedTriplets:
     def long_runs(self):
         """0 when the long-run hint has reached the host and says no id has a run longer than a 32-position chunk, 1
         when it says one has, -1 while nobody knows."""
-        if self.hint is None or not self.hint[2].query():
-            return -1
-        from ..wikipedia.train_cooccurence import hint_value
-        return hint_value(self.hint)
+        return hint_long_runs(self.hint)
 
     def take(self):
         if self.event is not None:
@@ -288,21 +286,11 @@ def train_step(state, scene, pos_product, neg_product, regularization, batch_siz
     return new_state, loss.reshape(())
 
 
-class _Group:
-    """A group of batches whose id lists were sorted and planned together (``_FusedTripletLoop.sort_batch``)."""
-    __slots__ = ("nb", "B", "ptrs", "sorted_ptr", "perm_ptr", "plans_ptr", "which", "gen", "keep", "side")
-
-    def __init__(self, nb, B, ptrs, sorted_ptr, perm_ptr, plans_ptr, which, gen, keep, side=False):
-        self.nb, self.B, self.ptrs, self.sorted_ptr, self.perm_ptr = nb, B, ptrs, sorted_ptr, perm_ptr
-        self.plans_ptr, self.which, self.gen, self.keep = plans_ptr, which, gen, keep  # keep: the id tensors, alive
-        self.side = side  # sorted + planned on the second stream: the group's first step waits for its event
-
-
 class _FusedTripletLoop:
     """What the one-pass triplet step needs that does not change from batch to batch, resolved once: tower / accumulator
     / RowVersions pointers, the library entry points, a loss slot per step, and a ring of id-sort buffers on the side
     stream.  At the reference's batch sizes the step is three short kernels behind a two-launch id sort; the sort needs
-    the ids only, so it runs `depth` batches ahead on a second stream (same idea as wikipedia.train_epoch), and the
+    the ids only, so it runs `depth` batches ahead on a second stream (same idea as GloVe's train_epoch), and the
     per-step Python is two library calls and three event operations."""
 
     def __init__(self, state, steps, depth):
@@ -335,18 +323,10 @@ class _FusedTripletLoop:
         self.depth = depth
         self.ring, self.B = [], -1
         self.ws = None
-        self.batch_buf, self.sort_batch_max = [None, None], _SORT_BATCH  # two sets: group g + 1 is made before g steps
-        self.batch_ptrs = [(ctypes.c_void_p * (3 * _SORT_BATCH))(), (ctypes.c_void_p * (3 * _SORT_BATCH))()]
-        self.long_arr = (ctypes.c_int32 * _SORT_BATCH)()
-        # esr_triplet_plan's hints ("list b has a run longer than a chunk": only then is the long-run launch needed),
-        # written by the plan kernel straight into pinned host memory; a group is planned one group ahead of its steps,
-        # so the words have landed when they are issued (if they have not, the launch is simply made)
-        self.hints_host = torch.zeros((2, _SORT_BATCH), dtype=torch.int32).pin_memory()
-        self.hints_event = [torch.cuda.Event(), torch.cuda.Event()]
+        # groups of batches: sorted and planned (esr_triplet_plan) one group ahead of their steps
+        self.planner, self.plan_fn = GroupPlanner(self.dev, _SORT_BATCH, _HINT_WAIT, 3), self.lib.esr_triplet_plan
         self.drawn_event = [torch.cuda.Event(), torch.cuda.Event()]
-        self.hints_known = [None, None]  # per set: list of long_runs values once the event has been seen complete
         self.group_ws, self.group_ws_B = None, -1  # esr_triplet_train_steps' workspace, sized for the group it steps
-        self.gen = 0
         self.allow_side = True  # (presorted()'s per-step calls keep sort + plan on the main stream: see _plan_on_side)
         if self.direct:
             self.fixed_s = (self.st.data_ptr(), None, None, self.acc_s.data_ptr(), self.Vs)
@@ -436,68 +416,36 @@ class _FusedTripletLoop:
         B = group[0][0].numel()
         self._sized(B)
         nb, n = len(group), 3 * B
-        pb = ops._ws_bytes("esr_triplet_plan_bytes", B)
-        if self.batch_buf[which] is None or self.batch_buf[which][0].shape != (self.sort_batch_max, n):
-            self.batch_buf[which] = (torch.empty((self.sort_batch_max, n), dtype=torch.int32, device=self.dev),
-                                     torch.empty((self.sort_batch_max, n), dtype=torch.int32, device=self.dev),
-                                     ops._ws(ops._ws_bytes("esr_segment_sort_batched_workspace_bytes", n,
-                                                           self.sort_batch_max), self.dev),
-                                     ops._aligned_bytes(self.sort_batch_max * pb, self.dev))
-        srt, prm, ws, plans = self.batch_buf[which]
-        # (the library call itself, not ops.segment_sort_batched: its per-tensor checks and ctypes arrays were 67 us per
-        # group -- the ids were validated by ``ids``, the arrays are kept)
-        ptrs = self.batch_ptrs[which]
+        ptrs = self.planner.ptrs[which]  # (the ids were validated by ``ids``)
         i = 0
         for g in group:
             ptrs[i], ptrs[i + 1], ptrs[i + 2] = g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr()
             i += 3
-        stream, raw = self.main, self.main_raw
+        # (new plan records are zeroed on the main stream: in front of the hand-over to the second one)
+        bufs = self.planner.buffers(which, n, ops._ws_bytes("esr_triplet_plan_bytes", B))
+        stream = self.main
         on_side = _plan_on_side(B) and self.allow_side
         if on_side:
             # sort + plan of group g + 1 beside the steps of group g: the side stream waits for what the main stream held
             # when the group was drawn (the steps of group g - 1, whose buffers this set reuses; id copies), the main
             # stream waits for the plan before the group's first step (step_group)
-            stream, raw = self.side, self.side.cuda_stream
+            stream = self.side
             self.drawn_event[which].record(self.main)
             self.side.wait_event(self.drawn_event[which])
-        self.check(self.lib.esr_segment_sort_ids_batched(ptrs, self.cnt, self.off, 3, nb, self.Vs + self.Vp,
-                                                         srt.data_ptr(), prm.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                         raw), "esr_segment_sort_ids_batched")
-        self.gen += 1
-        self.check(self.lib.esr_triplet_plan(ptrs, nb, B, self.Vs, srt.data_ptr(), prm.data_ptr(), plans.data_ptr(),
-                                             self.hints_host[which].data_ptr(), self.gen, raw),
-                   "esr_triplet_plan")
-        self.hints_event[which].record(stream)
-        self.hints_known[which] = None
         # the whole group is stepped by ONE library call (esr_triplet_train_steps): at the reference's own batch sizes
         # (16 - 128 triplets: train_shop_the_look.py:60) a step is ~12 us of kernels, at 8192 it is 21 us -- less than
         # a 29-argument foreign call plus the Python around it
-        return _Group(nb, B, ptrs, srt.data_ptr(), prm.data_ptr(), plans.data_ptr(), which, self.gen, group, on_side)
+        return self.planner.plan(which, nb, B, bufs, (self.cnt, self.off, self.Vs + self.Vp),
+                                 (self.plan_fn, (ptrs, nb, B, self.Vs)), group, stream, on_side)
 
     def step_group(self, k, gr, regularization, batch_size):
         """Steps k .. k + gr.nb - 1: the batches of a sorted and planned group, issued by one library call."""
-        known = self.hints_known[gr.which]
-        done = known is not None
-        if known is None:
-            # the HOST waits for the group's plan launch: it was queued in front of the steps of the group before, so
-            # the wait ends with those steps (a group's worth of work) still queued -- the device never runs dry, the
-            # host stays at most two groups ahead, and every step knows whether it needs its long-run launch (a loop
-            # that ran further ahead never saw a hint in time and made all of them: 4.8 us per step at B = 8192)
-            if _HINT_WAIT:
-                self.hints_event[gr.which].synchronize()
-            if self.hints_event[gr.which].query():
-                done = True
-                known = self.hints_known[gr.which] = self.hints_host[gr.which].tolist()
-        if gr.side and not done:
+        long_runs = self.planner.long_runs(gr)  # (None: the library makes every long-run launch)
+        if gr.side and long_runs is None:
             # (the plan was made on the second stream: the steps wait for it ON THE DEVICE only when the host has not seen
             # its event complete -- a stream wait is a barrier packet in front of the group's first step, ~5 us of idle
             # main stream per group for an event that has long fired)
-            self.main.wait_event(self.hints_event[gr.which])
-        long_runs = None
-        if known is not None:  # (else: the hint has not reached the host; the library makes every long-run launch)
-            long_runs = self.long_arr
-            for j in range(gr.nb):
-                long_runs[j] = 1 if known[j] == gr.gen else 0
+            self.main.wait_event(self.planner.events[gr.which])
         # (the group's OWN batch size: the next group -- sorted before this one is stepped -- may have resized self.ws)
         if gr.B != self.group_ws_B:
             self.group_ws = ops._ws(ops._ws_bytes("esr_triplet_step_workspace_bytes", gr.B, self.D), self.dev)
@@ -559,16 +507,11 @@ class PlannedTriplets:
         k = ctx.next_loss_slot()
         n = 3 * gr.B
         if gr.side and j == 0:  # (the group's sort + plan ran on the second stream: its first step waits for them)
-            ctx.main.wait_event(ctx.hints_event[gr.which])
-        known = ctx.hints_known[gr.which]
-        if known is None:
-            # the group's plan launch was queued a whole group ahead of this step (see presorted): the wait ends with that
-            # group's steps still in the queue, and every step then knows whether it needs its long-run launch
-            if _HINT_WAIT:
-                ctx.hints_event[gr.which].synchronize()
-            if ctx.hints_event[gr.which].query():
-                known = ctx.hints_known[gr.which] = ctx.hints_host[gr.which].tolist()
-        long_runs = -1 if known is None else (1 if known[j] == gr.gen else 0)
+            ctx.main.wait_event(ctx.planner.events[gr.which])
+        long = gr.long
+        if long is None:  # (once per group: its plan launch was queued a whole group ahead of this step, see presorted)
+            long = ctx.planner.long_runs(gr)
+        long_runs = -1 if long is None else long[j]
         if gr.B != ctx.group_ws_B:
             ctx.group_ws = ops._ws(ops._ws_bytes("esr_triplet_step_workspace_bytes", gr.B, ctx.D), ctx.dev)
             ctx.group_ws_B = gr.B
@@ -611,7 +554,7 @@ def presorted(state, batches):
     which = 0
 
     def draw():
-        """('group', _Group) of 2 .. 8 equal-sized triplet batches, or ('plain', [batches]) to pass through, or None."""
+        """('group', Group) of 2 .. 8 equal-sized triplet batches, or ('plain', [batches]) to pass through, or None."""
         nonlocal which
         first = next(it, None)
         if first is None:
@@ -653,7 +596,7 @@ def presorted(state, batches):
 # Default 0: measured with depth 2 at B = 8192 the loop is host-bound (52 us per step against 41 us in line: three event
 # operations and a second library call per step cost more than the 15 us sort they hide), and at B = 262 144 the sort
 # beside the HBM-bound update kernel slows that kernel by more than its own length (0.689 against 0.640 ms) -- the same
-# finding as for the GloVe step, where only filling the gaps BETWEEN steps pays (wikipedia.train_epoch).
+# finding as for the GloVe step, where only filling the gaps BETWEEN steps pays (its train_epoch).
 _LOOP_DEPTH = max(0, int(_os.environ.get("ESR_STL_PRESORT_DEPTH", "0")))
 # Batches whose id lists are sorted together, by one library call on the main stream, before the first of them is
 # stepped (esr_segment_sort_ids_batched; ESR_STL_SORT_BATCH=1: every step sorts its own list in line).  Up to 2^20 ids per
@@ -718,15 +661,8 @@ def _inbatch_steps(state, it, first, num_steps, regularization, batch_size, scal
         if sparse and _SORT_BATCH > 1 and len(group) > 1 and n <= _SORT_BATCH_MAX_IDS and \
                 all(g[0].numel() == group[0][0].numel() == g[1].numel() for g in group):
             srt, prm = ops.segment_sort_batched([list(g) for g in group], (0, Vs), Vs + Vp)
-            # one screening launch for the whole group (the [nb, n] array as one list: a run across two lists can only
-            # make the answer "long"): hint word in pinned memory, read once its event is complete -- a group without
-            # hot ids then skips the long-run launch of every optimizer step (5 us of 237 at C2)
-            from ..wikipedia.train_cooccurence import _hint_slot
-            hh, gen = _hint_slot(dev)
-            ops.long_run_hint(srt.reshape(-1), 32, hh, gen)
-            ev = torch.cuda.Event()
-            ev.record()
-            hint = (hh, gen, ev)
+            # (a group without hot ids then skips the long-run launch of every optimizer step: 5 us of 237 at C2)
+            hint = screen_group(srt, dev)
             return [PresortedTriplets(g[0], g[1], None, srt[j], prm[j], None, hint) for j, g in enumerate(group)]
         return [PresortedTriplets(g[0], g[1], None, None, None, None) for g in group]
 
@@ -833,7 +769,7 @@ def _train_steps(state, batches, num_steps, regularization, batch_size, scale, p
             # the NEXT group is drawn, sorted and planned before this one is stepped: its long-run hints reach the host
             # a whole group ahead of the steps that ask for them
             following = draw_group(False)
-            if type(handles) is _Group:
+            if type(handles) is Group:
                 ctx.step_group(k, handles, regularization, batch_size)
                 k += handles.nb
             else:

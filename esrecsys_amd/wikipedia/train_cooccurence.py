@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..loop_plan import Group, GroupPlanner, _hint_slot, hint_long_runs, screen_group
 from ..train_state import RowGrads, SegmentIndex
 from .models import Glove
 
@@ -151,13 +152,13 @@ def fused_step_available(state):
 class PresortedInputs:
     """The occurrence ids of a batch, already on the device and sorted on the side stream (``presort_inputs``): the sort
     needs the ids only, so ``train_epoch`` runs it for batch k + 1 while batch k's update kernel streams the rows.  With
-    the batch's counts at hand the step's plan record is made there too (``plan``; ``hint`` = (pinned int32 [1], gen):
-    the word equals gen when a token has a run longer than a chunk -- only then does the step need its long-run launch)."""
+    the batch's counts at hand the step's plan record is made there too (``plan``; ``hint`` = (pinned int32 [1], gen,
+    event recorded behind the hint's launch): the word equals gen when a token has a run longer than a chunk -- only then
+    does the step need its long-run launch)."""
 
     def __init__(self, inputs, sorted_ids, perm, event, plan=None, hint=None, target=None):
         self.inputs, self.sorted_ids, self.perm, self.event = inputs, sorted_ids, perm, event
         self.plan, self.hint, self.target = plan, hint, target
-        self._done = event
 
     def take(self, host_wait_s=0.0):
         """(sorted_ids, perm) for the current stream (waits for the side stream's event, once).  host_wait_s > 0 (the
@@ -179,9 +180,7 @@ class PresortedInputs:
 
     def long_runs(self):
         """0 / 1 from the plan's hint once it has reached the host, -1 while it has not (or without a plan)."""
-        if self.hint is None or self._done is None or not self._done.query():
-            return -1
-        return hint_value(self.hint)
+        return hint_long_runs(self.hint)
 
 
 # ESR_GLOVE_PRESORT=0 sorts in line instead of one batch ahead on the side stream.  ESR_GLOVE_STEP_BLOCKS_PER_CU caps the
@@ -195,7 +194,6 @@ _HINT_WAIT = os.environ.get("ESR_GLOVE_HINT_WAIT", "1") == "1"
 _HOST_WAIT_S = float(os.environ.get("ESR_GLOVE_HOST_WAIT_US", "0")) * 1e-6
 
 
-_hint_ring = {}  # device -> [pinned int32 [R], next slot, next gen]
 _start_words = {}  # device -> [int32 [1] device word, sequence number of the latest step that announces itself there]
 
 
@@ -208,35 +206,6 @@ def _start_word(dev):
         _start_words[key] = [torch.zeros(1, dtype=torch.int32, device=dev), 0]
     return _start_words[key]
 _RESOLVE_MIN_IDS = 32768  # esr_glove.hip kResolveMinIds: longer lists resolve their records per step, plans are unused
-
-
-def _hint_slot(dev):
-    """One word of a small ring of PINNED host memory for a long-run hint: (view [1], gen).  The kernels write the word
-    themselves (pinned memory is mapped into the device's address space): no copy launch."""
-    R = 16
-    key = (dev.type, dev.index)
-    if key not in _hint_ring:
-        _hint_ring[key] = [torch.zeros(R, dtype=torch.int32).pin_memory(), 0, 1]
-    ring = _hint_ring[key]
-    i, gen = ring[1], ring[2]
-    ring[1], ring[2] = (i + 1) % R, gen + 1 if gen < 2 ** 31 - 2 else 1
-    word = ring[0][i:i + 1]
-    _hint_owner[word.data_ptr()] = gen  # the slot is this generation's until the ring comes round to it again
-    return word, gen
-
-
-_hint_owner = {}  # address of a ring word -> the generation it was last handed to
-
-
-def hint_value(hint):
-    """1 / 0 = the hint kernel of `hint` = (word, gen, ...) found / did not find a long run -- valid only while the word
-    is still this generation's.  A kernel writes its gen into the word only when it finds a long run, so a word that a
-    LATER hint has been handed (more than a ring's worth of handles outstanding) would read as "no long run" whatever
-    this generation's kernel had found: that case answers -1 (unknown: the step makes its long-run launch)."""
-    word, gen = hint[0], hint[1]
-    if _hint_owner.get(word.data_ptr()) != gen:
-        return -1
-    return 1 if int(word[0]) == gen else 0
 
 
 def presort_inputs(state, inputs, target=None, after=None, out=None):
@@ -258,6 +227,7 @@ def presort_inputs(state, inputs, target=None, after=None, out=None):
     elif not isinstance(after, tuple):
         side.wait_event(after)  # an event of the main stream behind which the ids are ready
     plan = hint = None
+    event = torch.cuda.Event()
     with torch.cuda.stream(side):
         if isinstance(after, tuple):
             # (flag, value): the start word of a step NOT YET ISSUED when the ids were drawn (train_epoch) -- whatever
@@ -271,8 +241,7 @@ def presort_inputs(state, inputs, target=None, after=None, out=None):
             if ids.numel() <= _RESOLVE_MIN_IDS:
                 hh, gen = _hint_slot(emb.device)
                 plan = ops.glove_plan([ids], [tgt], sorted_ids, perm, hints=hh, gen=gen)
-                hint = (hh, gen)
-        event = torch.cuda.Event()
+                hint = (hh, gen, event)
         event.record(side)
     ids.record_stream(side)
     if out is None:
@@ -334,17 +303,6 @@ def _ids_count(inputs):
     return int(np.prod(x.shape)) if hasattr(x, "shape") else 2 * len(x[0])
 
 
-class _Group:
-    """A group of batches whose id lists were sorted and planned together (``_FusedEpoch.sort_batch``): the raw pointers
-    of everything esr_glove_train_steps takes, and the tensors, kept alive."""
-    __slots__ = ("nb", "B", "in_ptrs", "tgt_ptrs", "sorted_ptr", "perm_ptr", "plans_ptr", "which", "gen", "keep")
-
-    def __init__(self, nb, B, in_ptrs, tgt_ptrs, sorted_ptr, perm_ptr, plans_ptr, which, gen, keep):
-        self.nb, self.B, self.in_ptrs, self.tgt_ptrs = nb, B, in_ptrs, tgt_ptrs
-        self.sorted_ptr, self.perm_ptr, self.plans_ptr = sorted_ptr, perm_ptr, plans_ptr
-        self.which, self.gen, self.keep = which, gen, keep
-
-
 class _FusedEpoch:
     """What the one-pass step needs that does not change from batch to batch, resolved once per epoch: table / accumulator
     / RowVersions pointers, the library entry point, one loss slot per step and a reusable workspace.  At the reference's
@@ -373,18 +331,10 @@ class _FusedEpoch:
         self.steps_issued = 0
         self.uses_gate = False  # a side-stream sort waits on the start word: every issued step must advance it
         self.ws, self.ws_B = None, -1
-        self.sort_buf = [None, None]  # two sets: a group is sorted and planned while the one before it is stepped
-        self.long_buf = [None, None]  # the same for lists too long for plans (_sort_batch_long)
+        # groups of short lists: sorted and planned (esr_glove_plan) while the group before is stepped
+        self.planner, self.plan_fn = GroupPlanner(self.dev, _SORT_BATCH, _HINT_WAIT, 1, targets=True), self.lib.esr_glove_plan
         self.which = 0
         import ctypes
-        self.sort_ptrs = [(ctypes.c_void_p * _SORT_BATCH)(), (ctypes.c_void_p * _SORT_BATCH)()]
-        self.tgt_ptrs = [(ctypes.c_void_p * _SORT_BATCH)(), (ctypes.c_void_p * _SORT_BATCH)()]
-        self.long_arr = (ctypes.c_int32 * _SORT_BATCH)()
-        # esr_glove_plan's long-run hints, copied to pinned memory behind the plan launch (see _FusedTripletLoop)
-        self.hints_host = torch.zeros((2, _SORT_BATCH), dtype=torch.int32).pin_memory()  # written by the plan kernel
-        self.hints_event = [torch.cuda.Event(), torch.cuda.Event()]
-        self.hints_known = [None, None]
-        self.gen = 0
         self.sort_cnt, self.sort_off = (ctypes.c_int64 * 1)(0), (ctypes.c_int64 * 1)(0)
         self.start = _start_word(self.dev)  # [int32 [1] device word, sequence number of the latest step issued]
         self.check_ids = os.environ.get("ESR_CHECK_IDS") == "1"
@@ -393,7 +343,7 @@ class _FusedEpoch:
                       self.D)
 
     def sort_batch(self, group):
-        """[(inputs, target), ...] of the coming batches -> a _Group: their id lists sorted by one batched call and their
+        """[(inputs, target), ...] of the coming batches -> a Group: their id lists sorted by one batched call and their
         plan records made by one more on the current stream, everything ``step_group`` hands the library resolved here
         (batches of unequal size or longer than the two-launch sort takes: the list as it is, every step on its own)."""
         ids = [ops.as_ids(inp, self.dev, check_range=self.V) for inp, _ in group]
@@ -408,16 +358,13 @@ class _FusedEpoch:
         self.which ^= 1
         which = self.which
         B = n // 2
+        sort_ptrs = self.planner.ptrs[which]
+        for b, i in enumerate(ids):
+            sort_ptrs[b] = i.data_ptr()
+        self.sort_cnt[0] = n
+        lists = (self.sort_cnt, self.sort_off, self.V)
         if n > _RESOLVE_MIN_IDS:
-            return self._sort_batch_long(ids, group, n, which)
-        pbytes = ops._ws_bytes("esr_glove_plan_bytes", B)
-        if self.sort_buf[which] is None or self.sort_buf[which][0].shape[1] != n:
-            self.sort_buf[which] = (torch.empty((_SORT_BATCH, n), dtype=torch.int32, device=self.dev),
-                                    torch.empty((_SORT_BATCH, n), dtype=torch.int32, device=self.dev),
-                                    ops._ws(ops._ws_bytes("esr_segment_sort_batched_workspace_bytes", n, _SORT_BATCH),
-                                            self.dev),
-                                    ops._aligned_bytes(_SORT_BATCH * pbytes, self.dev))
-        srt, prm, ws, plans = self.sort_buf[which]
+            return self._sort_batch_long(ids, group, n, which, lists)
         tgts = []
         for _, t in group:
             if not (type(t) is torch.Tensor and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
@@ -425,28 +372,15 @@ class _FusedEpoch:
             if t.numel() * 2 != n:
                 raise ValueError("inputs must be [2, B] and target [B]")
             tgts.append(t)
-        # (the library calls themselves: ops.segment_sort_batched re-validates every tensor and rebuilds its ctypes arrays)
-        sort_ptrs, tgt_ptrs = self.sort_ptrs[which], self.tgt_ptrs[which]
-        for b, (i, t) in enumerate(zip(ids, tgts)):
-            sort_ptrs[b] = i.data_ptr()
+        tgt_ptrs = self.planner.tgt_ptrs[which]
+        for b, t in enumerate(tgts):
             tgt_ptrs[b] = t.data_ptr()
-        self.sort_cnt[0] = n
-        st = ops._stream()
-        self.check(self.lib.esr_segment_sort_ids_batched(sort_ptrs, self.sort_cnt, self.sort_off, 1, nb, self.V,
-                                                         srt.data_ptr(), prm.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                         st), "esr_segment_sort_ids_batched")
-        self.gen += 1
-        self.check(self.lib.esr_glove_plan(sort_ptrs, tgt_ptrs, nb, B, srt.data_ptr(), prm.data_ptr(),
-                                           plans.data_ptr(), self.hints_host[which].data_ptr(), self.gen, st),
-                   "esr_glove_plan")
-        self.hints_event[which].record()
-        self.hints_known[which] = None
         # the whole group is stepped by ONE library call (esr_glove_train_steps): at 2048 pairs a step is ~20 us of
         # kernels, less than a 25-argument foreign call plus the Python around it
-        return _Group(nb, B, self.sort_ptrs[which], self.tgt_ptrs[which], srt.data_ptr(), prm.data_ptr(),
-                      plans.data_ptr(), which, self.gen, (ids, tgts))
+        bufs = self.planner.buffers(which, n, ops._ws_bytes("esr_glove_plan_bytes", B))
+        return self.planner.plan(which, nb, B, bufs, lists, (self.plan_fn, (sort_ptrs, tgt_ptrs, nb, B)), (ids, tgts))
 
-    def _sort_batch_long(self, ids, group, n, which):
+    def _sort_batch_long(self, ids, group, n, which, lists):
         """Lists of more than _RESOLVE_MIN_IDS ids (the steps resolve their own records: no plans): the lists of the group
         sorted by ONE batched call on the current stream, each step then issued on its own with its slice.  The sort of
         one such list is four launches of 64 workgroups -- latency, not work -- so eight lists cost little more than one,
@@ -454,52 +388,18 @@ class _FusedEpoch:
         shares the chip with the update kernel: at C3 it stretched to the length of a step and held the loop to its own
         pace, 0.143 ms)."""
         nb = len(ids)
-        if self.long_buf[which] is None or self.long_buf[which][0].shape[1] != n:
-            self.long_buf[which] = (torch.empty((_SORT_BATCH, n), dtype=torch.int32, device=self.dev),
-                                    torch.empty((_SORT_BATCH, n), dtype=torch.int32, device=self.dev),
-                                    ops._ws(ops._ws_bytes("esr_segment_sort_batched_workspace_bytes", n, _SORT_BATCH),
-                                            self.dev))
-        srt, prm, ws = self.long_buf[which]
-        sort_ptrs = self.sort_ptrs[which]
-        for b, i in enumerate(ids):
-            sort_ptrs[b] = i.data_ptr()
-        self.sort_cnt[0] = n
-        self.check(self.lib.esr_segment_sort_ids_batched(sort_ptrs, self.sort_cnt, self.sort_off, 1, nb, self.V,
-                                                         srt.data_ptr(), prm.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                         ops._stream()), "esr_segment_sort_ids_batched")
-        # one screening launch for the group (the [nb, n] array as one list: a run across two lists can only make the
-        # answer "long"): on a cleared hint the steps skip their long-run launch (5 us of 134 at C3)
-        hh, gen = _hint_slot(self.dev)
-        ops.long_run_hint(srt[:nb].reshape(-1), 32, hh, gen)
-        ev = torch.cuda.Event()
-        ev.record()
-        out = []
-        for b, (i, (_, t)) in enumerate(zip(ids, group)):
-            pre = PresortedInputs(i, srt[b], prm[b], None, hint=(hh, gen))
-            pre._done = ev
-            out.append((pre, t))
-        return out
+        bufs = srt, prm, _, _ = self.planner.buffers(which, n)
+        self.planner.sort(which, nb, bufs, lists, ops._stream())
+        hint = screen_group(srt[:nb], self.dev)  # (a skipped long-run launch: 5 us of 134 at C3)
+        return [(PresortedInputs(i, srt[b], prm[b], None, hint=hint), t) for b, (i, (_, t)) in enumerate(zip(ids, group))]
 
     def step_group(self, k, gr):
         """Steps k .. k + gr.nb - 1: the batches of a sorted and planned group, issued by one library call."""
-        known = self.hints_known[gr.which]
-        if known is None:
-            # the HOST waits for the group's plan launch (queued in front of the steps of the group before it: the wait
-            # ends with a group's worth of work still queued), so that every step knows whether it needs its long-run
-            # launch -- see pinterest.train_shop_the_look._FusedTripletLoop.step_group
-            if _HINT_WAIT:
-                self.hints_event[gr.which].synchronize()
-            if self.hints_event[gr.which].query():
-                known = self.hints_known[gr.which] = self.hints_host[gr.which].tolist()
-        long_runs = None
-        if known is not None:  # (else: the hint has not reached the host; the library makes every long-run launch)
-            long_runs = self.long_arr
-            for j in range(gr.nb):
-                long_runs[j] = 1 if known[j] == gr.gen else 0
+        long_runs = self.planner.long_runs(gr)  # (None: the library makes every long-run launch)
         if gr.B != self.ws_B:
             self.ws = ops._ws(ops._ws_bytes("esr_glove_step_workspace_bytes", gr.B, self.D), self.dev)
             self.ws_B = gr.B
-        self.check(self.lib.esr_glove_train_steps(*self.fixed, gr.nb, gr.in_ptrs, gr.tgt_ptrs, gr.B, self.mode, self.lr,
+        self.check(self.lib.esr_glove_train_steps(*self.fixed, gr.nb, gr.ptrs, gr.tgt_ptrs, gr.B, self.mode, self.lr,
                                                   self.eps, self.next_stamp(self.rv, count=gr.nb), gr.sorted_ptr,
                                                   gr.perm_ptr, gr.plans_ptr, long_runs, self.losses_ptr + 4 * k,
                                                   self.ws.data_ptr(), self.ws.numel(), ops._stream()),
@@ -526,11 +426,10 @@ class _FusedEpoch:
     def step(self, k, inputs, target):
         presorted, plan_ptr, long_runs = None, 0, -1
         if isinstance(inputs, PresortedInputs):
-            if _HINT_WAIT and inputs.hint is not None and inputs.event is None and inputs._done is not None and \
-                    not inputs._done.query():
+            if _HINT_WAIT and inputs.hint is not None and inputs.event is None and not inputs.hint[2].query():
                 # (a group-sorted list: its screening launch was queued in front of the previous group's steps -- see
-                # step_group; the wait ends with that group's work still queued)
-                inputs._done.synchronize()
+                # loop_plan.GroupPlanner; the wait ends with that group's work still queued)
+                inputs.hint[2].synchronize()
             long_runs = inputs.long_runs()
             if inputs.plan is not None:
                 plan_ptr = inputs.plan.data_ptr()
@@ -602,7 +501,7 @@ def _train_epoch(state, steps_per_epoch, train_it, losses_out=None):
         # (esr_segment_sort_ids_batched) in front of their steps.
         from collections import deque
         import time
-        queue, fetched, queued = deque(), 0, 0  # queue items: (inputs, targets) of one step, or a _Group; queued = steps
+        queue, fetched, queued = deque(), 0, 0  # queue items: (inputs, targets) of one step, or a Group; queued = steps
         t_host = time.perf_counter()
         grouped = False  # short lists: a whole group is drawn, sorted and planned at a time
         k, dry = 0, False
@@ -633,7 +532,7 @@ def _train_epoch(state, steps_per_epoch, train_it, losses_out=None):
                             break
                         fetched += 1
                     made = ctx.sort_batch(group) if len(group) > 1 else group
-                    if type(made) is _Group:
+                    if type(made) is Group:
                         queue.append(made)
                     else:
                         queue.extend(made)
@@ -648,7 +547,7 @@ def _train_epoch(state, steps_per_epoch, train_it, losses_out=None):
             if not queue:
                 raise StopIteration("train_epoch: the batch iterator ended after %d of %d steps" % (k, steps_per_epoch))
             item = queue.popleft()
-            if type(item) is _Group:
+            if type(item) is Group:
                 ctx.step_group(k, item)
                 k += item.nb
                 queued -= item.nb

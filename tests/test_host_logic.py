@@ -145,7 +145,7 @@ def test_long_run_hint_words_are_unknown_once_their_slot_is_reused():
     """the long-run hint words live in a 16-slot ring and a kernel writes its generation only when it FINDS a
     long run.  A handle whose slot a later hint has been handed must answer "unknown" (-1), never "no long run" (0)."""
     import torch
-    from esrecsys_amd.wikipedia import train_cooccurence as tc
+    from esrecsys_amd import loop_plan as tc
     dev = torch.device("cpu")
     key = (dev.type, dev.index)
     tc._hint_ring[key] = [torch.zeros(16, dtype=torch.int32), 0, 1]  # (the product ring is pinned host memory)
@@ -164,3 +164,55 @@ def test_long_run_hint_words_are_unknown_once_their_slot_is_reused():
         assert tc.hint_value(again) == 1 and tc.hint_value(first) == -1
     finally:
         tc._hint_ring.pop(key, None)
+
+
+def test_group_planner_answers_long_runs_from_its_hint_words(monkeypatch):
+    """loop_plan.GroupPlanner.long_runs with stand-in events and a stand-in library (the plan kernel's part -- storing the
+    call's generation into the word of a list with a long run -- is played by the test): unknown until the set's event
+    is complete; then 1 for a word equal to the group's generation and 0 for any other word, a newer generation's
+    included; planning the set again forgets what was known of it."""
+    import types
+    import torch
+    from esrecsys_amd import loop_plan
+
+    class Event:
+        done = False
+
+        def record(self, stream=None):
+            self.done = False
+
+        def query(self):
+            return self.done
+
+        def synchronize(self):
+            self.waited = True
+
+    monkeypatch.setattr(torch.cuda, "Event", Event)
+    monkeypatch.setattr(torch.Tensor, "pin_memory", lambda t: t)
+    monkeypatch.setattr(loop_plan.ops, "_stream", lambda: 0)
+    planner = loop_plan.GroupPlanner(torch.device("cpu"), 8, False, 3)
+    planner.lib = types.SimpleNamespace(esr_segment_sort_ids_batched=lambda *a: 0)
+    planner.check = lambda code, name: None
+
+    def plan(which, nb):
+        return planner.plan(which, nb, 4, planner.buffers(which, 12, 64), (None, None, 100), (lambda *a: 0, ()), None)
+
+    first = plan(1, 3)
+    assert first.gen == 1 and first.nb == 3 and first.long is None
+    planner.words[1, 1] = first.gen                     # list 1 of the group has a long run
+    assert planner.long_runs(first) is None and first.long is None and planner.known[1] is None   # event not complete
+    assert not hasattr(planner.events[1], "waited")     # hint_wait off: the host does not block
+    planner.events[1].done = True
+    assert list(planner.long_runs(first))[:3] == [0, 1, 0] and list(first.long)[:3] == [0, 1, 0]
+    other = plan(0, 2)                                  # the other set: nothing known of it, set 1 untouched
+    assert other.gen == 2 and planner.known[0] is None and planner.known[1] is not None
+    second = plan(1, 3)                                 # set 1 again: forgotten, and its event is open again
+    assert second.gen == 3 and planner.known[1] is None and planner.long_runs(second) is None
+    planner.words[1, 2] = second.gen
+    planner.events[1].done = True
+    assert list(planner.long_runs(second))[:3] == [0, 0, 1]    # word 1 still holds generation 1: not this group's
+    assert list(planner.long_runs(first))[:3] == [0, 1, 0]     # an old handle: word 2 holds a NEWER generation -> 0
+    planner.hint_wait = True
+    third = plan(1, 1)
+    planner.events[1].done = True                       # (a real wait returns with the event complete)
+    assert list(planner.long_runs(third))[:1] == [0] and planner.events[1].waited
