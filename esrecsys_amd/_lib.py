@@ -283,6 +283,11 @@ SIGNATURES = {
     "esr_fpmc_fwd_bwd": (c_int, [c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_i32p, c_i64, c_i32p, c_i32p, c_i32p,
                                  c_i32p, c_i32p, c_i32p, c_i64, c_vp, c_i64, c_f32, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p,
                                  c_vp]),
+    "esr_sgns_geometry": (c_int, [ctypes.POINTER(c_int)] * 4),
+    "esr_sgns_sample": (c_int, [c_vp, c_i32p, c_i32p, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_i32p, c_uint64, c_uint32,
+                                c_i64, c_i64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_vp]),
+    "esr_sgns_fwd_bwd": (c_int, [c_f32p, c_f32p, c_i64, c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i64, c_int, c_f32, c_f32p,
+                                 c_f32p, c_f32p, c_i32p, c_vp]),
     "esr_rerank_geometry": (c_int, [c_int, c_int] + [ctypes.POINTER(c_int)] * 8),
     "esr_rerank_mmr": (c_int, [c_f32p, c_i64, c_int, c_i32p, c_f32p, c_i32p, c_i64, c_int, c_int, c_f32, c_i32p, c_i32p, c_f32p,
                                c_f32p, c_i32p, c_i32p, c_vp]),

@@ -14,12 +14,14 @@ LIB_PATH = os.path.join(HERE, "libesr_hip.so")
 SOURCES = ["esr_core.hip", "esr_glove.hip", "esr_triplet.hip", "esr_inbatch.hip", "esr_inbatch3.hip", "esr_inbatch2h.hip", "esr_optim.hip", "esr_sort.hip",
            "esr_retrieve.hip", "esr_spotify.hip", "esr_comm.hip", "esr_triplet_step.hip", "esr_shard.hip", "esr_shard_step.hip", "esr_ivf.hip",
            "esr_adam.hip", "esr_spotify_eval.hip", "esr_cooccur.hip", "esr_dice.hip", "esr_terms.hip", "esr_neighbours.hip", "esr_eval.hip",
-           "esr_ratings.hip", "esr_als.hip", "esr_bpr.hip", "esr_warp.hip", "esr_bag.hip", "esr_rerank.hip", "esr_fpmc.hip"]
+           "esr_ratings.hip", "esr_als.hip", "esr_bpr.hip", "esr_warp.hip", "esr_bag.hip", "esr_rerank.hip", "esr_fpmc.hip",
+           "esr_sgns.hip"]
 HEADERS = [os.path.join(HERE, "..", "include", "esr_probe.h"), os.path.join(CSRC, "esr_common.h"), os.path.join(CSRC, "esr_versioned.h"), os.path.join(CSRC, "esr_inbatch_mfma.h"),
            os.path.join(HERE, "..", "include", "esr_hip.h"), os.path.join(CSRC, "esr_adam.h"), os.path.join(CSRC, "esr_segment.h"), os.path.join(CSRC, "esr_cooccur_table.h"),
            os.path.join(CSRC, "esr_philox.h"), os.path.join(CSRC, "esr_rank_keys.h"), os.path.join(CSRC, "esr_wide_table.h"),
            os.path.join(CSRC, "esr_bpr_sample.h"), os.path.join(CSRC, "esr_warp_sample.h"), os.path.join(CSRC, "esr_bag_rule.h"), os.path.join(CSRC, "esr_row4.h"),
-           os.path.join(CSRC, "esr_rerank_rule.h"), os.path.join(CSRC, "esr_fpmc_sample.h")]
+           os.path.join(CSRC, "esr_rerank_rule.h"), os.path.join(CSRC, "esr_fpmc_sample.h"),
+           os.path.join(CSRC, "esr_sgns_sample.h")]
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -33,9 +33,10 @@ by the row-sparse engine; ``WARP`` (last) is BPR's model trained with the rank-w
 for on the device by one fused call (esr_warp.hip).  ``HybridBPR`` is BPR over users and items that are weighted sums of
 feature embeddings (esr_bag.hip): side information and cold start.  ``FPMC`` (at the end) is the sequential member: BPR's
 user-item term plus a factorised transition term from the items just consumed (esr_fpmc.hip), which also serves sessions of
-users the model never saw.
+users the model never saw.  ``SGNS`` (the last class) has no users at all: skip-gram with negative sampling over id sequences
+(esr_sgns.hip) -- word2vec, item2vec.
 
-All six derive from ``_Factorization`` (device, indexed pairs, ``score`` / ``recommend`` / ``from_documents`` and
+All of them derive from ``_Factorization`` (device, indexed pairs, ``score`` / ``recommend`` / ``from_documents`` and
 ``diversify``, the MMR re-ranking of ``rerank.py`` applied to ``recommend``'s lists); ``_ALS`` holds
 what the two alternating models share, ``BPR`` the step tail and the update of the three triple models.
 """
@@ -1374,3 +1375,266 @@ class FPMC(BPR):
             return _recommend_rows(torch.cat([half, m], 1).contiguous(), None, torch.arange(ndocs, dtype=torch.int64, device=dev),
                                    item_rows, self.items, k, slack, seen_offsets, key, lambda q: "sequence %d" % q, "holds",
                                    "exclude_seen")
+
+
+# ---- skip-gram with negative sampling ------------------------------------------------------------------------------------
+NOISE_COLUMN = 1 << 32       # the mass of one column of the alias table: a 32-bit Philox word
+
+
+def sgns_noise_masses(counts, power=0.75):
+    """int64[ni] on the host: ``count ** power`` quantised to integer masses that sum to ``ni * 2^32`` exactly.  An item
+    that occurs gets a mass of at least 1, one that never occurs mass 0.  The float64 targets are floored; what the
+    floors (and the lifts to 1) leave over is spread over the occurring items in descending mass, one unit at a time."""
+    counts = np.asarray(counts)
+    if counts.ndim != 1 or counts.size < 1 or counts.dtype.kind not in "iu" or bool((counts < 0).any()):
+        raise ValueError("counts must be a non-empty array of non-negative integers")
+    power = float(power)
+    if not (math.isfinite(power) and power >= 0.0):
+        raise ValueError("power = %r must be finite and not negative" % (power,))
+    ni = counts.size
+    occurs = counts > 0
+    n_occ = int(occurs.sum())
+    if n_occ == 0:
+        raise ValueError("no item occurs: the noise distribution is empty")
+    total = ni * NOISE_COLUMN
+    f = np.where(occurs, np.maximum(counts, 1).astype(np.float64) ** power, 0.0)
+    masses = np.where(occurs, np.maximum(np.floor(f / f.sum() * total), 1.0), 0.0).astype(np.int64)
+    rest = total - int(masses.sum())
+    order = np.argsort(-masses, kind="stable")[:n_occ]                # descending mass, ascending id
+    if rest > 0:
+        q, r = divmod(rest, n_occ)
+        masses[order] += q
+        masses[order[:r]] += 1
+    elif rest < 0:
+        spare = masses[order] - 1
+        before = np.cumsum(spare) - spare
+        masses[order] -= np.minimum(spare, np.maximum(-rest - before, 0))
+    assert int(masses.sum()) == total and bool((masses[occurs] >= 1).all())
+    return masses
+
+
+def sgns_alias_table(masses):
+    """(noise_keep uint32[ni], noise_alias int32[ni]) on the host: Walker / Vose alias columns of the integer `masses`
+    (which sum to ``ni * 2^32``), built in integer arithmetic only, so the table represents the masses exactly:
+
+        masses[i] = keep'[i] + sum over n != i with alias[n] == i of (2^32 - keep[n]),  keep' = 2^32 for a full column.
+
+    Column n yields item n for a 32-bit word below ``keep[n]`` and ``alias[n]`` otherwise; a full column is stored as
+    ``alias[n] == n`` (keep = 2^32 - 1).  An item of mass 0 gets keep 0 and is nobody's alias: it is never drawn.  The
+    pairing is a Python loop over the ni columns -- a one-off per model: 0.11 s at ni = 200 000 with Zipf counts, measured
+    on the CPU (``sgns_noise_masses`` before it: 0.27 s)."""
+    rem = [int(v) for v in np.asarray(masses).reshape(-1)]
+    ni = len(rem)
+    if ni < 1 or min(rem) < 0 or sum(rem) != ni * NOISE_COLUMN:
+        raise ValueError("masses must be non-negative and sum to ni * 2^32")
+    keep, alias = [NOISE_COLUMN - 1] * ni, list(range(ni))
+    small = [i for i in range(ni - 1, -1, -1) if rem[i] < NOISE_COLUMN]   # popped in ascending id
+    large = [i for i in range(ni - 1, -1, -1) if rem[i] > NOISE_COLUMN]
+    while small and large:
+        s, l = small.pop(), large.pop()
+        keep[s], alias[s] = rem[s], l
+        rem[l] -= NOISE_COLUMN - rem[s]
+        if rem[l] < NOISE_COLUMN:
+            small.append(l)
+        elif rem[l] > NOISE_COLUMN:
+            large.append(l)
+    assert not small and not large                                      # the masses sum to ni columns: none is left open
+    return np.array(keep, np.uint32), np.array(alias, np.int32)
+
+
+class SGNS(BPR):
+    """Skip-gram with negative sampling (Mikolov, Sutskever, Chen, Corrado, Dean, NIPS 2013): word2vec for token streams,
+    item2vec / prod2vec (Barkan and Koenigstein 2016; Grbovic et al. 2015) for playlists, baskets and sessions -- item
+    vectors trained straight from id sequences, without users and without a co-occurrence matrix.
+
+        model = SGNS.from_documents(indices, doc_offsets, window=5, negatives=5, rank=64)    # a document is a sequence
+        losses = model.fit(steps=2000)
+        ids, scores, lengths = model.similar_items(items, k=20)                     # cosine neighbours of the in rows
+        rec_ids, rec_scores, rec_lengths = model.recommend_sequences(ids, offsets, k=10)     # next items of sessions
+
+    Model.  Two tables of one rank: ``in_factors`` [ni, rank] (the centre vectors v) and ``out_factors`` [ni, rank] (the
+    context vectors w).  An event is a place of a document -- the events in the order given, or by a stable sort on
+    (doc, time) with `time`; repeats are kept.
+
+    Step.  ``batch`` slots are drawn on the device (``ops.sgns_sample``: BPR's Philox counter layout): an event, its item
+    the centre c; a distance d in [1, window] with weight ``window - d + 1`` (word2vec's shrunk window) on a random side,
+    the item there the context o -- a slot whose context would leave the document is dropped (``valid = 0``); and
+    ``negatives`` noise items from the alias table of ``counts ** power`` (``noise_keep`` / ``noise_alias``, built once
+    on the host by ``sgns_alias_table``).  The objective of a step is the sum over its valid slots of
+    ``softplus(-v_c . w_o) + sum_k m_k softplus(v_c . w_n_k) + (reg / 2)(|v_c|^2 + |w_o|^2 + sum_k m_k |w_n_k|^2)``,
+    ``m_k = 0`` where the noise item is the context itself (word2vec skips that draw).  ``ops.sgns_fwd_bwd`` writes one
+    gradient row per occurrence and the row-sparse engine updates both tables (``BPR._apply``).  The reported loss is the
+    logistic part, as in the other models of this module.  The fit is a function of the inputs and the seed.
+    Frequent-item subsampling (Mikolov's threshold t) is out of scope: every event is a centre with equal probability.
+
+    ``items``: int32 ascending ids; ``counts``: int64[ni], the items' occurrence counts; the tables are ``randn *
+    init_scale`` from the seeded CPU generator in the order in, out, their Adagrad accumulators ``in_accum`` /
+    ``out_accum``; ``noise_keep`` holds the uint32 thresholds as int32 bits on the device; ``step``: the steps taken.
+    There is no user table: ``score``, ``recommend`` and ``auc`` are refused; ``accuracy`` is the counterpart of ``auc``."""
+
+    def __init__(self, doc, item, time=None, window=5, negatives=5, power=0.75, rank=64, reg=0.0, lr=0.05,
+                 optimizer="adagrad", batch=65536, seed=0, init_scale=None, device=None):
+        top_window, top_negatives, _, _ = ops.sgns_geometry()
+        window, negatives, power = int(window), int(negatives), float(power)
+        if not 1 <= window <= top_window:
+            raise ValueError("window = %d outside [1, %d]" % (window, top_window))
+        if not 1 <= negatives <= top_negatives:
+            raise ValueError("negatives = %d outside [1, %d]" % (negatives, top_negatives))
+        if not (math.isfinite(power) and power >= 0.0):
+            raise ValueError("power = %r must be finite and not negative" % (power,))
+        if time is not None:
+            time = _tensor(time, "time")
+            _same_length("doc, item and time", _tensor(doc, "doc"), _tensor(item, "item"), time)
+        if (2 + negatives) * int(batch) > 2 ** 31 - 1:
+            raise ValueError("(2 + negatives) * batch = %d gradient rows exceed 2^31 - 1" % ((2 + negatives) * int(batch)))
+        doc, item = self._configure(doc, item, rank, reg, lr, optimizer, batch, seed, init_scale, device)
+        self.window, self.negatives, self.power = window, negatives, power
+        dev = self.device
+        with torch.cuda.device(dev):
+            _, upos, ipos = self._index_pairs(doc, item)
+            nd, ni = int(self.users.numel()), int(self.items.numel())
+            if 2 * ni > 2 ** 31 - 1:
+                raise ValueError("2 ni = %d rows exceed 2^31 - 1 (the row space of the update)" % (2 * ni))
+            if upos.numel() > 2 ** 31 - 1:
+                raise ValueError("%d events exceed 2^31 - 1" % upos.numel())
+            # the documents: a CSR in the order given or by (time, order given), as FPMC's sequences
+            order = torch.arange(upos.numel(), device=dev) if time is None else torch.sort(time.to(dev), stable=True).indices
+            order = order[torch.sort(upos[order], stable=True).indices]
+            self._seq_offsets = _host_offsets(torch.bincount(upos, minlength=nd))
+            self._seq_offsets_dev = torch.from_numpy(self._seq_offsets).to(dev)
+            self._seq_upos = upos[order].to(torch.int32).contiguous()
+            self._seq_ipos = ipos[order].to(torch.int32).contiguous()
+            self.counts = torch.bincount(ipos, minlength=ni)
+            keep, alias = sgns_alias_table(sgns_noise_masses(self.counts.cpu().numpy(), power))
+            self.noise_keep = torch.from_numpy(keep.view(np.int32)).to(dev)
+            self.noise_alias = torch.from_numpy(alias).to(dev)
+            self._failed = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.in_factors, self.out_factors, self.in_accum, self.out_accum = self._new_tables(ni, ni)
+
+    n_events = property(lambda self: int(self._seq_ipos.numel()))
+    nnz = n_events
+
+    def _rows(self):
+        return self.in_factors, self.out_factors
+
+    def _no_users(self, *a, **kw):
+        raise TypeError("SGNS has no user table: use similar_items, recommend_sequences and accuracy")
+
+    score = recommend = auc = _no_users
+
+    # ---- training -------------------------------------------------------------------------------------------------------
+    def sample(self, K, step0=None, seed=None):
+        """(c, e, o, valid) int32 [K, batch], neg int32 [K, batch, negatives] and dropped int32[K]: the slots of the global
+        steps step0 .. step0 + K - 1 (``step0`` = the next step to take when None) -- c, o and neg positions into
+        ``items``, e the centre's event number in the document CSR."""
+        with torch.cuda.device(self.device):
+            return ops.sgns_sample(self._seq_offsets_dev, self._seq_upos, self._seq_ipos, self.users.numel(),
+                                   self.items.numel(), self.window, self.negatives, self.noise_keep, self.noise_alias,
+                                   self.seed if seed is None else int(seed), self.step if step0 is None else int(step0),
+                                   int(K), self.batch)
+
+    def train_steps(self, K):
+        """K steps: one sampler launch, then per step the forward / backward, the sort and the update over both tables.
+        Returns the mean loss over the valid slots of every step (an fp64 sum of the per-slot losses divided on the host;
+        NaN for a step without a valid slot).  Raises ``FactorizationError`` when a kernel met a position outside its
+        table."""
+        K = self._check_K(K)
+        ni = int(self.items.numel())
+        with torch.cuda.device(self.device):
+            c, _, o, valid, neg, dropped = self.sample(K)
+            # the id list of the gradient rows after the centres: [o ; neg[:, 0] ; .. ; neg[:, negatives - 1]] per step
+            context = torch.cat([o[:, None, :], neg.permute(0, 2, 1)], 1).contiguous()
+
+            def one_step(k):
+                loss_t, _, grads = ops.sgns_fwd_bwd(self.in_factors, self.out_factors, c[k], o[k], neg[k], valid[k], self.reg,
+                                                    failed=self._failed)
+                self._apply([self.in_factors, self.out_factors], [self.in_accum, self.out_accum],
+                            [c[k], context[k].reshape(-1)], [0, ni, 2 * ni], grads)
+                return (loss_t.to(torch.float64).sum(),)
+            sums = self._run_steps(K, "an SGNS step met a position outside its table (bit 30)", one_step)
+            return _step_means(sums[0], self.batch - dropped.cpu().numpy().astype(np.int64))
+
+    def accuracy(self, K=1, seed=None):
+        """The share of (context, noise) score pairs that the model orders correctly, ``s_o > s_k``, over K * batch
+        sampled slots (valid ones; a noise item that is the context itself is no pair); a tie counts half -- ``BPR.auc``'s
+        convention.  The slots are steps 0 .. K - 1 of `seed` (``self.seed + 1`` when None: not a training stream, and the
+        same slots before and after training).  NaN when there is no pair."""
+        with torch.cuda.device(self.device):
+            c, _, o, valid, neg, _ = self.sample(int(K), step0=0, seed=self.seed + 1 if seed is None else seed)
+            c, o, valid, neg = c.reshape(-1), o.reshape(-1), valid.reshape(-1), neg.reshape(-1, self.negatives)
+            self._failed.zero_()
+            _, s, _ = ops.sgns_fwd_bwd(self.in_factors, self.out_factors, c, o, neg, valid, self.reg, want_grads=False,
+                                       want_diff=True, failed=self._failed)
+            self._raise_bad_position("accuracy met a position outside its table (bit 30)")
+            pair = (valid != 0)[:, None] & (neg != o[:, None])
+            d = s[:, :1] - s[:, 1:]
+            n = int(pair.sum())
+            wins, ties = int(((d > 0) & pair).sum()), int(((d == 0) & pair).sum())
+        return (wins + 0.5 * ties) / n if n else float("nan")
+
+    # ---- serving --------------------------------------------------------------------------------------------------------
+    def item_rows(self, which="in", normalize=False):
+        """float32[ni, rank]: the ``"in"`` (centre) or ``"out"`` (context) rows of every item in ``items``' order; of unit
+        length (``rerank.unit_rows``) when `normalize`."""
+        if which not in ("in", "out"):
+            raise ValueError("which must be 'in' or 'out', got %r" % (which,))
+        from . import rerank
+        rows = self.in_factors if which == "in" else self.out_factors
+        return rerank.unit_rows(rows) if normalize else rows.contiguous()
+
+    def similar_items(self, items, k=20, exclude_self=True, slack=16):
+        """Per query item its k nearest items by the cosine of the ``in`` rows, ordered (score descending, item id
+        ascending), without the item itself when `exclude_self`: (ids int32[nq, k] padded with -1, scores float32[nq, k]
+        padded with 0, lengths int32[nq]), the triple ``recommend`` returns, by its candidate scheme
+        (``ops.retrieve_topk`` on the unit rows, re-scored by the predict kernel).  An unknown item gets an empty list."""
+        with torch.cuda.device(self.device):
+            unit = self.item_rows("in", normalize=True)
+            pos = self._positions(items, self.items).to(torch.int64)
+            ni = int(self.items.numel())
+            own = torch.arange(ni, dtype=torch.int64, device=self.device)
+            return _recommend_rows(unit, None, pos, unit, self.items, k, slack,
+                                   np.arange(ni + 1, dtype=np.int64) if exclude_self else None, (own << 32) | own,
+                                   lambda q: "item %d" % int(_tensor(items, "items")[q]), "is", "exclude_self")
+
+    def _sequences(self, indices, doc_offsets):
+        """(docs, ipos int64 on the device -- the ids the model knows, the others skipped -- and the host offsets)"""
+        ids, off = _ids_and_offsets(indices, doc_offsets, self.device)
+        ndocs = off.size - 1
+        docs = torch.from_numpy(np.repeat(np.arange(ndocs, dtype=np.int64), np.diff(off))).to(self.device)
+        ipos = self._positions(ids, self.items).to(torch.int64)
+        known = ipos >= 0
+        docs, ipos = docs[known], ipos[known]
+        return docs, ipos, _host_offsets(torch.bincount(docs, minlength=ndocs))
+
+    def _query_rows(self, ipos, offsets):
+        ndocs = offsets.size - 1
+        bags = _tail_bags(ipos, offsets, self.window, self.device)
+        if bags is None:
+            return torch.zeros((ndocs, self.rank), dtype=torch.float32, device=self.device)
+        self._failed.zero_()
+        rows = ops.bag_sum(self.in_factors, *bags.args(), failed=self._failed)
+        self._raise_bad_position("a sequence names an item position outside the table (bit 30)")
+        return rows
+
+    def query_rows(self, indices, doc_offsets):
+        """float32[ndocs, rank]: per sequence ``indices[doc_offsets[d]:doc_offsets[d + 1]]`` the mean of the ``in`` rows of
+        its last ``window`` ids that the model knows (unknown ids are skipped): ``ops.bag_sum`` with the weights
+        ``float32(1 / c)``, oldest first.  A sequence without a known id gets zeros."""
+        with torch.cuda.device(self.device):
+            _, ipos, offsets = self._sequences(indices, doc_offsets)
+            return self._query_rows(ipos, offsets)
+
+    def recommend_sequences(self, indices, doc_offsets, k=500, exclude_seen=True, slack=16):
+        """``recommend``'s lists for GIVEN sequences: ``query_rows`` scored against ``out_factors`` -- the items most likely
+        in the context of the sequence's tail.  Sessions the model never saw are served; ids it does not know are
+        skipped, as ``FPMC.recommend_sequences`` skips them.  `exclude_seen` leaves out the sequence's own items.  Returns
+        (rec_ids, rec_scores, rec_lengths), what ``evaluate.ranking_metrics`` and ``diversify`` take."""
+        with torch.cuda.device(self.device):
+            docs, ipos, offsets = self._sequences(indices, doc_offsets)
+            ndocs = offsets.size - 1
+            queries = self._query_rows(ipos, offsets)
+            key = torch.unique((docs << 32) | ipos)
+            seen_offsets = _host_offsets(torch.bincount(key >> 32, minlength=ndocs)) if exclude_seen else None
+            return _recommend_rows(queries, None, torch.arange(ndocs, dtype=torch.int64, device=self.device),
+                                   self.out_factors, self.items, k, slack, seen_offsets, key, lambda q: "sequence %d" % q,
+                                   "holds", "exclude_seen")

@@ -2327,6 +2327,79 @@ def fpmc_fwd_bwd(user_table, item_table, next_table, prev_table, seq_ipos, u, e,
 
 
 # ---------------------------------------------------------------------------------------------
+# Skip-gram with negative sampling (esr_sgns.hip): the slot sampler and the fused forward / backward over 2 + K rows
+def sgns_geometry():
+    """(max_window, max_negatives, max_rank, rank_multiple): the largest context distance and the most noise items per
+    slot; sgns_fwd_bwd takes a rank that is a multiple of rank_multiple and at most max_rank."""
+    out = [ctypes.c_int(0) for _ in range(4)]
+    check(_lib.load().esr_sgns_geometry(*[ctypes.byref(v) for v in out]), "esr_sgns_geometry")
+    return tuple(int(v.value) for v in out)
+
+
+def sgns_sample(seq_offsets, seq_upos, seq_ipos, nd, ni, window, negatives, noise_keep, noise_alias, seed, step0, K, B):
+    """K steps of B slots drawn on the device: (c, e, o, valid) int32 [K, B], neg int32 [K, B, negatives] -- row k is
+    global step step0 + k (mod 2^32) -- and dropped int32[K], the count of valid == 0 per step.  The documents are a CSR in
+    order on the DEVICE (seq_offsets int64[nd + 1], seq_upos / seq_ipos int32[nnz_seq], repeats kept); the noise table is
+    noise_keep (the uint32 thresholds, held as int32 bits) and noise_alias int32[ni].  The rule is esr_sgns_sample.h's:
+    e is the event, c its item, o the item at a distance d <= window drawn with weight window - d + 1 on a random side
+    (valid = 0 where that leaves the document), neg the alias table's draws."""
+    lib = _lib.load()
+    nd, ni, K, B, window, negatives = int(nd), int(ni), int(K), int(B), int(window), int(negatives)
+    nnz_seq = _check_device_csr("sgns_sample", "seq_offsets", seq_offsets, seq_upos, seq_ipos, nd, ni=ni, K=K, B=B)
+    _req(noise_keep, torch.int32, "noise_keep"), _req(noise_alias, torch.int32, "noise_alias")
+    if noise_keep.numel() != ni or noise_alias.numel() != ni:
+        raise ValueError("sgns_sample: noise_keep and noise_alias must hold ni = %d entries" % ni)
+    top_window, top_negatives = sgns_geometry()[:2]
+    if not 1 <= window <= top_window:
+        raise ValueError("sgns_sample: window = %d outside [1, %d]" % (window, top_window))
+    if not 1 <= negatives <= top_negatives:
+        raise ValueError("sgns_sample: negatives = %d outside [1, %d]" % (negatives, top_negatives))
+    dev = seq_upos.device
+    out = torch.empty((4, K, B), dtype=torch.int32, device=dev)
+    neg = torch.empty((K, B, negatives), dtype=torch.int32, device=dev)
+    dropped = torch.empty(K, dtype=torch.int32, device=dev)
+    check(lib.esr_sgns_sample(_p(seq_offsets), _p(seq_upos), _p(seq_ipos), nnz_seq, nd, ni, window, negatives, _p(noise_keep),
+                              _p(noise_alias), int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF, K, B, _p(out[0]), _p(out[1]),
+                              _p(out[2]), _p(out[3]), _p(neg), _p(dropped), _stream()), "esr_sgns_sample")
+    return out[0], out[1], out[2], out[3], neg, dropped
+
+
+def sgns_fwd_bwd(in_table, out_table, c, o, neg, valid, reg, want_grads=True, want_diff=False, failed=None):
+    """(loss_t float32[B], diff_t float32[B, 1 + K] or None, grads float32[(2 + K) B, D] or None) of the slots (c, o)
+    int32[B], neg int32[B, K] over the tables in [ni, D] (centre vectors) and out [ni, D] (context vectors):
+    s_o = v_c . w_o, s_k = v_c . w_{n_k}, m_k = (n_k != o), loss_t = softplus(-s_o) + sum_k m_k softplus(s_k), diff_t =
+    [s_o, s_0, ..], and the gradient rows [centre ; positive ; noise k-major] in occurrence order with the L2 term
+    reg * row (include/esr_hip.h).  valid int32[B] or None (all valid): valid = 0 gives zeros.  `failed` (int32[1], device;
+    a scratch word when None) gets bit 30 when an id lies outside the tables -- that slot gives zeros too; the caller
+    zeroes and reads it."""
+    lib = _lib.load()
+    _req(in_table, torch.float32, "in_table"), _req(out_table, torch.float32, "out_table")
+    _req(c, torch.int32, "c"), _req(o, torch.int32, "o"), _req(neg, torch.int32, "neg")
+    if in_table.dim() != 2 or in_table.shape != out_table.shape:
+        raise ValueError("in_table and out_table must be [ni, rank] alike")
+    B, D = c.numel(), int(in_table.shape[1])
+    if neg.dim() != 2 or o.numel() != B or neg.shape[0] != B:
+        raise ValueError("c and o must have one length B and neg be [B, negatives]")
+    K = int(neg.shape[1])
+    if not 1 <= K <= sgns_geometry()[1]:
+        raise ValueError("sgns_fwd_bwd: negatives = %d outside [1, %d]" % (K, sgns_geometry()[1]))
+    if valid is not None:
+        _req(valid, torch.int32, "valid")
+        if valid.numel() != B:
+            raise ValueError("valid must hold one entry per slot")
+    _check_rank4(D, *sgns_geometry()[2:])
+    dev = in_table.device
+    failed = _failed_word(failed, dev)
+    loss_t = torch.empty(B, dtype=torch.float32, device=dev)
+    diff_t = torch.empty((B, 1 + K), dtype=torch.float32, device=dev) if want_diff else None
+    grads = torch.empty(((2 + K) * B, D), dtype=torch.float32, device=dev) if want_grads else None
+    if B:
+        check(lib.esr_sgns_fwd_bwd(_p(in_table), _p(out_table), in_table.shape[0], D, _p(c), _p(o), _p(neg), _p(valid), B, K,
+                                   float(reg), _p(loss_t), _p(diff_t), _p(grads), _p(failed), _stream()), "esr_sgns_fwd_bwd")
+    return loss_t, diff_t, grads
+
+
+# ---------------------------------------------------------------------------------------------
 # Diversity re-ranking (esr_rerank.hip): MMR over candidate lists, intra-list similarity
 def rerank_geometry(D, width):
     """A dict for lists of `width` candidates over rows of rank `D`: the limits (max_rank, rank_multiple, max_width,

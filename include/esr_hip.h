@@ -1294,6 +1294,45 @@ int esr_fpmc_fwd_bwd(const float* user_table, int64_t nu, const float* item_tabl
                      const int64_t* ctx_offsets, int64_t M, float reg, float* loss_t, float* diff_t, float* grads,
                      int32_t* ctx_ids, int32_t* failed, esr_stream_t stream);
 
+/* ---- Skip-gram with negative sampling (Mikolov et al., NIPS 2013; item2vec, Barkan and Koenigstein 2016; esr_sgns.hip) ----
+ * Item or word vectors trained straight from id sequences: two f32 tables of ni rows and one rank D, in_table (the centre
+ * vectors v) and out_table (the context vectors w); no user table.  The documents are a CSR in order with repeats kept:
+ * seq_offsets int64[nd + 1], seq_upos (the document of an event) / seq_ipos (its item position) int32[nnz_seq].  The noise
+ * distribution is an alias table: noise_keep uint32[ni], noise_alias int32[ni]; column n yields item n for a 32-bit word
+ * below noise_keep[n] and noise_alias[n] otherwise (a full column: noise_alias[n] == n).  No workspace; the calls never
+ * synchronise.
+ *   geometry    max_window (32), max_negatives (16); D is a multiple of rank_multiple (4) and at most max_rank (128).
+ *   sample      K steps of B slots in one launch, outputs int32 row-major: c, e, o, valid [K, B], neg [K, B, negatives];
+ *               row k = global step step0 + k (mod 2^32).  The rule is esr_sgns_sample.h's sgns_sample_slot over
+ *               esr_bpr_sample's counter layout (t, s, block, 0): word 0 of block 0 picks the event e by multiply-high
+ *               over nnz_seq, c = seq_ipos[e]; word 1 the distance d in [1, window] with weight window - d + 1; the top
+ *               bit of word 2 the side; o = seq_ipos[e +- d] when that event lies in e's document, else valid = 0 and
+ *               o = c.  Noise item k takes words 2 (k & 1), 2 (k & 1) + 1 of block 1 + (k >> 1): the column by
+ *               multiply-high over ni, then the column's own item or its alias.  A slot is a function of (seed, step,
+ *               slot, the CSR, window, negatives, the noise table) alone.  dropped int32[K] = the exact count of
+ *               valid == 0 per step (zeroed by the call; integer atomics).
+ *   fwd_bwd     per slot t (c, o int32[B], neg int32[B, negatives]; valid int32[B] or null = all valid) with v = in[c],
+ *               s_o = v . out[o], s_k = v . out[n_k] in f32 in the order esr_sgns.hip states (a function of D alone) and
+ *               m_k = (n_k != o):  loss_t[t] = softplus(-s_o) + sum_k m_k softplus(s_k);  diff_t float[B, 1 + negatives]
+ *               (may be null) = [s_o, s_0, ..];  grads float[(2 + negatives) B, D] (may be null: forward only) =
+ *               [centre rows ; positive rows ; noise rows k-major], noise item k of slot t at row (2 + k) B + t:
+ *                 g_c = (sigmoid(s_o) - 1) out[o] + sum_k m_k sigmoid(s_k) out[n_k] + reg v   (positive, then k ascending),
+ *                 g_o = (sigmoid(s_o) - 1) v + reg out[o],   g_n_k = m_k (sigmoid(s_k) v + reg out[n_k]).
+ *               valid[t] == 0 writes zero rows, loss_t = 0 and zero scores and reads no table row.  A c, o or n_k outside
+ *               [0, ni) sets bit 30 of *failed (the caller zeroes and reads it) whatever valid says; that slot reads no
+ *               table row and writes zeros.  No reduction across slots: an output depends on its own slot, reg and D only.
+ * 1 <= nd, ni, nnz_seq, K, B <= 2^31 - 1; 2 ni <= 2^31 - 1 (the virtual row space of the update over the two tables);
+ * (2 + negatives) B <= 2^31 - 1; 1 <= window <= 32; 1 <= negatives <= 16; reg finite and not negative.  Tables and grads
+ * 16-byte aligned, seq_offsets 8-byte aligned. */
+int esr_sgns_geometry(int* max_window, int* max_negatives, int* max_rank, int* rank_multiple);
+int esr_sgns_sample(const int64_t* seq_offsets, const int32_t* seq_upos, const int32_t* seq_ipos, int64_t nnz_seq, int64_t nd,
+                    int64_t ni, int window, int negatives, const uint32_t* noise_keep, const int32_t* noise_alias,
+                    uint64_t seed, uint32_t step0, int64_t K, int64_t B, int32_t* out_c, int32_t* out_e, int32_t* out_o,
+                    int32_t* out_valid, int32_t* out_neg, int32_t* dropped, esr_stream_t stream);
+int esr_sgns_fwd_bwd(const float* in_table, const float* out_table, int64_t ni, int D, const int32_t* c, const int32_t* o,
+                     const int32_t* neg, const int32_t* valid, int64_t B, int negatives, float reg, float* loss_t,
+                     float* diff_t, float* grads, int32_t* failed, esr_stream_t stream);
+
 /* ---- Diversity re-ranking (MMR, Carbonell and Goldstein 1998; intra-list similarity, Ziegler et al. 2005; esr_rerank.hip) ----
  * rows float[ni, D] are the items' rows (D a multiple of 4 in [4, 128]), cand int32[nq, width] item POSITIONS into rows,
  * rel float[nq, width], lengths int32[nq] or null (full rows), 1 <= width <= 1024.  The rule of both calls is stated in
