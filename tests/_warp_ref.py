@@ -41,13 +41,25 @@ ARRAYS = ("loss_t", "d", "grads")
 
 
 # ---- the rule --------------------------------------------------------------------------------------------------------------
-def stream_words(seed, step, B, nwords):
-    """uint64 [B, >= nwords]: word 4 b + w of slot t is word w of philox4x32_10((t, step, b, 0), (seed lo, seed hi))"""
+def _slot_numbers(B, slots):
+    """the slot numbers a restatement runs over: arange(B), or the chosen ones (each in [0, B))"""
+    if slots is None:
+        return np.arange(B, dtype=np.int64)
+    slots = np.asarray(slots, np.int64).reshape(-1)
+    assert slots.size == 0 or (0 <= slots.min() and slots.max() < B)
+    return slots
+
+
+def stream_words(seed, step, B, nwords, slots=None):
+    """uint64 [B, >= nwords]: word 4 b + w of slot t is word w of philox4x32_10((t, step, b, 0), (seed lo, seed hi)); with
+    `slots` (int array of slot numbers below B) row n is the stream of slot slots[n]"""
     seed = int(seed) & (2 ** 64 - 1)
     key = np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint64)
     nblocks = (nwords + 3) // 4
+    slots = _slot_numbers(B, slots)
+    B = slots.size
     counter = np.zeros((B, nblocks, 4), np.uint64)
-    counter[:, :, 0] = np.arange(B, dtype=np.uint64)[:, None]
+    counter[:, :, 0] = slots.astype(np.uint64)[:, None]
     counter[:, :, 1] = int(step) & 0xFFFFFFFF
     counter[:, :, 2] = np.arange(nblocks, dtype=np.uint64)[None, :]
     return philox4x32_10(counter, key).astype(np.uint64).reshape(B, 4 * nblocks)
@@ -57,17 +69,20 @@ def harmonic(ni):
     return np.concatenate([[0.0], np.cumsum(1.0 / np.arange(1, ni + 1, dtype=np.float64))]).astype(np.float32)
 
 
-def warp_ref(user, item, csr, rank_weight, seed, step, B, T, margin, reg, dtype):
+def warp_ref(user, item, csr, rank_weight, seed, step, B, T, margin, reg, dtype, slots=None):
     """The step's outputs by the rule of esr_warp_sample.h in `dtype`: a dict with u, i, j, valid, trials (int32 [B]), s_i,
     d, loss_t ([B]), grads ([3 B, D]), bad (did a slot meet an item position outside the table) and undecided (bool [B]:
-    some scored candidate lies within the window around the margin; meaningful for dtype = float64)."""
+    some scored candidate lies within the window around the margin; meaningful for dtype = float64).  With `slots` (an
+    int array of slot numbers below B) the rule runs for those slots only: every output is indexed by the position in
+    `slots` and grads is [3 len(slots), D] -- a slot is a function of its own number, never of B."""
     row_offsets, row_upos, row_ipos = (np.asarray(a, np.int64) for a in csr)
     U, Y = np.asarray(user).astype(dtype), np.asarray(item).astype(dtype)
     nu, ni, nnz, D = U.shape[0], Y.shape[0], row_upos.size, U.shape[1]
     assert 1 <= T <= MAX_TRIALS and row_offsets.size == nu + 1 and np.asarray(rank_weight).shape == (ni + 1,)
     weight = np.asarray(rank_weight, np.float32).astype(dtype)
     margin, reg = dtype(np.float32(margin)), dtype(np.float32(reg))
-    words = stream_words(seed, step, B, T + 1)
+    words = stream_words(seed, step, B, T + 1, slots)
+    B = words.shape[0]
     p = ((words[:, 0] * np.uint64(nnz)) >> np.uint64(32)).astype(np.int64)
     u = np.clip(row_upos[p], 0, nu - 1)
     i = row_ipos[p]

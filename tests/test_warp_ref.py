@@ -114,6 +114,31 @@ def test_the_cases_cover_every_class_of_search():
     assert ties["valid"].all() and (ties["trials"] > 1).any()         # ties were walked past
 
 
+def test_chosen_slots_equal_the_same_rows_of_the_whole_step():
+    """warp_ref(slots=...) is the whole restatement's rows at those slots, for every key: an exact case, a random one in
+    both dtypes, slots out of order with a repeat, and the empty choice"""
+    exact = next((c, r) for c, r in wref.exact_cases() if c["name"] == "grid-D100-B257-T5")
+    rand = wref.random_cases()[1]                                    # D 64, B 1024, T 32
+    for case, full, dtype in (exact + (np.float64,), (rand[0], rand[1], np.float64), (rand[0], rand[2], np.float32)):
+        B = case["B"]
+        for slots in (np.array([B - 1, 0, 63, 64, 65, 0, B // 2]), np.arange(B - 7, B), np.arange(B), np.zeros(0, np.int64)):
+            part = wref.warp_ref(case["user"], case["item"], case["csr"], case["weight"], case["seed"], case["step"], B,
+                                 case["T"], case["margin"], case["reg"], dtype, slots=slots)
+            assert set(part) == set(full)
+            for k in wref.IDS + ("s_i", "d", "loss_t", "undecided"):
+                assert part[k].dtype == full[k].dtype and np.array_equal(part[k], full[k][slots]), (case["name"], k)
+            assert part["grads"].shape == (3 * slots.size, case["user"].shape[1]) and part["grads"].dtype == full["grads"].dtype
+            for third in range(3):
+                assert np.array_equal(part["grads"][third * slots.size:(third + 1) * slots.size],
+                                      full["grads"][third * B + slots]), (case["name"], third)
+            assert part["bad"] is False and full["bad"] is False
+        words = wref.stream_words(case["seed"], case["step"], B, case["T"] + 1)
+        two = wref.stream_words(case["seed"], case["step"], B, case["T"] + 1, slots=[B - 1, 3])
+        assert np.array_equal(two, words[[B - 1, 3]])
+    with pytest.raises(AssertionError):
+        wref.stream_words(1, 0, 8, 4, slots=[8])                     # a slot number is below B
+
+
 def test_rank_weight_tables():
     h = wref.harmonic(5)
     assert h.dtype == np.float32 and h[0] == 0 and h[1] == 1 and h[2] == 1.5 and h[5] == np.float32(137.0 / 60.0)
