@@ -21,7 +21,7 @@ HEADERS = [os.path.join(HERE, "..", "include", "esr_probe.h"), os.path.join(CSRC
            os.path.join(CSRC, "esr_philox.h"), os.path.join(CSRC, "esr_rank_keys.h"), os.path.join(CSRC, "esr_wide_table.h"),
            os.path.join(CSRC, "esr_bpr_sample.h"), os.path.join(CSRC, "esr_warp_sample.h"), os.path.join(CSRC, "esr_bag_rule.h"), os.path.join(CSRC, "esr_row4.h"),
            os.path.join(CSRC, "esr_rerank_rule.h"), os.path.join(CSRC, "esr_fpmc_sample.h"),
-           os.path.join(CSRC, "esr_sgns_sample.h")]
+           os.path.join(CSRC, "esr_sgns_sample.h"), os.path.join(CSRC, "esr_sampled.h")]
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

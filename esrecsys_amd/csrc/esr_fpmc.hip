@@ -6,16 +6,15 @@
 // event, oldest first, every weight w = 1.0f / c:  m = fmaf(w, P[l], m) from +0.0f over the context in order.
 //
 // Sampler.  One lane per slot; the rule is fpmc_sample_slot (esr_fpmc_sample.h), a function of (seed, step, slot, the two
-// CSRs, window) alone.  A workgroup serves 256 consecutive slots of ONE step, so the invalid slots of a wave are counted
-// with a ballot and added to dropped[k] by one integer atomic per wave.  Integer arithmetic only; the only loops are the
-// 15 candidates and the 31-probe binary search; no workgroup waits on another and nothing is polled.
+// CSRs, window) alone, inside the sampler shell of esr_sampled.h (sample_slots).  Integer arithmetic only; the only loops
+// are BPR's 15 candidates and 31-probe binary search (bpr_walk_negative); no workgroup waits on another, nothing is polled.
 //
 // Forward / backward.  One slot per group of G lanes in the float4 row-group layout of esr_row4.h.  The group reads its
 // slot's words and its c context ids, then issues the 5 + c row loads (at most 13 float4 per lane) before the first use:
 // a gather kernel of this shape lives on the loads it keeps in flight.
 //   Summation order of d, a function of D alone: per lane from acc = 0 the chain fmaf(x[e], a_i[e] - a_j[e], acc) over
-//   e = 0 .. 3, then fmaf(m[e], bn_i[e] - bn_j[e], acc) over e = 0 .. 3; then the butterfly of group_sum over the G lanes.
-//   loss_t and g = sigmoid(-d) take the overflow-free forms of bpr_fwd_bwd_kernel.
+//   e = 0 .. 3, then fmaf(m[e], bn_i[e] - bn_j[e], acc) over e = 0 .. 3 (two row4_dot, the second on from the first); then
+//   the butterfly of group_sum over the G lanes.  loss_t and g = sigmoid(-d) are logistic(-d, ..) of esr_row4.h.
 //   Rows: triple_grads(x, a_i, a_j, g, reg) for U_u, A_i, A_j; triple_grads(m, bn_i, bn_j, g, reg) for Bn_i, Bn_j, and its
 //   first output with reg = 0 is g_m; context occurrence n gets bag_expand_elem(w, g_m, reg, P[l_n]) per element.
 // Occurrence n of slot t is row 5 B + ctx_offsets[t] + n of grads and entry ctx_offsets[t] + n of ctx_ids; the caller
@@ -27,11 +26,9 @@
 #include "esr_common.h"
 #include "esr_fpmc_sample.h"
 #include "esr_row4.h"
+#include "esr_sampled.h"
 
 namespace esr {
-
-constexpr int kFpmcFailBadPosition = 1 << 30;  // as FAIL_BAD_POSITION of esr_als.hip
-constexpr int64_t kFpmcMaxSampleBlocks = (int64_t)kMaxGrid * 16;
 
 __global__ __launch_bounds__(kBlock) void fpmc_sample_kernel(
     const int64_t* __restrict__ seq_offsets, const int32_t* __restrict__ seq_upos, const int32_t* __restrict__ seq_ipos,
@@ -39,25 +36,17 @@ __global__ __launch_bounds__(kBlock) void fpmc_sample_kernel(
     int64_t nu, uint32_t ni, int window, uint64_t seed, uint32_t step0, int64_t K, int64_t B, int64_t blocks_per_step,
     int32_t* __restrict__ out_u, int32_t* __restrict__ out_e, int32_t* __restrict__ out_c, int32_t* __restrict__ out_i,
     int32_t* __restrict__ out_j, int32_t* __restrict__ out_valid, int32_t* __restrict__ dropped) {
-  const int64_t nblocks = K * blocks_per_step;
-  for (int64_t w = blockIdx.x; w < nblocks; w += gridDim.x) {  // (uniform per workgroup)
-    const int64_t k = w / blocks_per_step, t = (w % blocks_per_step) * kBlock + threadIdx.x;
-    bool bad = false;
-    if (t < B) {
-      const FpmcSlot r = fpmc_sample_slot(seq_offsets, seq_upos, seq_ipos, nnz_seq, row_offsets, row_ipos, nnz_seen, nu, ni,
-                                          window, seed, step0 + (uint32_t)k, (uint32_t)t);
-      const int64_t at = k * B + t;
-      out_u[at] = r.u;
-      out_e[at] = r.e;
-      out_c[at] = r.c;
-      out_i[at] = r.i;
-      out_j[at] = r.j;
-      out_valid[at] = r.valid;
-      bad = !r.valid;
-    }
-    const unsigned long long mask = __ballot(bad);
-    if ((threadIdx.x & (kWave - 1)) == 0 && mask) atomicAdd(dropped + k, (int32_t)__popcll(mask));
-  }
+  sample_slots(K, B, blocks_per_step, dropped, [&](int64_t k, int64_t t, int64_t at) {
+    const FpmcSlot r = fpmc_sample_slot(seq_offsets, seq_upos, seq_ipos, nnz_seq, row_offsets, row_ipos, nnz_seen, nu, ni,
+                                        window, seed, step0 + (uint32_t)k, (uint32_t)t);
+    out_u[at] = r.u;
+    out_e[at] = r.e;
+    out_c[at] = r.c;
+    out_i[at] = r.i;
+    out_j[at] = r.j;
+    out_valid[at] = r.valid;
+    return r.valid != 0;
+  });
 }
 
 __device__ __forceinline__ float4 fpmc_step4(float w, float4 e, float4 acc) {
@@ -119,20 +108,9 @@ __global__ __launch_bounds__(kBlock) void fpmc_fwd_bwd_kernel(
 #pragma unroll
       for (int n = 0; n < kFpmcMaxWindow; ++n)
         if (n < c) m = fpmc_step4(w, p[n], m);
-      const float4 da = make_float4(ai.x - aj.x, ai.y - aj.y, ai.z - aj.z, ai.w - aj.w);
-      const float4 db = make_float4(bi.x - bj.x, bi.y - bj.y, bi.z - bj.z, bi.w - bj.w);
-      float acc = __fmaf_rn(x.x, da.x, 0.f);
-      acc = __fmaf_rn(x.y, da.y, acc);
-      acc = __fmaf_rn(x.z, da.z, acc);
-      acc = __fmaf_rn(x.w, da.w, acc);
-      acc = __fmaf_rn(m.x, db.x, acc);
-      acc = __fmaf_rn(m.y, db.y, acc);
-      acc = __fmaf_rn(m.z, db.z, acc);
-      acc = __fmaf_rn(m.w, db.w, acc);
-      d = group_sum(acc, G);
-      const float ex = expf(-fabsf(d));
-      loss = fmaxf(-d, 0.f) + log1pf(ex);
-      const float g = __fdiv_rn(d >= 0.f ? ex : 1.0f, 1.0f + ex);  // sigmoid(-d)
+      d = group_sum(row4_dot(m, sub4(bi, bj), row4_dot(x, sub4(ai, aj))), G);
+      float g;
+      logistic(-d, loss, g);
       triple_grads(x, ai, aj, g, reg, gu, gai, gaj);
       float4 unused_i, unused_j;
       triple_grads(m, bi, bj, g, 0.f, gm, unused_i, unused_j);
@@ -142,16 +120,12 @@ __global__ __launch_bounds__(kBlock) void fpmc_fwd_bwd_kernel(
     if (lig == 0) {
       loss_t[t] = loss;
       if (diff_t) diff_t[t] = d;
-      if (bad) atomicOr(failed, kFpmcFailBadPosition);
+      if (bad) atomicOr(failed, kFailBadPosition);
     }
     if (grads) {
-      if (holds) {
-        *reinterpret_cast<float4*>(grads + t * D + 4 * lig) = gu;
-        *reinterpret_cast<float4*>(grads + (B + t) * D + 4 * lig) = gai;
-        *reinterpret_cast<float4*>(grads + (2 * B + t) * D + 4 * lig) = gaj;
-        *reinterpret_cast<float4*>(grads + (3 * B + t) * D + 4 * lig) = gbi;
-        *reinterpret_cast<float4*>(grads + (4 * B + t) * D + 4 * lig) = gbj;
-      }
+      triple_store(grads, t, B, D, lig, holds, gu, gai, gaj);
+      row4_store(grads, 3 * B + t, D, lig, holds, gbi);
+      row4_store(grads, 4 * B + t, D, lig, holds, gbj);
       float* rows = grads + 5 * B * D;
 #pragma unroll
       for (int n = 0; n < kFpmcMaxWindow; ++n) {
@@ -162,13 +136,13 @@ __global__ __launch_bounds__(kBlock) void fpmc_fwd_bwd_kernel(
             o = make_float4(bag_expand_elem(w, gm.x, reg, p[n].x), bag_expand_elem(w, gm.y, reg, p[n].y),
                             bag_expand_elem(w, gm.z, reg, p[n].z), bag_expand_elem(w, gm.w, reg, p[n].w));
           if (lig == 0) ctx_ids[q] = (int32_t)l[n];
-          if (holds) *reinterpret_cast<float4*>(rows + q * D + 4 * lig) = o;
+          row4_store(rows, q, D, lig, holds, o);
         }
       }
       // (a range longer than the window -- ctx_offsets that are not the scan of c -- was refused above: zeros under id 0)
       for (int64_t q = q0 + kFpmcMaxWindow; q < q1; ++q) {
         if (lig == 0) ctx_ids[q] = 0;
-        if (holds) *reinterpret_cast<float4*>(rows + q * D + 4 * lig) = row4_zero();
+        row4_store(rows, q, D, lig, holds, row4_zero());
       }
     }
   }
@@ -194,15 +168,11 @@ int esr_fpmc_sample(const int64_t* seq_offsets, const int32_t* seq_upos, const i
                     int32_t* out_i, int32_t* out_j, int32_t* out_valid, int32_t* dropped, esr_stream_t stream) {
   TraceScope trace_scope_("esr_fpmc_sample");
   const char* who = "esr_fpmc_sample";
-  ESR_REQUIRE(nnz_seq >= 1 && nnz_seq <= (int64_t)INT32_MAX && nnz_seen >= 1 && nnz_seen <= (int64_t)INT32_MAX && ni >= 1 &&
-                  ni <= (int64_t)INT32_MAX && nu >= 1 && nu <= (int64_t)INT32_MAX,
-              "%s: bad sizes nu=%lld ni=%lld nnz_seq=%lld nnz_seen=%lld (each in [1, 2^31 - 1]: nnz_seq and ni are 32-bit "
-              "multiply-high factors)",
-              who, (long long)nu, (long long)ni, (long long)nnz_seq, (long long)nnz_seen);
+  if (int rc = check_sizes(who, {{"nu", nu}, {"ni", ni}, {"nnz_seq", nnz_seq}, {"nnz_seen", nnz_seen}},
+                           ": nnz_seq and ni are 32-bit multiply-high factors"))
+    return rc;
   ESR_REQUIRE(nu + 3 * ni <= (int64_t)INT32_MAX, "%s: nu + 3 ni = %lld exceeds 2^31 - 1 (the virtual row space of the update)",
               who, (long long)(nu + 3 * ni));
-  ESR_REQUIRE(K >= 1 && K <= (int64_t)INT32_MAX && B >= 1 && B <= (int64_t)INT32_MAX,
-              "%s: bad sizes K=%lld B=%lld (each in [1, 2^31 - 1])", who, (long long)K, (long long)B);
   ESR_REQUIRE(window >= 1 && window <= kFpmcMaxWindow, "%s: window=%d outside [1, %d]", who, window, kFpmcMaxWindow);
   ESR_REQUIRE(seq_offsets && seq_upos && seq_ipos && row_offsets && row_ipos && out_u && out_e && out_c && out_i && out_j &&
                   out_valid && dropped,
@@ -212,10 +182,9 @@ int esr_fpmc_sample(const int64_t* seq_offsets, const int32_t* seq_upos, const i
                     (uintptr_t)out_c | (uintptr_t)out_i | (uintptr_t)out_j | (uintptr_t)out_valid | (uintptr_t)dropped) & 3) == 0,
               "%s: misaligned pointer (int64 arrays: 8 bytes)", who);
   hipStream_t st = as_stream(stream);
-  if (hipMemsetAsync(dropped, 0, (size_t)K * sizeof(int32_t), st) != hipSuccess) return check_launch(who);
-  const int64_t blocks_per_step = cdiv(B, kBlock);
-  // (K * blocks_per_step < 2^31 * 2^23: no overflow)
-  const int grid = (int)std::min<int64_t>(K * blocks_per_step, kFpmcMaxSampleBlocks);
+  int grid;
+  int64_t blocks_per_step;
+  if (int rc = sample_plan(who, K, B, dropped, st, grid, blocks_per_step)) return rc;
   ESR_KT("fpmc_sample", st,
          hipLaunchKernelGGL(fpmc_sample_kernel, dim3(grid), dim3(kBlock), 0, st, seq_offsets, seq_upos, seq_ipos,
                             (uint32_t)nnz_seq, row_offsets, row_ipos, nnz_seen, nu, (uint32_t)ni, window, seed, step0, K, B,
@@ -230,17 +199,13 @@ int esr_fpmc_fwd_bwd(const float* user_table, int64_t nu, const float* item_tabl
                      int32_t* ctx_ids, int32_t* failed, esr_stream_t stream) {
   TraceScope trace_scope_("esr_fpmc_fwd_bwd");
   const char* who = "esr_fpmc_fwd_bwd";
-  ESR_REQUIRE(D >= kRow4RankMultiple && D <= kRow4MaxRank && D % kRow4RankMultiple == 0,
-              "%s: D=%d is not a multiple of %d in [%d, %d]", who, D, kRow4RankMultiple, kRow4RankMultiple, kRow4MaxRank);
-  ESR_REQUIRE(nu >= 1 && nu <= (int64_t)INT32_MAX && ni >= 1 && ni <= (int64_t)INT32_MAX && nnz_seq >= 1 &&
-                  nnz_seq <= (int64_t)INT32_MAX && B >= 1 && B <= (int64_t)INT32_MAX,
-              "%s: bad sizes nu=%lld ni=%lld nnz_seq=%lld B=%lld (each in [1, 2^31 - 1])", who, (long long)nu, (long long)ni,
-              (long long)nnz_seq, (long long)B);
+  if (int rc = check_rank(who, D)) return rc;
+  if (int rc = check_sizes(who, {{"nu", nu}, {"ni", ni}, {"nnz_seq", nnz_seq}, {"B", B}})) return rc;
   ESR_REQUIRE(nu + 3 * ni <= (int64_t)INT32_MAX, "%s: nu + 3 ni = %lld exceeds 2^31 - 1 (the virtual row space of the update)",
               who, (long long)(nu + 3 * ni));
   ESR_REQUIRE(M >= 0 && M <= (int64_t)INT32_MAX, "%s: bad sizes M=%lld (the context occurrences, in [0, 2^31 - 1])", who,
               (long long)M);
-  ESR_REQUIRE(reg >= 0.f && reg <= 3.0e38f, "%s: reg=%g must be finite and not negative", who, (double)reg);
+  if (int rc = check_reg(who, reg)) return rc;
   ESR_REQUIRE(user_table && item_table && next_table && prev_table && seq_ipos && u && e && c && i && j && loss_t && failed,
               "%s: null pointer", who);
   ESR_REQUIRE(!grads || (ctx_offsets && (M == 0 || ctx_ids)), "%s: null pointer (grads without ctx_offsets or ctx_ids)", who);

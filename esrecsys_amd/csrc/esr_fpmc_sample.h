@@ -27,44 +27,28 @@ struct FpmcSlot {
 //   the row the slot carries the last candidate and valid = 0.
 // Nothing else enters: a slot is a function of (seed, s, t, the two CSRs, window) alone.  The relative bias of the event
 // draw is at most nnz_seq / 2^32, that of a candidate at most ni / 2^32.
-// e < nnz_seq by construction; u is clamped into [0, nu), the start of its sequence into [0, e] and its seen row's bounds
-// into [0, nnz_seen] (no-ops on CSRs as described), so an ill-formed CSR gives a wrong slot but never a read outside the
-// arrays, and c <= e - start: the context never crosses into the events of the user before.
+// e < nnz_seq by construction; u and its seen row are clamped by bpr_user_row, the start of its sequence into [0, e]
+// (no-ops on CSRs as described), so an ill-formed CSR gives a wrong slot but never a read outside the arrays, and
+// c <= e - start: the context never crosses into the events of the user before.  The negative is bpr_walk_negative's.
 ESR_HD inline FpmcSlot fpmc_sample_slot(const int64_t* seq_offsets, const int32_t* seq_upos, const int32_t* seq_ipos,
                                         uint32_t nnz_seq, const int64_t* row_offsets, const int32_t* row_ipos,
                                         int64_t nnz_seen, int64_t nu, uint32_t ni, int window, uint64_t seed, uint32_t step,
                                         uint32_t t) {
   const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-  uint32_t counter[4] = {t, step, 0u, 0u}, w[4];
+  const uint32_t counter[4] = {t, step, 0u, 0u};
+  uint32_t w[4];
   philox4x32_10(counter, key, w);
   const int64_t e = (int64_t)(((uint64_t)w[0] * nnz_seq) >> 32);
+  const BprRow row = bpr_user_row(row_offsets, seq_upos[e], nu, nnz_seen);
   FpmcSlot r;
-  int64_t u = seq_upos[e];
-  u = u < 0 ? 0 : (u >= nu ? nu - 1 : u);
-  r.u = (int32_t)u;
+  r.u = row.u;
   r.e = (int32_t)e;
   r.i = seq_ipos[e];
-  int64_t start = seq_offsets[u];
+  int64_t start = seq_offsets[row.u];
   start = start < 0 ? 0 : (start > e ? e : start);
   const int64_t pos = e - start;
   r.c = (int32_t)(pos < (int64_t)window ? pos : (int64_t)window);
-  int64_t lo = row_offsets[u], hi = row_offsets[u + 1];
-  lo = lo < 0 ? 0 : (lo > nnz_seen ? nnz_seen : lo);
-  hi = hi < lo ? lo : (hi > nnz_seen ? nnz_seen : hi);
-  r.j = 0;
-  r.valid = 0;
-  for (int c = 0; c < kBprMaxTries; ++c) {
-    const int word = (c + 1) & 3;
-    if (word == 0) {
-      counter[2] = (uint32_t)(c + 1) >> 2;
-      philox4x32_10(counter, key, w);
-    }
-    r.j = (int32_t)(((uint64_t)w[word] * ni) >> 32);
-    if (!bpr_row_has(row_ipos, lo, hi, r.j)) {
-      r.valid = 1;
-      break;
-    }
-  }
+  r.j = bpr_walk_negative(row_ipos, row.lo, row.hi, key, step, t, ni, w, r.valid);
   return r;
 }
 

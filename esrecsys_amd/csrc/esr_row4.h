@@ -1,9 +1,13 @@
-// The float4 row-group layer of esr_bpr.hip, esr_warp.hip and esr_bag.hip.  One item (a triple, a slot, a selected bag) per
-// group of G lanes, G the power of two >= D / 4 (1 .. 32): lane l of the group holds elements 4 l .. 4 l + 3 of every row as
-// one float4 (lanes with 4 l >= D hold zeros and store nothing): 16 bytes per lane and access, 64 / G items per wave.
-// The first part is plain C++ (tests/host reach it through esr_warp_sample.h); the device functions keep the expressions
-// the kernels used to spell out: kernels agree bit for bit only on the same expression (the note above group_sum).
+// The float4 row-group layer of esr_bpr.hip, esr_warp.hip, esr_fpmc.hip, esr_sgns.hip, esr_bag.hip and esr_rerank.hip.  One
+// item (a triple, a slot, a selected bag) per group of G lanes, G the power of two >= D / 4 (1 .. 32): lane l of the group
+// holds elements 4 l .. 4 l + 3 of every row as one float4 (lanes with 4 l >= D hold zeros and store nothing): 16 bytes per
+// lane and access, 64 / G items per wave.
+// The first part is plain C++ (tests/host reach it through esr_warp_sample.h): the geometry and the one summation chain.
+// The device part holds where a thread stands, the row accesses, the float4 arithmetic, the one logistic and the triple
+// family's gradient rows; each keeps the expression the kernels used to spell out: kernels agree bit for bit only on the
+// same expression (the note above group_sum).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #ifndef ESR_HD
@@ -23,6 +27,15 @@ ESR_HD inline int row4_lanes(int D) {
   int G = 1;
   while (G < D / 4) G <<= 1;
   return G;
+}
+
+// One lane's chain over its four elements, on from acc: the only text of the summation order of every score of the
+// family (warp_lane_dot for the host programs, row4_dot for the kernels).
+ESR_HD inline float row4_chain(float x0, float x1, float x2, float x3, float y0, float y1, float y2, float y3, float acc) {
+  acc = fmaf(x0, y0, acc);
+  acc = fmaf(x1, y1, acc);
+  acc = fmaf(x2, y2, acc);
+  return fmaf(x3, y3, acc);
 }
 
 }  // namespace esr
@@ -68,11 +81,34 @@ __device__ __forceinline__ void row4_store(float* table, int64_t row, int D, int
   if (holds) *reinterpret_cast<float4*>(table + row * D + 4 * lig) = v;
 }
 
-// The triple family (BPR, WARP): the lane's chunks of the three gradient rows of (x, y_i, y_j) under the scalar g,
+// The lane's share of a . b in row4_chain's order, on from acc.
+__device__ __forceinline__ float row4_dot(float4 a, float4 b, float acc = 0.f) {
+  return row4_chain(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, acc);
+}
+// per element: a - b, fmaf(a, x, y), a * x, m ? a : b (a ternary on the struct itself selects between two addresses: scratch)
+__device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+__device__ __forceinline__ float4 fma4(float a, float4 x, float4 y) {
+  return make_float4(__fmaf_rn(a, x.x, y.x), __fmaf_rn(a, x.y, y.y), __fmaf_rn(a, x.z, y.z), __fmaf_rn(a, x.w, y.w));
+}
+__device__ __forceinline__ float4 mul4(float a, float4 x) {
+  return make_float4(__fmul_rn(a, x.x), __fmul_rn(a, x.y), __fmul_rn(a, x.z), __fmul_rn(a, x.w));
+}
+__device__ __forceinline__ float4 sel4(bool m, float4 a, float4 b) {
+  return make_float4(m ? a.x : b.x, m ? a.y : b.y, m ? a.z : b.z, m ? a.w : b.w);
+}
+// softplus(s) and sigmoid(s) from ex = expf(-|s|) <= 1: neither overflows; expf / log1pf are the precise forms.  A ranking
+// loss softplus(-d) and its g = sigmoid(-d) are logistic(-d, loss, g).
+__device__ __forceinline__ void logistic(float s, float& softplus, float& sigmoid) {
+  const float ex = expf(-fabsf(s));
+  softplus = fmaxf(s, 0.f) + log1pf(ex);
+  sigmoid = __fdiv_rn(s >= 0.f ? 1.0f : ex, 1.0f + ex);
+}
+
+// The triple family (BPR, WARP, FPMC): the lane's chunks of the three gradient rows of (x, y_i, y_j) under the scalar g,
 // g_u = reg x - g (y_i - y_j), g_i = reg y_i - g x, g_j = reg y_j + g x.
 __device__ __forceinline__ void triple_grads(float4 x, float4 yi, float4 yj, float g, float reg, float4& gu,
                                              float4& gi, float4& gj) {
-  const float4 df = make_float4(yi.x - yj.x, yi.y - yj.y, yi.z - yj.z, yi.w - yj.w);
+  const float4 df = sub4(yi, yj);
   gu = make_float4(reg * x.x - g * df.x, reg * x.y - g * df.y, reg * x.z - g * df.z, reg * x.w - g * df.w);
   gi = make_float4(reg * yi.x - g * x.x, reg * yi.y - g * x.y, reg * yi.z - g * x.z, reg * yi.w - g * x.w);
   gj = make_float4(reg * yj.x + g * x.x, reg * yj.y + g * x.y, reg * yj.z + g * x.z, reg * yj.w + g * x.w);
@@ -81,10 +117,10 @@ __device__ __forceinline__ void triple_grads(float4 x, float4 yi, float4 yj, flo
 // [user rows ; positive rows ; negative rows] of triple t of B, one row per occurrence; nothing when grads is null
 __device__ __forceinline__ void triple_store(float* grads, int64_t t, int64_t B, int D, int lig, bool holds, float4 gu,
                                              float4 gi, float4 gj) {
-  if (grads && holds) {
-    *reinterpret_cast<float4*>(grads + t * D + 4 * lig) = gu;
-    *reinterpret_cast<float4*>(grads + (B + t) * D + 4 * lig) = gi;
-    *reinterpret_cast<float4*>(grads + (2 * B + t) * D + 4 * lig) = gj;
+  if (grads) {
+    row4_store(grads, t, D, lig, holds, gu);
+    row4_store(grads, B + t, D, lig, holds, gi);
+    row4_store(grads, 2 * B + t, D, lig, holds, gj);
   }
 }
 

@@ -7,17 +7,17 @@
 //   loss_t = softplus(-s_o) + sum_k m_k softplus(s_k)          (the L2 term enters the gradient rows only, as in BPR).
 //
 // Sampler.  One lane per slot; the rule is sgns_sample_slot (esr_sgns_sample.h), a function of (seed, step, slot, the
-// sequence CSR, window, K, the noise table) alone.  A workgroup serves 256 consecutive slots of ONE step, so the invalid
-// slots of a wave are counted with a ballot and added to dropped[k] by one integer atomic per wave.  Integer arithmetic
-// only; the only loops are the window's turns and the K noise items; no workgroup waits on another, nothing is polled.
+// sequence CSR, window, K, the noise table) alone, inside the sampler shell of esr_sampled.h (sample_slots).  Integer
+// arithmetic only; the only loops are the window's turns and the K noise items; no workgroup waits on another, nothing is
+// polled.
 //
 // Forward / backward.  One slot per group of G lanes in the float4 row-group layout of esr_row4.h.  The group reads its
 // slot's 2 + K ids, then issues the 2 + K row loads (at most 18 float4 per lane) before the first use: a gather kernel of
 // this shape lives on the loads it keeps in flight.
-//   A score, a function of D alone: per lane from acc = 0 the chain fmaf(v[e], w[e], acc) over e = 0 .. 3, then the
-//   butterfly of group_sum over the G lanes.
-//   With ex = expf(-|s|):  softplus(s) = max(s, 0) + log1pf(ex),  sigmoid(s) = (s >= 0 ? 1 : ex) / (1 + ex); the positive
-//   takes both at -s_o, so a_o = -sigmoid(-s_o) = sigmoid(s_o) - 1 and a_k = m_k sigmoid(s_k).
+//   A score, a function of D alone: per lane from acc = 0 the chain fmaf(v[e], w[e], acc) over e = 0 .. 3 (row4_dot), then
+//   the butterfly of group_sum over the G lanes.
+//   logistic of esr_row4.h: with ex = expf(-|s|), softplus(s) = max(s, 0) + log1pf(ex), sigmoid(s) = (s >= 0 ? 1 : ex) /
+//   (1 + ex); the positive takes both at -s_o, so a_o = -sigmoid(-s_o) = sigmoid(s_o) - 1 and a_k = m_k sigmoid(s_k).
 //   Order within a slot: the positive, then k ascending.  loss = softplus(-s_o), then loss += softplus(s_k) where m_k;
 //   g_c = a_o * w_o, then g_c = fmaf(a_k, w_k, g_c) where m_k, last g_c = fmaf(reg, v, g_c), per element;
 //   g_o = fmaf(a_o, v, reg * w_o);  g_n_k = fmaf(a_k, v, reg * w_k) where m_k, else zeros.
@@ -27,12 +27,10 @@
 // across slots, no float atomic, no LDS, no scratch, no grid-wide pass; the step's loss is summed from loss_t by the caller.
 #include "esr_common.h"
 #include "esr_row4.h"
+#include "esr_sampled.h"
 #include "esr_sgns_sample.h"
 
 namespace esr {
-
-constexpr int kSgnsFailBadPosition = 1 << 30;  // as FAIL_BAD_POSITION of esr_als.hip
-constexpr int64_t kSgnsMaxSampleBlocks = (int64_t)kMaxGrid * 16;
 
 __global__ __launch_bounds__(kBlock) void sgns_sample_kernel(
     const int64_t* __restrict__ seq_offsets, const int32_t* __restrict__ seq_upos, const int32_t* __restrict__ seq_ipos,
@@ -40,47 +38,15 @@ __global__ __launch_bounds__(kBlock) void sgns_sample_kernel(
     const int32_t* __restrict__ noise_alias, uint64_t seed, uint32_t step0, int64_t steps, int64_t B,
     int64_t blocks_per_step, int32_t* __restrict__ out_c, int32_t* __restrict__ out_e, int32_t* __restrict__ out_o,
     int32_t* __restrict__ out_valid, int32_t* __restrict__ out_neg, int32_t* __restrict__ dropped) {
-  const int64_t nblocks = steps * blocks_per_step;
-  for (int64_t w = blockIdx.x; w < nblocks; w += gridDim.x) {  // (uniform per workgroup)
-    const int64_t k = w / blocks_per_step, t = (w % blocks_per_step) * kBlock + threadIdx.x;
-    bool bad = false;
-    if (t < B) {
-      const int64_t at = k * B + t;
-      const SgnsSlot r = sgns_sample_slot(seq_offsets, seq_upos, seq_ipos, nnz_seq, nd, ni, window, K, noise_keep,
-                                          noise_alias, seed, step0 + (uint32_t)k, (uint32_t)t, out_neg + at * K);
-      out_c[at] = r.c;
-      out_e[at] = r.e;
-      out_o[at] = r.o;
-      out_valid[at] = r.valid;
-      bad = !r.valid;
-    }
-    const unsigned long long mask = __ballot(bad);
-    if ((threadIdx.x & (kWave - 1)) == 0 && mask) atomicAdd(dropped + k, (int32_t)__popcll(mask));
-  }
-}
-
-__device__ __forceinline__ float sgns_dot4(float4 a, float4 b) {
-  float acc = __fmaf_rn(a.x, b.x, 0.f);
-  acc = __fmaf_rn(a.y, b.y, acc);
-  acc = __fmaf_rn(a.z, b.z, acc);
-  return __fmaf_rn(a.w, b.w, acc);
-}
-// fmaf(a, x, y) per element
-__device__ __forceinline__ float4 sgns_fma4(float a, float4 x, float4 y) {
-  return make_float4(__fmaf_rn(a, x.x, y.x), __fmaf_rn(a, x.y, y.y), __fmaf_rn(a, x.z, y.z), __fmaf_rn(a, x.w, y.w));
-}
-__device__ __forceinline__ float4 sgns_mul4(float a, float4 x) {
-  return make_float4(__fmul_rn(a, x.x), __fmul_rn(a, x.y), __fmul_rn(a, x.z), __fmul_rn(a, x.w));
-}
-// m ? a : b per element (a ternary on the struct itself selects between two addresses: scratch)
-__device__ __forceinline__ float4 sgns_sel4(bool m, float4 a, float4 b) {
-  return make_float4(m ? a.x : b.x, m ? a.y : b.y, m ? a.z : b.z, m ? a.w : b.w);
-}
-// softplus(s) and sigmoid(s) from ex = expf(-|s|) <= 1: neither overflows
-__device__ __forceinline__ void sgns_logistic(float s, float& softplus, float& sigmoid) {
-  const float ex = expf(-fabsf(s));
-  softplus = fmaxf(s, 0.f) + log1pf(ex);
-  sigmoid = __fdiv_rn(s >= 0.f ? 1.0f : ex, 1.0f + ex);
+  sample_slots(steps, B, blocks_per_step, dropped, [&](int64_t k, int64_t t, int64_t at) {
+    const SgnsSlot r = sgns_sample_slot(seq_offsets, seq_upos, seq_ipos, nnz_seq, nd, ni, window, K, noise_keep, noise_alias,
+                                        seed, step0 + (uint32_t)k, (uint32_t)t, out_neg + at * K);
+    out_c[at] = r.c;
+    out_e[at] = r.e;
+    out_o[at] = r.o;
+    out_valid[at] = r.valid;
+    return r.valid != 0;
+  });
 }
 
 // K is a template argument: with K in a register every guard k < K of the three unrolled loops became a lane mask or a
@@ -124,32 +90,32 @@ __global__ __launch_bounds__(kBlock) void sgns_fwd_bwd_kernel(
 #pragma unroll
       for (int k = 0; k < K; ++k) w[k] = row4_load(out_table, n[k], D, lig, holds);
       __builtin_amdgcn_sched_barrier(0);  // (every row load is issued above this line)
-      const float so = group_sum(sgns_dot4(v, wo), G);
+      const float so = group_sum(row4_dot(v, wo), G);
       float loss, sig;
-      sgns_logistic(-so, loss, sig);
+      logistic(-so, loss, sig);
       const float ao = -sig;  // sigmoid(s_o) - 1
-      float4 gc = sgns_mul4(ao, wo);
+      float4 gc = mul4(ao, wo);
       float* const centre = row;
-      if (row) *reinterpret_cast<float4*>(row += pitch) = sgns_fma4(ao, v, sgns_mul4(reg, wo));
+      if (row) *reinterpret_cast<float4*>(row += pitch) = fma4(ao, v, mul4(reg, wo));
       if (diff) diff[0] = so;
 #pragma unroll
       for (int k = 0; k < K; ++k) {
-        const float sk = group_sum(sgns_dot4(v, w[k]), G);
+        const float sk = group_sum(row4_dot(v, w[k]), G);
         const bool m = (differs >> k) & 1u;
         float sp, ak;
-        sgns_logistic(sk, sp, ak);
+        logistic(sk, sp, ak);
         loss += m ? sp : 0.f;
-        const float4 next = sgns_fma4(ak, w[k], gc), gn = sgns_fma4(ak, v, sgns_mul4(reg, w[k]));
-        gc = sgns_sel4(m, next, gc);
-        if (row) *reinterpret_cast<float4*>(row += pitch) = sgns_sel4(m, gn, row4_zero());
+        const float4 next = fma4(ak, w[k], gc), gn = fma4(ak, v, mul4(reg, w[k]));
+        gc = sel4(m, next, gc);
+        if (row) *reinterpret_cast<float4*>(row += pitch) = sel4(m, gn, row4_zero());
         if (diff) diff[1 + k] = sk;
       }
-      if (centre) *reinterpret_cast<float4*>(centre) = sgns_fma4(reg, v, gc);
+      if (centre) *reinterpret_cast<float4*>(centre) = fma4(reg, v, gc);
       if (lig == 0) loss_t[t] = loss;
     } else {
       if (lig == 0) {
         loss_t[t] = 0.f;
-        if (bad) atomicOr(failed, kSgnsFailBadPosition);
+        if (bad) atomicOr(failed, kFailBadPosition);
       }
       for (int k = 0; k < K + 2; ++k) {
         if (row) *reinterpret_cast<float4*>(row + k * pitch) = row4_zero();
@@ -202,15 +168,10 @@ int esr_sgns_sample(const int64_t* seq_offsets, const int32_t* seq_upos, const i
                     int32_t* out_valid, int32_t* out_neg, int32_t* dropped, esr_stream_t stream) {
   TraceScope trace_scope_("esr_sgns_sample");
   const char* who = "esr_sgns_sample";
-  ESR_REQUIRE(nnz_seq >= 1 && nnz_seq <= (int64_t)INT32_MAX && ni >= 1 && ni <= (int64_t)INT32_MAX && nd >= 1 &&
-                  nd <= (int64_t)INT32_MAX,
-              "%s: bad sizes nd=%lld ni=%lld nnz_seq=%lld (each in [1, 2^31 - 1]: nnz_seq and ni are 32-bit multiply-high "
-              "factors)",
-              who, (long long)nd, (long long)ni, (long long)nnz_seq);
+  if (int rc = check_sizes(who, {{"nd", nd}, {"ni", ni}, {"nnz_seq", nnz_seq}}, ": nnz_seq and ni are 32-bit multiply-high factors"))
+    return rc;
   ESR_REQUIRE(2 * ni <= (int64_t)INT32_MAX, "%s: 2 ni = %lld exceeds 2^31 - 1 (the virtual row space of the update)", who,
               (long long)(2 * ni));
-  ESR_REQUIRE(K >= 1 && K <= (int64_t)INT32_MAX && B >= 1 && B <= (int64_t)INT32_MAX,
-              "%s: bad sizes K=%lld B=%lld (each in [1, 2^31 - 1])", who, (long long)K, (long long)B);
   ESR_REQUIRE(window >= 1 && window <= kSgnsMaxWindow, "%s: window=%d outside [1, %d]", who, window, kSgnsMaxWindow);
   ESR_REQUIRE(negatives >= 1 && negatives <= kSgnsMaxNegatives, "%s: negatives=%d outside [1, %d]", who, negatives,
               kSgnsMaxNegatives);
@@ -223,10 +184,9 @@ int esr_sgns_sample(const int64_t* seq_offsets, const int32_t* seq_upos, const i
                     (uintptr_t)dropped) & 3) == 0,
               "%s: misaligned pointer (seq_offsets: 8 bytes)", who);
   hipStream_t st = as_stream(stream);
-  if (hipMemsetAsync(dropped, 0, (size_t)K * sizeof(int32_t), st) != hipSuccess) return check_launch(who);
-  const int64_t blocks_per_step = cdiv(B, kBlock);
-  // (K * blocks_per_step < 2^31 * 2^23: no overflow)
-  const int grid = (int)std::min<int64_t>(K * blocks_per_step, kSgnsMaxSampleBlocks);
+  int grid;
+  int64_t blocks_per_step;
+  if (int rc = sample_plan(who, K, B, dropped, st, grid, blocks_per_step)) return rc;
   ESR_KT("sgns_sample", st,
          hipLaunchKernelGGL(sgns_sample_kernel, dim3(grid), dim3(kBlock), 0, st, seq_offsets, seq_upos, seq_ipos,
                             (uint32_t)nnz_seq, nd, (uint32_t)ni, window, negatives, noise_keep, noise_alias, seed, step0, K, B,
@@ -239,17 +199,15 @@ int esr_sgns_fwd_bwd(const float* in_table, const float* out_table, int64_t ni, 
                      float* diff_t, float* grads, int32_t* failed, esr_stream_t stream) {
   TraceScope trace_scope_("esr_sgns_fwd_bwd");
   const char* who = "esr_sgns_fwd_bwd";
-  ESR_REQUIRE(D >= kRow4RankMultiple && D <= kRow4MaxRank && D % kRow4RankMultiple == 0,
-              "%s: D=%d is not a multiple of %d in [%d, %d]", who, D, kRow4RankMultiple, kRow4RankMultiple, kRow4MaxRank);
-  ESR_REQUIRE(ni >= 1 && ni <= (int64_t)INT32_MAX && B >= 1 && B <= (int64_t)INT32_MAX,
-              "%s: bad sizes ni=%lld B=%lld (each in [1, 2^31 - 1])", who, (long long)ni, (long long)B);
+  if (int rc = check_rank(who, D)) return rc;
+  if (int rc = check_sizes(who, {{"ni", ni}, {"B", B}})) return rc;
   ESR_REQUIRE(2 * ni <= (int64_t)INT32_MAX, "%s: 2 ni = %lld exceeds 2^31 - 1 (the virtual row space of the update)", who,
               (long long)(2 * ni));
   ESR_REQUIRE(negatives >= 1 && negatives <= kSgnsMaxNegatives, "%s: negatives=%d outside [1, %d]", who, negatives,
               kSgnsMaxNegatives);
   ESR_REQUIRE((int64_t)(2 + negatives) * B <= (int64_t)INT32_MAX,
               "%s: (2 + negatives) B = %lld gradient rows exceed 2^31 - 1", who, (long long)((int64_t)(2 + negatives) * B));
-  ESR_REQUIRE(reg >= 0.f && reg <= 3.0e38f, "%s: reg=%g must be finite and not negative", who, (double)reg);
+  if (int rc = check_reg(who, reg)) return rc;
   ESR_REQUIRE(in_table && out_table && c && o && neg && loss_t && failed, "%s: null pointer", who);
   ESR_REQUIRE((((uintptr_t)in_table | (uintptr_t)out_table | (uintptr_t)grads) & 15) == 0 &&
                   (((uintptr_t)c | (uintptr_t)o | (uintptr_t)neg | (uintptr_t)valid | (uintptr_t)loss_t | (uintptr_t)diff_t |

@@ -1,7 +1,7 @@
 // WARP (Weston, Bengio, Usunier, IJCAI 2011) on the device: one fused kernel that samples the pair, scores the positive,
 // searches the candidate stream for a negative that violates the margin, weights the step by the rank estimate and writes
-// the loss and the three gradient rows.  The rule of one slot is esr_warp_sample.h's, which also holds the integer pieces
-// and the per-lane chain this kernel calls; the update itself is the row-sparse engine (esr_sort.hip, esr_optim.hip) driven
+// the loss and the three gradient rows.  The rule of one slot is esr_warp_sample.h's; its integer pieces are BPR's
+// (bpr_pick_pair, bpr_candidate, bpr_row_has of esr_bpr_sample.h) and its per-lane chain is row4_dot; the update itself is the row-sparse engine (esr_sort.hip, esr_optim.hip) driven
 // from factorization.WARP.
 //
 // Layout.  One slot per group of G lanes in the float4 row-group layout of esr_row4.h (as bpr_fwd_bwd_kernel, whose
@@ -15,15 +15,13 @@
 // grid-wide pass and nothing polled.  The only loops are the <= max_trials trials and the <= 32-probe search.
 #include "esr_common.h"
 #include "esr_row4.h"
+#include "esr_sampled.h"
 #include "esr_warp_sample.h"
 
 namespace esr {
 
-constexpr int kWarpFailBadPosition = 1 << 30;  // as FAIL_BAD_POSITION of esr_als.hip
-constexpr int64_t kWarpMaxBlocks = (int64_t)kMaxGrid * 16;
-
 __device__ __forceinline__ float warp_group_dot(const float4& x, const float4& y, int G) {
-  return group_sum(warp_lane_dot(x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w), G);
+  return group_sum(row4_dot(x, y), G);
 }
 
 template <int G>
@@ -40,13 +38,13 @@ __global__ __launch_bounds__(kBlock) void warp_step_kernel(
   const int64_t ngroups = row4_stride<G>();
   for (int64_t t = row4_first<G>(); t < B; t += ngroups) {  // (uniform per group)
     uint32_t w[4];
-    const WarpPair pr = warp_pick_pair(row_offsets, row_upos, row_ipos, nu, nnz, key, step, (uint32_t)t, w);
+    const BprPair pr = bpr_pick_pair(row_offsets, row_upos, row_ipos, nu, nnz, key, step, (uint32_t)t, w);
     const float4 zero = row4_zero();
     float4 gu = zero, gi = zero, gj = zero;
     float loss = 0.f, d = 0.f;
     int32_t j = 0, valid = 0, trials = 0;
     if (pr.i < 0 || (uint32_t)pr.i >= ni) {
-      if (lig == 0) atomicOr(failed, kWarpFailBadPosition);
+      if (lig == 0) atomicOr(failed, kFailBadPosition);
     } else {
       float4 x = zero, yi = zero, yj = zero;
       if (holds) {
@@ -55,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void warp_step_kernel(
       }
       const float si = warp_group_dot(x, yi, G);
       for (int c = 0; c < max_trials && !valid; ++c) {
-        j = warp_candidate(key, step, (uint32_t)t, c, ni, w);
+        j = bpr_candidate(key, step, (uint32_t)t, c, ni, w);
         if (!bpr_row_has(row_ipos, pr.lo, pr.hi, j)) {
           trials += 1;
           if (holds) yj = *row4_ptr(item_table, j, D, lig);
@@ -106,16 +104,13 @@ int esr_warp_step(const float* user_table, int64_t nu, const float* item_table, 
                   int32_t* failed, esr_stream_t stream) {
   TraceScope trace_scope_("esr_warp_step");
   const char* who = "esr_warp_step";
-  ESR_REQUIRE(D >= kRow4RankMultiple && D <= kRow4MaxRank && D % kRow4RankMultiple == 0,
-              "%s: D=%d is not a multiple of %d in [%d, %d]", who, D, kRow4RankMultiple, kRow4RankMultiple, kRow4MaxRank);
-  ESR_REQUIRE(nnz >= 1 && nnz <= (int64_t)INT32_MAX && ni >= 1 && ni <= (int64_t)INT32_MAX && nu >= 1 &&
-                  nu <= (int64_t)INT32_MAX && B >= 1 && B <= (int64_t)INT32_MAX,
-              "%s: bad sizes nu=%lld ni=%lld nnz=%lld B=%lld (each in [1, 2^31 - 1]: nnz and ni are 32-bit multiply-high factors)",
-              who, (long long)nu, (long long)ni, (long long)nnz, (long long)B);
+  if (int rc = check_rank(who, D)) return rc;
+  if (int rc = check_sizes(who, {{"nu", nu}, {"ni", ni}, {"nnz", nnz}, {"B", B}}, ": nnz and ni are 32-bit multiply-high factors"))
+    return rc;
   ESR_REQUIRE(max_trials >= 1 && max_trials <= kWarpMaxTrials, "%s: max_trials=%d outside [1, %d]", who, max_trials,
               kWarpMaxTrials);
   ESR_REQUIRE(margin >= -3.4028235e38f && margin <= 3.4028235e38f, "%s: margin=%g must be finite", who, (double)margin);
-  ESR_REQUIRE(reg >= 0.f && reg <= 3.4028235e38f, "%s: reg=%g must be finite and not negative", who, (double)reg);
+  if (int rc = check_reg(who, reg)) return rc;
   ESR_REQUIRE(user_table && item_table && row_offsets && row_upos && row_ipos && rank_weight && out_u && out_i && out_j &&
                   out_valid && out_trials && loss_t && failed,
               "%s: null pointer", who);
@@ -127,7 +122,7 @@ int esr_warp_step(const float* user_table, int64_t nu, const float* item_table, 
               "%s: misaligned pointer (tables and grads: 16 bytes, row_offsets: 8)", who);
   hipStream_t st = as_stream(stream);
   const int G = row4_lanes(D);
-  const int grid = (int)std::min<int64_t>(cdiv(B, kBlock / G), kWarpMaxBlocks);
+  const int grid = (int)std::min<int64_t>(cdiv(B, kBlock / G), kSampledMaxBlocks);
   ESR_DISPATCH_G(G, ESR_KT("warp_step", st,
                            hipLaunchKernelGGL(warp_step_kernel<GG>, dim3(grid), dim3(kBlock), 0, st, user_table, nu, item_table,
                                               (uint32_t)ni, D, row_offsets, row_upos, row_ipos, (uint32_t)nnz, rank_weight, seed,

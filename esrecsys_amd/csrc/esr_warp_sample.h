@@ -1,8 +1,8 @@
 // WARP (Weston, Bengio, Usunier, "WSABIE: Scaling Up To Large Vocabulary Image Annotation", IJCAI 2011): the search for
 // a margin-violating negative, the rank estimate and the rank-weighted hinge step of ONE slot, as scalar code.  Plain C++
-// with no HIP dependency of its own: the kernel of esr_warp.hip takes its integer pieces (warp_pick_pair, warp_candidate,
-// warp_rank) and its per-lane chain (warp_lane_dot) from here, and a stand-alone host program
-// (tests/host/warp_sample_host.cpp) compiles the whole rule, warp_slot, for the host.
+// with no HIP dependency of its own: the kernel of esr_warp.hip takes its integer pieces (bpr_pick_pair and
+// bpr_candidate of esr_bpr_sample.h, warp_rank) and its per-lane chain (warp_lane_dot, the row4_chain of esr_row4.h)
+// through this file, and a stand-alone host program (tests/host/warp_sample_host.cpp) compiles the whole rule, warp_slot, for the host.
 //
 // The rule.  Inputs: the CSR of seen pairs by user (row_offsets[nu + 1], row_upos[nnz], row_ipos[nnz], item positions
 // ascending and distinct within a row), user_table [nu, D] and item_table [ni, D] float32 with D a multiple of 4 in
@@ -42,47 +42,9 @@ namespace esr {
 constexpr int kWarpMaxTrials = 255;  // candidate c is word c + 1 of the slot's stream: blocks 0 .. 63
 constexpr int kWarpMaxRank = kRow4MaxRank, kWarpRankMultiple = kRow4RankMultiple;  // (tests/host name these)
 
-struct WarpPair {
-  int32_t u, i;
-  int64_t lo, hi;  // u's row of the CSR, clamped into [0, nnz]
-};
-
-// Step 1, the pair: w receives Philox block 0 of the slot (its words 1..3 are candidates 0..2).
-ESR_HD inline WarpPair warp_pick_pair(const int64_t* row_offsets, const int32_t* row_upos, const int32_t* row_ipos, int64_t nu,
-                                      uint32_t nnz, const uint32_t key[2], uint32_t step, uint32_t t, uint32_t w[4]) {
-  const uint32_t counter[4] = {t, step, 0u, 0u};
-  philox4x32_10(counter, key, w);
-  const uint32_t p = (uint32_t)(((uint64_t)w[0] * nnz) >> 32);
-  WarpPair r;
-  int64_t u = row_upos[p];
-  u = u < 0 ? 0 : (u >= nu ? nu - 1 : u);
-  r.u = (int32_t)u;
-  r.i = row_ipos[p];
-  int64_t lo = row_offsets[u], hi = row_offsets[u + 1];
-  lo = lo < 0 ? 0 : (lo > (int64_t)nnz ? (int64_t)nnz : lo);
-  hi = hi < lo ? lo : (hi > (int64_t)nnz ? (int64_t)nnz : hi);
-  r.lo = lo;
-  r.hi = hi;
-  return r;
-}
-
-// Step 1, candidate c: refreshes w with block (c + 1) >> 2 when c + 1 is its first word.
-ESR_HD inline int32_t warp_candidate(const uint32_t key[2], uint32_t step, uint32_t t, int c, uint32_t ni, uint32_t w[4]) {
-  const int word = (c + 1) & 3;
-  if (word == 0) {
-    const uint32_t counter[4] = {t, step, (uint32_t)(c + 1) >> 2, 0u};
-    philox4x32_10(counter, key, w);
-  }
-  const uint32_t v = word == 0 ? w[0] : (word == 1 ? w[1] : (word == 2 ? w[2] : w[3]));  // (no runtime-indexed array)
-  return (int32_t)(((uint64_t)v * ni) >> 32);
-}
-
-// Step 2, one lane's chain over its four elements.
+// Step 1 is bpr_pick_pair and bpr_candidate (esr_bpr_sample.h).  Step 2, one lane's chain over its four elements:
 ESR_HD inline float warp_lane_dot(float x0, float x1, float x2, float x3, float y0, float y1, float y2, float y3) {
-  float acc = fmaf(x0, y0, 0.f);
-  acc = fmaf(x1, y1, acc);
-  acc = fmaf(x2, y2, acc);
-  return fmaf(x3, y3, acc);
+  return row4_chain(x0, x1, x2, x3, y0, y1, y2, y3, 0.f);
 }
 
 // Step 4, the rank estimate of a valid slot (N >= 1): in [1, max(1, ni)], an index into rank_weight[ni + 1].
@@ -118,7 +80,7 @@ ESR_HD inline WarpSlot warp_slot(const float* user_table, int64_t nu, const floa
                           float reg, float* grads3) {
   const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
   uint32_t w[4];
-  const WarpPair pr = warp_pick_pair(row_offsets, row_upos, row_ipos, nu, nnz, key, step, t, w);
+  const BprPair pr = bpr_pick_pair(row_offsets, row_upos, row_ipos, nu, nnz, key, step, t, w);
   WarpSlot r;
   r.u = pr.u;
   r.i = pr.i;
@@ -132,7 +94,7 @@ ESR_HD inline WarpSlot warp_slot(const float* user_table, int64_t nu, const floa
   const float *x = user_table + (int64_t)pr.u * D, *yi = item_table + (int64_t)pr.i * D, *yj = yi;
   r.s_i = warp_row_dot(x, yi, D);
   for (int c = 0; c < max_trials; ++c) {
-    r.j = warp_candidate(key, step, t, c, ni, w);
+    r.j = bpr_candidate(key, step, t, c, ni, w);
     if (bpr_row_has(row_ipos, pr.lo, pr.hi, r.j)) continue;
     r.trials += 1;
     yj = item_table + (int64_t)r.j * D;

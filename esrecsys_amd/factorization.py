@@ -38,7 +38,10 @@ users the model never saw.  ``SGNS`` (the last class) has no users at all: skip-
 
 All of them derive from ``_Factorization`` (device, indexed pairs, ``score`` / ``recommend`` / ``from_documents`` and
 ``diversify``, the MMR re-ranking of ``rerank.py`` applied to ``recommend``'s lists); ``_ALS`` holds
-what the two alternating models share, ``BPR`` the step tail and the update of the three triple models.
+what the two alternating models share, ``_SampledSGD`` what the five models trained by sampled SGD share (the
+hyper-parameters, the seeded tables, the row-sparse update, the tail of ``train_steps``, ``fit``); ``BPR`` adds the seen
+pairs and the triple step that ``WARP``, ``HybridBPR`` and ``FPMC`` build on, and ``_Sequences`` holds the event CSR and
+the serving of given sequences for ``FPMC`` and ``SGNS``.
 """
 import math
 
@@ -131,6 +134,7 @@ class _Factorization:
         users, upos = torch.unique(user, return_inverse=True)
         items, ipos = torch.unique(item, return_inverse=True)
         self.users, self.items = users.to(torch.int32).contiguous(), items.to(torch.int32).contiguous()
+        self._failed = torch.zeros(1, dtype=torch.int32, device=self.device)     # the failure word of every kernel call
         return user, upos, ipos
 
     def _set_pairs(self, key, user_offsets):
@@ -138,7 +142,6 @@ class _Factorization:
         self._key, self._user_offsets = key, user_offsets
         self._row_upos = (key >> 32).to(torch.int32).contiguous()
         self._row_ipos = (key & 0xFFFFFFFF).to(torch.int32).contiguous()
-        self._failed = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def _raise_bad_position(self, what):
         """Reads the failure word; bit 30 raises ``FactorizationError(what)``."""
@@ -624,30 +627,10 @@ def _step_means(sums, counts):
     return [float(s) / int(n) if n else float("nan") for s, n in zip(sums, counts)]
 
 
-class BPR(_Factorization):
-    """Matrix factorisation trained on the ranking itself (Rendle, Freudenthaler, Gantner, Schmidt-Thieme, UAI 2009).
-
-        model = BPR.from_documents(indices, doc_offsets, rank=64)       # user = document, a repeated id is one seen pair
-        losses = model.fit(steps=2000)                                  # the mean loss of every step
-        rec_ids, rec_scores, rec_lengths = model.recommend(users, k=500)     # straight into evaluate.ranking_metrics
-
-    Step.  ``batch`` triples (user u, seen item i, unseen item j) are drawn on the device (``ops.bpr_sample``: Philox keyed
-    by ``seed``, a function of (seed, step, slot) and the seen pairs alone; a triple whose 15 candidates were all seen is
-    dropped: ``valid = 0``).  The objective of a step is the sum over its valid triples of ``softplus(-d) + (reg / 2)
-    (|x_u|^2 + |y_i|^2 + |y_j|^2)``, ``d = x_u . y_i - x_u . y_j``.  ``ops.bpr_fwd_bwd`` writes one gradient row per
-    occurrence; rows of a repeated id add (the engine's segment sum in a fixed order: Rendle's per-triple SGD taken as a
-    minibatch) and the row-sparse engine applies Adagrad (``ops.sparse_adagrad_multi`` over both tables at once) or SGD
-    (``ops.sparse_sgd``, users then items).  The fit is a function of the inputs and the seed.
-
-    ``users`` / ``items``: int32 ascending ids; ``user_factors`` / ``item_factors``: float32 [nu, rank] / [ni, rank], both
-    ``randn * init_scale`` from the seeded CPU generator (users first); ``step``: the steps taken so far."""
-
-    def __init__(self, user, item, rank=64, reg=0.01, lr=0.05, optimizer="adagrad", batch=65536, seed=0, init_scale=None,
-                 device=None):
-        user, item = self._configure(user, item, rank, reg, lr, optimizer, batch, seed, init_scale, device)
-        with torch.cuda.device(self.device):
-            nu, ni = self._index_seen(user, item)
-            self._init_tables(nu, ni)
+class _SampledSGD(_Factorization):
+    """What the models trained by sampled SGD through the row-sparse engine share (``BPR`` and its subclasses, ``SGNS``):
+    the hyper-parameters, the seeded tables with their Adagrad accumulators, the update, the tail of ``train_steps`` and
+    ``fit``.  A subclass provides ``sample`` and ``train_steps``."""
 
     def _configure(self, user, item, rank, reg, lr, optimizer, batch, seed, init_scale, device):
         """The checks that need no device, then the hyper-parameters as attributes; returns the flat (user, item) tensors."""
@@ -676,19 +659,6 @@ class BPR(_Factorization):
         self.step = 0
         return user, item
 
-    def _index_seen(self, user, item):
-        """users / items, the CSR of the seen pairs on the host and on the device; returns (nu, ni)."""
-        _, upos, ipos = self._index_pairs(user, item)
-        return self._set_seen(upos, ipos)
-
-    def _set_seen(self, upos, ipos):
-        """The CSR of the seen pairs of the events (upos, ipos) on the host and on the device; returns (nu, ni)."""
-        nu = int(self.users.numel())
-        key = torch.unique((upos << 32) | ipos)                     # repeated events collapse to one seen pair
-        self._set_pairs(key, _host_offsets(torch.bincount(key >> 32, minlength=nu)))
-        self._offsets_dev = torch.from_numpy(self._user_offsets).to(self.device)    # the sampler reads the CSR on the device
-        return nu, int(self.items.numel())
-
     def _new_tables(self, *rows):
         """(a table [n, rank] per entry of `rows`, then their Adagrad accumulators): ``randn * init_scale`` from the seeded
         CPU generator in the order given (users first)."""
@@ -697,19 +667,9 @@ class BPR(_Factorization):
         tables = [(torch.randn(n, rank, generator=gen) * self.init_scale).to(dev).contiguous() for n in rows]
         return tuple(tables) + tuple(torch.full((n, rank), ADAGRAD_INIT, dtype=torch.float32, device=dev) for n in rows)
 
-    def _init_tables(self, nu, ni):
-        self.user_factors, self.item_factors, self.user_accum, self.item_accum = self._new_tables(nu, ni)
-
-    nnz = property(lambda self: int(self._key.numel()))
-
-    # ---- training -------------------------------------------------------------------------------------------------------
-    def sample(self, K, step0=None, seed=None):
-        """(u, i, j, valid) int32 [K, batch] and dropped int32[K]: the triples of the global steps step0 .. step0 + K - 1
-        (``step0`` = the next step to take when None) as positions into ``users`` / ``items``."""
-        with torch.cuda.device(self.device):
-            return ops.bpr_sample(self._offsets_dev, self._row_upos, self._row_ipos, self.users.numel(), self.items.numel(),
-                                  self.seed if seed is None else int(seed), self.step if step0 is None else int(step0),
-                                  int(K), self.batch)
+    def _stream(self, seed, step0):
+        """(seed, first step) of a ``sample`` call: the model's seed and the next step to take where None."""
+        return self.seed if seed is None else int(seed), self.step if step0 is None else int(step0)
 
     def _apply(self, tables, accums, ids, bounds, grads, table_of=None):
         """One update of the tables (rows [bounds[n], bounds[n + 1]) of the stacked row space) through the row-sparse engine:
@@ -732,11 +692,6 @@ class BPR(_Factorization):
                 ops.sparse_sgd(table, sorted_ids, perm, grads[at:at + count], self.lr)
             at += count
 
-    def _update(self, u, i, j, grads):
-        nu, ni = int(self.users.numel()), int(self.items.numel())
-        self._apply([self.user_factors, self.item_factors], [self.user_accum, self.item_accum], [u, i, j], [0, nu, nu + ni],
-                    grads)
-
     def _run_steps(self, K, what, one_step, rows=1):
         """The tail every ``train_steps`` shares: the failure word zeroed, ``one_step(k)`` = the `rows` fp64 device scalars
         of step k for k < K, ``step += K``, the word read (`what` words its refusal).  Returns float64[rows, K] on the host."""
@@ -756,6 +711,77 @@ class BPR(_Factorization):
             raise ValueError("K = %d below 1" % K)
         return K
 
+    def fit(self, steps):
+        """`steps` steps in groups of 64 (one sampler launch per group); returns every step's mean loss."""
+        losses, steps = [], int(steps)
+        for a in range(0, steps, FIT_GROUP):
+            losses += self.train_steps(min(FIT_GROUP, steps - a))
+        return losses
+
+    @staticmethod
+    def _ordered_share(d, mask):
+        """The share of the differences `d` under `mask` that are positive, a tie counting half; NaN under an empty mask."""
+        n = int(mask.sum())
+        wins, ties = int(((d > 0) & mask).sum()), int(((d == 0) & mask).sum())
+        return (wins + 0.5 * ties) / n if n else float("nan")
+
+
+class BPR(_SampledSGD):
+    """Matrix factorisation trained on the ranking itself (Rendle, Freudenthaler, Gantner, Schmidt-Thieme, UAI 2009).
+
+        model = BPR.from_documents(indices, doc_offsets, rank=64)       # user = document, a repeated id is one seen pair
+        losses = model.fit(steps=2000)                                  # the mean loss of every step
+        rec_ids, rec_scores, rec_lengths = model.recommend(users, k=500)     # straight into evaluate.ranking_metrics
+
+    Step.  ``batch`` triples (user u, seen item i, unseen item j) are drawn on the device (``ops.bpr_sample``: Philox keyed
+    by ``seed``, a function of (seed, step, slot) and the seen pairs alone; a triple whose 15 candidates were all seen is
+    dropped: ``valid = 0``).  The objective of a step is the sum over its valid triples of ``softplus(-d) + (reg / 2)
+    (|x_u|^2 + |y_i|^2 + |y_j|^2)``, ``d = x_u . y_i - x_u . y_j``.  ``ops.bpr_fwd_bwd`` writes one gradient row per
+    occurrence; rows of a repeated id add (the engine's segment sum in a fixed order: Rendle's per-triple SGD taken as a
+    minibatch) and the row-sparse engine applies Adagrad (``ops.sparse_adagrad_multi`` over both tables at once) or SGD
+    (``ops.sparse_sgd``, users then items).  The fit is a function of the inputs and the seed.
+
+    ``users`` / ``items``: int32 ascending ids; ``user_factors`` / ``item_factors``: float32 [nu, rank] / [ni, rank], both
+    ``randn * init_scale`` from the seeded CPU generator (users first); ``step``: the steps taken so far."""
+
+    def __init__(self, user, item, rank=64, reg=0.01, lr=0.05, optimizer="adagrad", batch=65536, seed=0, init_scale=None,
+                 device=None):
+        user, item = self._configure(user, item, rank, reg, lr, optimizer, batch, seed, init_scale, device)
+        with torch.cuda.device(self.device):
+            nu, ni = self._index_seen(user, item)
+            self._init_tables(nu, ni)
+
+    def _index_seen(self, user, item):
+        """users / items, the CSR of the seen pairs on the host and on the device; returns (nu, ni)."""
+        _, upos, ipos = self._index_pairs(user, item)
+        return self._set_seen(upos, ipos)
+
+    def _set_seen(self, upos, ipos):
+        """The CSR of the seen pairs of the events (upos, ipos) on the host and on the device; returns (nu, ni)."""
+        nu = int(self.users.numel())
+        key = torch.unique((upos << 32) | ipos)                     # repeated events collapse to one seen pair
+        self._set_pairs(key, _host_offsets(torch.bincount(key >> 32, minlength=nu)))
+        self._offsets_dev = torch.from_numpy(self._user_offsets).to(self.device)    # the sampler reads the CSR on the device
+        return nu, int(self.items.numel())
+
+    def _init_tables(self, nu, ni):
+        self.user_factors, self.item_factors, self.user_accum, self.item_accum = self._new_tables(nu, ni)
+
+    nnz = property(lambda self: int(self._key.numel()))
+
+    # ---- training -------------------------------------------------------------------------------------------------------
+    def sample(self, K, step0=None, seed=None):
+        """(u, i, j, valid) int32 [K, batch] and dropped int32[K]: the triples of the global steps step0 .. step0 + K - 1
+        (``step0`` = the next step to take when None) as positions into ``users`` / ``items``."""
+        with torch.cuda.device(self.device):
+            return ops.bpr_sample(self._offsets_dev, self._row_upos, self._row_ipos, self.users.numel(), self.items.numel(),
+                                  *self._stream(seed, step0), int(K), self.batch)
+
+    def _update(self, u, i, j, grads):
+        nu, ni = int(self.users.numel()), int(self.items.numel())
+        self._apply([self.user_factors, self.item_factors], [self.user_accum, self.item_accum], [u, i, j], [0, nu, nu + ni],
+                    grads)
+
     def train_steps(self, K):
         """K steps: one sampler launch, then per step the forward / backward, the sort and the update.  Returns the mean
         loss over the valid triples of every step (an fp64 sum of the per-triple losses divided on the host; NaN for a step
@@ -772,13 +798,6 @@ class BPR(_Factorization):
             sums = self._run_steps(K, "a BPR step met a position outside its table (bit 30)", one_step)
             return _step_means(sums[0], self.batch - dropped.cpu().numpy().astype(np.int64))
 
-    def fit(self, steps):
-        """`steps` steps in groups of 64 (one sampler launch per group); returns every step's mean loss."""
-        losses, steps = [], int(steps)
-        for a in range(0, steps, FIT_GROUP):
-            losses += self.train_steps(min(FIT_GROUP, steps - a))
-        return losses
-
     def auc(self, K=1, seed=None):
         """The fraction of K * batch sampled triples (valid ones) that the model orders correctly, ``d > 0``; a tie counts
         half.  The triples are steps 0 .. K - 1 of `seed` (``self.seed + 1`` when None: not a training stream, and the same
@@ -789,10 +808,7 @@ class BPR(_Factorization):
             _, d, _ = ops.bpr_fwd_bwd(self.user_factors, self.item_factors, u.reshape(-1), i.reshape(-1), j.reshape(-1),
                                       valid.reshape(-1), self.reg, want_grads=False, want_diff=True, failed=self._failed)
             self._raise_bad_position("auc met a position outside its table (bit 30)")
-            ok = valid.reshape(-1) != 0
-            n = int(ok.sum())
-            wins, ties = int(((d > 0) & ok).sum()), int(((d == 0) & ok).sum())
-        return (wins + 0.5 * ties) / n if n else float("nan")
+            return self._ordered_share(d, valid.reshape(-1) != 0)
 
 
 # ---- WARP ---------------------------------------------------------------------------------------------------------------
@@ -1182,7 +1198,56 @@ def _tail_bags(ipos, offsets, window, dev):
     return _Bags(bag_offsets, feat, weight, dev)
 
 
-class FPMC(BPR):
+class _Sequences:
+    """What the two models over id sequences (``FPMC``, ``SGNS``) share: the events as a CSR by sequence -- ``users`` names
+    the sequences -- and the serving of sequences given at query time."""
+
+    def _set_sequences(self, upos, ipos, time):
+        """The CSR of the events by sequence on the host and the device (``_seq_offsets``, ``_seq_upos`` / ``_seq_ipos``):
+        a sequence's events in the order given, or by (time, order given).  Returns ipos int64 in the CSR's order."""
+        dev = self.device
+        if upos.numel() > 2 ** 31 - 1:
+            raise ValueError("%d events exceed 2^31 - 1" % upos.numel())
+        order = torch.arange(upos.numel(), device=dev) if time is None else torch.sort(time.to(dev), stable=True).indices
+        order = order[torch.sort(upos[order], stable=True).indices]
+        self._seq_offsets = _host_offsets(torch.bincount(upos, minlength=int(self.users.numel())))
+        self._seq_offsets_dev = torch.from_numpy(self._seq_offsets).to(dev)
+        self._seq_upos = upos[order].to(torch.int32).contiguous()
+        self._seq_ipos = ipos[order].to(torch.int32).contiguous()
+        return ipos[order]
+
+    n_events = property(lambda self: int(self._seq_ipos.numel()))
+
+    def _known_sequences(self, indices, doc_offsets):
+        """(docs, ipos int64 on the device, host offsets) of the given sequences ``indices[doc_offsets[d]:doc_offsets[d +
+        1]]``, reduced to the ids the model knows (the others are skipped)."""
+        ids, off = _ids_and_offsets(indices, doc_offsets, self.device)
+        ndocs = off.size - 1
+        docs = torch.from_numpy(np.repeat(np.arange(ndocs, dtype=np.int64), np.diff(off))).to(self.device)
+        ipos = self._positions(ids, self.items).to(torch.int64)
+        known = ipos >= 0
+        docs, ipos = docs[known], ipos[known]
+        return docs, ipos, _host_offsets(torch.bincount(docs, minlength=ndocs))
+
+    def _bag_rows(self, table, bags, n, what):
+        """float32[n, rank]: ``ops.bag_sum`` of every bag of `bags` (``_tail_bags``) over `table`; zeros without bags."""
+        if bags is None:
+            return torch.zeros((n, self.rank), dtype=torch.float32, device=self.device)
+        self._failed.zero_()
+        rows = ops.bag_sum(table, *bags.args(), failed=self._failed)
+        self._raise_bad_position("a %s names an item position outside the table (bit 30)" % what)
+        return rows
+
+    def _recommend_sequences(self, queries, item_rows, docs, ipos, k, slack, exclude_seen):
+        """``_recommend_rows`` of one query row per given sequence; `exclude_seen` leaves out the sequence's own items."""
+        ndocs = int(queries.shape[0])
+        key = torch.unique((docs << 32) | ipos)
+        seen_offsets = _host_offsets(torch.bincount(key >> 32, minlength=ndocs)) if exclude_seen else None
+        return _recommend_rows(queries, None, torch.arange(ndocs, dtype=torch.int64, device=self.device), item_rows,
+                               self.items, k, slack, seen_offsets, key, lambda q: "sequence %d" % q, "holds", "exclude_seen")
+
+
+class FPMC(_Sequences, BPR):
     """The Factorised Personalised Markov Chain (Rendle, Freudenthaler, Schmidt-Thieme, WWW 2010) trained with the BPR step:
     BPR's user-item term plus a factorised transition term from the items just consumed -- "what comes next".
 
@@ -1229,24 +1294,13 @@ class FPMC(BPR):
             nu, ni = self._set_seen(upos, ipos)
             if nu + 3 * ni > 2 ** 31 - 1:
                 raise ValueError("nu + 3 ni = %d rows exceed 2^31 - 1 (the row space of the update)" % (nu + 3 * ni))
-            if upos.numel() > 2 ** 31 - 1:
-                raise ValueError("%d events exceed 2^31 - 1" % upos.numel())
-            # the sequences: a CSR by user, the events of a user in the order given or by (time, order given)
-            order = torch.arange(upos.numel(), device=dev) if time is None else torch.sort(time.to(dev), stable=True).indices
-            order = order[torch.sort(upos[order], stable=True).indices]
-            self._seq_offsets = _host_offsets(torch.bincount(upos, minlength=nu))
-            self._seq_offsets_dev = torch.from_numpy(self._seq_offsets).to(dev)
-            self._seq_upos = upos[order].to(torch.int32).contiguous()
-            self._seq_ipos = ipos[order].to(torch.int32).contiguous()
-            self._tails = _tail_bags(ipos[order], self._seq_offsets, window, dev)
+            self._tails = _tail_bags(self._set_sequences(upos, ipos, time), self._seq_offsets, window, dev)
             self._init_tables(nu, ni)
 
     def _init_tables(self, nu, ni):
         (self.user_factors, self.item_factors, self.next_factors, self.prev_factors, self.user_accum, self.item_accum,
          self.next_accum, self.prev_accum) = self._new_tables(nu, ni, ni, ni)
         self._served = None
-
-    n_events = property(lambda self: int(self._seq_ipos.numel()))
 
     # ---- training -------------------------------------------------------------------------------------------------------
     def sample(self, K, step0=None, seed=None):
@@ -1255,9 +1309,8 @@ class FPMC(BPR):
         in the sequence CSR and c its context length."""
         with torch.cuda.device(self.device):
             return ops.fpmc_sample(self._seq_offsets_dev, self._seq_upos, self._seq_ipos, self._offsets_dev, self._row_ipos,
-                                   self.users.numel(), self.items.numel(), self.window,
-                                   self.seed if seed is None else int(seed), self.step if step0 is None else int(step0),
-                                   int(K), self.batch)
+                                   self.users.numel(), self.items.numel(), self.window, *self._stream(seed, step0), int(K),
+                                   self.batch)
 
     def _tables(self):
         return [self.user_factors, self.item_factors, self.next_factors, self.prev_factors]
@@ -1305,21 +1358,9 @@ class FPMC(BPR):
             _, d, _, _ = ops.fpmc_fwd_bwd(*self._tables(), self._seq_ipos, u, e, c, i, j, valid, self.reg, want_grads=False,
                                           want_diff=True, failed=self._failed)
             self._raise_bad_position("auc met a position outside its table (bit 30)")
-            ok = valid != 0
-            n = int(ok.sum())
-            wins, ties = int(((d > 0) & ok).sum()), int(((d == 0) & ok).sum())
-        return (wins + 0.5 * ties) / n if n else float("nan")
+            return self._ordered_share(d, valid != 0)
 
     # ---- serving --------------------------------------------------------------------------------------------------------
-    def _context_rows(self, bags, n):
-        """float32[n, rank]: ``ops.bag_sum`` of every bag of `bags` over ``prev_factors`` (zeros without bags)."""
-        if bags is None:
-            return torch.zeros((n, self.rank), dtype=torch.float32, device=self.device)
-        self._failed.zero_()
-        m = ops.bag_sum(self.prev_factors, *bags.args(), failed=self._failed)
-        self._raise_bad_position("a context names an item position outside the table (bit 30)")
-        return m
-
     def _rows(self):
         top = predict_max_rank()
         if 2 * self.rank > top:
@@ -1335,7 +1376,7 @@ class FPMC(BPR):
         the context of the event that would follow u's training sequence: its last ``min(length, window)`` items by
         ``ops.bag_sum`` with the weights ``float32(1 / c)``, the chain the step kernel walks.  An unknown user gets NaN."""
         with torch.cuda.device(self.device):
-            m = self._context_rows(self._tails, int(self.users.numel()))
+            m = self._bag_rows(self.prev_factors, self._tails, int(self.users.numel()), "context")
             rows = torch.cat([self.user_factors, m], 1)
             if users is None:
                 return rows.contiguous()
@@ -1354,27 +1395,18 @@ class FPMC(BPR):
         pure session-based recommendation by the transition term.  `exclude_seen` leaves out the sequence's own items.
         Returns (rec_ids, rec_scores, rec_lengths), what ``evaluate.ranking_metrics`` takes; with a known user's training
         sequence the lists are ``recommend``'s."""
-        ids, off = _ids_and_offsets(indices, doc_offsets, self.device)
-        ndocs, dev = off.size - 1, self.device
-        with torch.cuda.device(dev):
+        with torch.cuda.device(self.device):
+            docs, ipos, offsets = self._known_sequences(indices, doc_offsets)
+            ndocs = offsets.size - 1
             item_rows = self._rows()[1]
-            docs = torch.from_numpy(np.repeat(np.arange(ndocs, dtype=np.int64), np.diff(off))).to(dev)
-            ipos = self._positions(ids, self.items).to(torch.int64)
-            known = ipos >= 0
-            docs, ipos = docs[known], ipos[known]
-            offsets = _host_offsets(torch.bincount(docs, minlength=ndocs))
-            m = self._context_rows(_tail_bags(ipos, offsets, self.window, dev), ndocs)
+            m = self._bag_rows(self.prev_factors, _tail_bags(ipos, offsets, self.window, self.device), ndocs, "context")
             half = torch.zeros_like(m)
             if users is not None:
                 upos = self._positions(users, self.users).to(torch.int64)
                 if upos.numel() != ndocs:
                     raise ValueError("users must name one user per sequence")
                 half = torch.where((upos >= 0)[:, None], self.user_factors[upos.clamp(min=0)], half)
-            key = torch.unique((docs << 32) | ipos)
-            seen_offsets = _host_offsets(torch.bincount(key >> 32, minlength=ndocs)) if exclude_seen else None
-            return _recommend_rows(torch.cat([half, m], 1).contiguous(), None, torch.arange(ndocs, dtype=torch.int64, device=dev),
-                                   item_rows, self.items, k, slack, seen_offsets, key, lambda q: "sequence %d" % q, "holds",
-                                   "exclude_seen")
+            return self._recommend_sequences(torch.cat([half, m], 1).contiguous(), item_rows, docs, ipos, k, slack, exclude_seen)
 
 
 # ---- skip-gram with negative sampling ------------------------------------------------------------------------------------
@@ -1442,7 +1474,7 @@ def sgns_alias_table(masses):
     return np.array(keep, np.uint32), np.array(alias, np.int32)
 
 
-class SGNS(BPR):
+class SGNS(_Sequences, _SampledSGD):
     """Skip-gram with negative sampling (Mikolov, Sutskever, Chen, Corrado, Dean, NIPS 2013): word2vec for token streams,
     item2vec / prod2vec (Barkan and Koenigstein 2016; Grbovic et al. 2015) for playlists, baskets and sessions -- item
     vectors trained straight from id sequences, without users and without a co-occurrence matrix.
@@ -1463,7 +1495,7 @@ class SGNS(BPR):
     on the host by ``sgns_alias_table``).  The objective of a step is the sum over its valid slots of
     ``softplus(-v_c . w_o) + sum_k m_k softplus(v_c . w_n_k) + (reg / 2)(|v_c|^2 + |w_o|^2 + sum_k m_k |w_n_k|^2)``,
     ``m_k = 0`` where the noise item is the context itself (word2vec skips that draw).  ``ops.sgns_fwd_bwd`` writes one
-    gradient row per occurrence and the row-sparse engine updates both tables (``BPR._apply``).  The reported loss is the
+    gradient row per occurrence and the row-sparse engine updates both tables (``_SampledSGD._apply``).  The reported loss is the
     logistic part, as in the other models of this module.  The fit is a function of the inputs and the seed.
     Frequent-item subsampling (Mikolov's threshold t) is out of scope: every event is a centre with equal probability.
 
@@ -1495,24 +1527,14 @@ class SGNS(BPR):
             nd, ni = int(self.users.numel()), int(self.items.numel())
             if 2 * ni > 2 ** 31 - 1:
                 raise ValueError("2 ni = %d rows exceed 2^31 - 1 (the row space of the update)" % (2 * ni))
-            if upos.numel() > 2 ** 31 - 1:
-                raise ValueError("%d events exceed 2^31 - 1" % upos.numel())
-            # the documents: a CSR in the order given or by (time, order given), as FPMC's sequences
-            order = torch.arange(upos.numel(), device=dev) if time is None else torch.sort(time.to(dev), stable=True).indices
-            order = order[torch.sort(upos[order], stable=True).indices]
-            self._seq_offsets = _host_offsets(torch.bincount(upos, minlength=nd))
-            self._seq_offsets_dev = torch.from_numpy(self._seq_offsets).to(dev)
-            self._seq_upos = upos[order].to(torch.int32).contiguous()
-            self._seq_ipos = ipos[order].to(torch.int32).contiguous()
+            self._set_sequences(upos, ipos, time)
             self.counts = torch.bincount(ipos, minlength=ni)
             keep, alias = sgns_alias_table(sgns_noise_masses(self.counts.cpu().numpy(), power))
             self.noise_keep = torch.from_numpy(keep.view(np.int32)).to(dev)
             self.noise_alias = torch.from_numpy(alias).to(dev)
-            self._failed = torch.zeros(1, dtype=torch.int32, device=dev)
             self.in_factors, self.out_factors, self.in_accum, self.out_accum = self._new_tables(ni, ni)
 
-    n_events = property(lambda self: int(self._seq_ipos.numel()))
-    nnz = n_events
+    nnz = _Sequences.n_events
 
     def _rows(self):
         return self.in_factors, self.out_factors
@@ -1530,8 +1552,7 @@ class SGNS(BPR):
         with torch.cuda.device(self.device):
             return ops.sgns_sample(self._seq_offsets_dev, self._seq_upos, self._seq_ipos, self.users.numel(),
                                    self.items.numel(), self.window, self.negatives, self.noise_keep, self.noise_alias,
-                                   self.seed if seed is None else int(seed), self.step if step0 is None else int(step0),
-                                   int(K), self.batch)
+                                   *self._stream(seed, step0), int(K), self.batch)
 
     def train_steps(self, K):
         """K steps: one sampler launch, then per step the forward / backward, the sort and the update over both tables.
@@ -1566,11 +1587,7 @@ class SGNS(BPR):
             _, s, _ = ops.sgns_fwd_bwd(self.in_factors, self.out_factors, c, o, neg, valid, self.reg, want_grads=False,
                                        want_diff=True, failed=self._failed)
             self._raise_bad_position("accuracy met a position outside its table (bit 30)")
-            pair = (valid != 0)[:, None] & (neg != o[:, None])
-            d = s[:, :1] - s[:, 1:]
-            n = int(pair.sum())
-            wins, ties = int(((d > 0) & pair).sum()), int(((d == 0) & pair).sum())
-        return (wins + 0.5 * ties) / n if n else float("nan")
+            return self._ordered_share(s[:, :1] - s[:, 1:], (valid != 0)[:, None] & (neg != o[:, None]))
 
     # ---- serving --------------------------------------------------------------------------------------------------------
     def item_rows(self, which="in", normalize=False):
@@ -1596,32 +1613,15 @@ class SGNS(BPR):
                                    np.arange(ni + 1, dtype=np.int64) if exclude_self else None, (own << 32) | own,
                                    lambda q: "item %d" % int(_tensor(items, "items")[q]), "is", "exclude_self")
 
-    def _sequences(self, indices, doc_offsets):
-        """(docs, ipos int64 on the device -- the ids the model knows, the others skipped -- and the host offsets)"""
-        ids, off = _ids_and_offsets(indices, doc_offsets, self.device)
-        ndocs = off.size - 1
-        docs = torch.from_numpy(np.repeat(np.arange(ndocs, dtype=np.int64), np.diff(off))).to(self.device)
-        ipos = self._positions(ids, self.items).to(torch.int64)
-        known = ipos >= 0
-        docs, ipos = docs[known], ipos[known]
-        return docs, ipos, _host_offsets(torch.bincount(docs, minlength=ndocs))
-
     def _query_rows(self, ipos, offsets):
-        ndocs = offsets.size - 1
-        bags = _tail_bags(ipos, offsets, self.window, self.device)
-        if bags is None:
-            return torch.zeros((ndocs, self.rank), dtype=torch.float32, device=self.device)
-        self._failed.zero_()
-        rows = ops.bag_sum(self.in_factors, *bags.args(), failed=self._failed)
-        self._raise_bad_position("a sequence names an item position outside the table (bit 30)")
-        return rows
+        return self._bag_rows(self.in_factors, _tail_bags(ipos, offsets, self.window, self.device), offsets.size - 1, "sequence")
 
     def query_rows(self, indices, doc_offsets):
         """float32[ndocs, rank]: per sequence ``indices[doc_offsets[d]:doc_offsets[d + 1]]`` the mean of the ``in`` rows of
         its last ``window`` ids that the model knows (unknown ids are skipped): ``ops.bag_sum`` with the weights
         ``float32(1 / c)``, oldest first.  A sequence without a known id gets zeros."""
         with torch.cuda.device(self.device):
-            _, ipos, offsets = self._sequences(indices, doc_offsets)
+            _, ipos, offsets = self._known_sequences(indices, doc_offsets)
             return self._query_rows(ipos, offsets)
 
     def recommend_sequences(self, indices, doc_offsets, k=500, exclude_seen=True, slack=16):
@@ -1630,11 +1630,6 @@ class SGNS(BPR):
         skipped, as ``FPMC.recommend_sequences`` skips them.  `exclude_seen` leaves out the sequence's own items.  Returns
         (rec_ids, rec_scores, rec_lengths), what ``evaluate.ranking_metrics`` and ``diversify`` take."""
         with torch.cuda.device(self.device):
-            docs, ipos, offsets = self._sequences(indices, doc_offsets)
-            ndocs = offsets.size - 1
-            queries = self._query_rows(ipos, offsets)
-            key = torch.unique((docs << 32) | ipos)
-            seen_offsets = _host_offsets(torch.bincount(key >> 32, minlength=ndocs)) if exclude_seen else None
-            return _recommend_rows(queries, None, torch.arange(ndocs, dtype=torch.int64, device=self.device),
-                                   self.out_factors, self.items, k, slack, seen_offsets, key, lambda q: "sequence %d" % q,
-                                   "holds", "exclude_seen")
+            docs, ipos, offsets = self._known_sequences(indices, doc_offsets)
+            return self._recommend_sequences(self._query_rows(ipos, offsets), self.out_factors, docs, ipos, k, slack,
+                                             exclude_seen)

@@ -2045,12 +2045,37 @@ def _check_device_csr(who, name, offsets, row_upos, row_ipos, nu, **sizes):
     return nnz
 
 
+def _geometry(name, n):
+    """The n ints esr_<name>_geometry() fills, as a tuple."""
+    out = [ctypes.c_int(0) for _ in range(n)]
+    check(getattr(_lib.load(), "esr_%s_geometry" % name)(*[ctypes.byref(v) for v in out]), "esr_%s_geometry" % name)
+    return tuple(int(v.value) for v in out)
+
+
+def _check_valid(valid, n, per, who=""):
+    """valid is None (all valid) or int32[n]."""
+    if valid is not None:
+        _req(valid, torch.int32, "valid")
+        if valid.numel() != n:
+            raise ValueError("%svalid must hold one entry per %s" % (who, per))
+
+
+def _sample_outputs(n, K, B, dev):
+    """(the n id planes int32[n, K, B] of a sampler, dropped int32[K])"""
+    return torch.empty((n, K, B), dtype=torch.int32, device=dev), torch.empty(K, dtype=torch.int32, device=dev)
+
+
+def _step_outputs(B, rows, D, dev, want_grads, want_diff, scores=None):
+    """(loss_t float32[B], diff_t float32[B] -- [B, scores] with `scores` -- or None, grads float32[rows, D] or None)"""
+    loss_t = torch.empty(B, dtype=torch.float32, device=dev)
+    diff_t = torch.empty(B if scores is None else (B, scores), dtype=torch.float32, device=dev) if want_diff else None
+    return loss_t, diff_t, torch.empty((rows, D), dtype=torch.float32, device=dev) if want_grads else None
+
+
 def bpr_geometry():
     """(max_tries, max_rank, rank_multiple): the negative candidates the sampler tries per triple; bpr_fwd_bwd takes a rank
     that is a multiple of rank_multiple and at most max_rank."""
-    tries, rank, mult = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-    check(_lib.load().esr_bpr_geometry(ctypes.byref(tries), ctypes.byref(rank), ctypes.byref(mult)), "esr_bpr_geometry")
-    return int(tries.value), int(rank.value), int(mult.value)
+    return _geometry("bpr", 3)
 
 
 def bpr_sample(row_offsets, row_upos, row_ipos, nu, ni, seed, step0, K, B):
@@ -2062,8 +2087,7 @@ def bpr_sample(row_offsets, row_upos, row_ipos, nu, ni, seed, step0, K, B):
     lib = _lib.load()
     nu, ni, K, B = int(nu), int(ni), int(K), int(B)
     nnz = _check_device_csr("bpr_sample", "row_offsets", row_offsets, row_upos, row_ipos, nu, ni=ni, K=K, B=B)
-    out = torch.empty((4, K, B), dtype=torch.int32, device=row_upos.device)
-    dropped = torch.empty(K, dtype=torch.int32, device=row_upos.device)
+    out, dropped = _sample_outputs(4, K, B, row_upos.device)
     check(lib.esr_bpr_sample(_p(row_offsets), _p(row_upos), _p(row_ipos), nu, ni, nnz, int(seed) & (2 ** 64 - 1),
                              int(step0) & 0xFFFFFFFF, K, B, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _p(dropped),
                              _stream()), "esr_bpr_sample")
@@ -2084,16 +2108,11 @@ def bpr_fwd_bwd(user_table, item_table, u, i, j, valid, reg, want_grads=True, wa
     B, D = u.numel(), int(user_table.shape[1])
     if i.numel() != B or j.numel() != B:
         raise ValueError("u, i and j must have one length")
-    if valid is not None:
-        _req(valid, torch.int32, "valid")
-        if valid.numel() != B:
-            raise ValueError("valid must hold one entry per triple")
+    _check_valid(valid, B, "triple")
     _check_rank4(D, *bpr_geometry()[1:])
     dev = user_table.device
     failed = _failed_word(failed, dev)
-    loss_t = torch.empty(B, dtype=torch.float32, device=dev)
-    diff_t = torch.empty(B, dtype=torch.float32, device=dev) if want_diff else None
-    grads = torch.empty((3 * B, D), dtype=torch.float32, device=dev) if want_grads else None
+    loss_t, diff_t, grads = _step_outputs(B, 3 * B, D, dev, want_grads, want_diff)
     if B:
         check(lib.esr_bpr_fwd_bwd(_p(user_table), user_table.shape[0], _p(item_table), item_table.shape[0], D, _p(u), _p(i),
                                   _p(j), _p(valid), B, float(reg), _p(loss_t), _p(diff_t), _p(grads), _p(failed), _stream()),
@@ -2106,9 +2125,7 @@ def bpr_fwd_bwd(user_table, item_table, u, i, j, valid, reg, want_grads=True, wa
 def warp_geometry():
     """(max_trials, max_rank, rank_multiple): the most candidates one search may walk; warp_step takes a rank that is a
     multiple of rank_multiple and at most max_rank."""
-    trials, rank, mult = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-    check(_lib.load().esr_warp_geometry(ctypes.byref(trials), ctypes.byref(rank), ctypes.byref(mult)), "esr_warp_geometry")
-    return int(trials.value), int(rank.value), int(mult.value)
+    return _geometry("warp", 3)
 
 
 def warp_step(user_factors, item_factors, offsets, row_upos, row_ipos, rank_weight, seed, step, B, max_trials, margin, reg,
@@ -2138,9 +2155,7 @@ def warp_step(user_factors, item_factors, offsets, row_upos, row_ipos, rank_weig
     dev = user_factors.device
     failed = _failed_word(failed, dev)
     ids = torch.empty((5, B), dtype=torch.int32, device=dev)
-    loss_t = torch.empty(B, dtype=torch.float32, device=dev)
-    diff = torch.empty(B, dtype=torch.float32, device=dev) if want_diff else None
-    grads = torch.empty((3 * B, D), dtype=torch.float32, device=dev) if want_grads else None
+    loss_t, diff, grads = _step_outputs(B, 3 * B, D, dev, want_grads, want_diff)
     check(lib.esr_warp_step(_p(user_factors), nu, _p(item_factors), ni, D, _p(offsets), _p(row_upos), _p(row_ipos), nnz,
                             _p(rank_weight), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, B, max_trials, float(margin),
                             float(reg), _p(ids[0]), _p(ids[1]), _p(ids[2]), _p(ids[3]), _p(ids[4]), _p(loss_t), _p(diff),
@@ -2153,9 +2168,7 @@ def warp_step(user_factors, item_factors, offsets, row_upos, row_ipos, rank_weig
 def bag_geometry():
     """(max_rank, rank_multiple): bag_sum and bag_expand take a rank that is a multiple of rank_multiple and at most
     max_rank -- bpr_fwd_bwd's geometry."""
-    rank, mult = ctypes.c_int(0), ctypes.c_int(0)
-    check(_lib.load().esr_bag_geometry(ctypes.byref(rank), ctypes.byref(mult)), "esr_bag_geometry")
-    return int(rank.value), int(mult.value)
+    return _geometry("bag", 2)
 
 
 def _bag_args(who, table, offsets, feat, weight, rows):
@@ -2217,10 +2230,7 @@ def bag_expand(table, offsets, feat, weight, rows, grad_rows, valid, out_offsets
         raise ValueError("bag_expand: grad_rows must be [n, rank] and out_offsets hold n + 1 entries")
     if not 0 <= M <= 2 ** 31 - 1:
         raise ValueError("bag_expand: M=%d expanded occurrences outside [0, 2^31 - 1]" % M)
-    if valid is not None:
-        _req(valid, torch.int32, "valid")
-        if valid.numel() != n:
-            raise ValueError("bag_expand: valid must hold one entry per selected bag")
+    _check_valid(valid, n, "selected bag", "bag_expand: ")
     dev = table.device
     if out is None:
         out = (torch.empty(M, dtype=torch.int32, device=dev), torch.empty((M, D), dtype=torch.float32, device=dev))
@@ -2241,9 +2251,7 @@ def bag_expand(table, offsets, feat, weight, rows, grad_rows, valid, out_offsets
 def fpmc_geometry():
     """(max_window, max_rank, rank_multiple): the most context items an event takes; fpmc_fwd_bwd takes a rank that is a
     multiple of rank_multiple and at most max_rank."""
-    window, rank, mult = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-    check(_lib.load().esr_fpmc_geometry(ctypes.byref(window), ctypes.byref(rank), ctypes.byref(mult)), "esr_fpmc_geometry")
-    return int(window.value), int(rank.value), int(mult.value)
+    return _geometry("fpmc", 3)
 
 
 def fpmc_sample(seq_offsets, seq_upos, seq_ipos, row_offsets, row_ipos, nu, ni, window, seed, step0, K, B):
@@ -2262,8 +2270,7 @@ def fpmc_sample(seq_offsets, seq_upos, seq_ipos, row_offsets, row_ipos, nu, ni, 
                          % (row_offsets.numel(), nu, nnz_seen))
     if not 1 <= window <= fpmc_geometry()[0]:
         raise ValueError("fpmc_sample: window = %d outside [1, %d]" % (window, fpmc_geometry()[0]))
-    out = torch.empty((6, K, B), dtype=torch.int32, device=seq_upos.device)
-    dropped = torch.empty(K, dtype=torch.int32, device=seq_upos.device)
+    out, dropped = _sample_outputs(6, K, B, seq_upos.device)
     check(lib.esr_fpmc_sample(_p(seq_offsets), _p(seq_upos), _p(seq_ipos), nnz_seq, _p(row_offsets), _p(row_ipos), nnz_seen,
                               nu, ni, window, int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF, K, B, _p(out[0]),
                               _p(out[1]), _p(out[2]), _p(out[3]), _p(out[4]), _p(out[5]), _p(dropped), _stream()),
@@ -2296,16 +2303,11 @@ def fpmc_fwd_bwd(user_table, item_table, next_table, prev_table, seq_ipos, u, e,
     B, D = u.numel(), int(user_table.shape[1])
     if any(t.numel() != B for t in ids):
         raise ValueError("u, e, c, i and j must have one length")
-    if valid is not None:
-        _req(valid, torch.int32, "valid")
-        if valid.numel() != B:
-            raise ValueError("valid must hold one entry per slot")
+    _check_valid(valid, B, "slot")
     _check_rank4(D, *fpmc_geometry()[1:])
     dev = user_table.device
     failed = _failed_word(failed, dev)
-    loss_t = torch.empty(B, dtype=torch.float32, device=dev)
-    diff_t = torch.empty(B, dtype=torch.float32, device=dev) if want_diff else None
-    grads = ctx_ids = None
+    ctx_ids = None
     if want_grads:
         if ctx_offsets is None:
             ctx_offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
@@ -2315,8 +2317,8 @@ def fpmc_fwd_bwd(user_table, item_table, next_table, prev_table, seq_ipos, u, e,
         M = int(M)
         if ctx_offsets.numel() != B + 1 or not 0 <= M <= 2 ** 31 - 1:
             raise ValueError("fpmc_fwd_bwd: ctx_offsets must hold B + 1 entries and M = %d lie in [0, 2^31 - 1]" % M)
-        grads = torch.empty((5 * B + M, D), dtype=torch.float32, device=dev)
         ctx_ids = torch.empty(M, dtype=torch.int32, device=dev)
+    loss_t, diff_t, grads = _step_outputs(B, 5 * B + (M or 0), D, dev, want_grads, want_diff)
     if B:
         check(lib.esr_fpmc_fwd_bwd(_p(user_table), user_table.shape[0], _p(item_table), _p(next_table), _p(prev_table),
                                    item_table.shape[0], D, _p(seq_ipos), seq_ipos.numel(), _p(u), _p(e), _p(c), _p(i), _p(j),
@@ -2331,9 +2333,7 @@ def fpmc_fwd_bwd(user_table, item_table, next_table, prev_table, seq_ipos, u, e,
 def sgns_geometry():
     """(max_window, max_negatives, max_rank, rank_multiple): the largest context distance and the most noise items per
     slot; sgns_fwd_bwd takes a rank that is a multiple of rank_multiple and at most max_rank."""
-    out = [ctypes.c_int(0) for _ in range(4)]
-    check(_lib.load().esr_sgns_geometry(*[ctypes.byref(v) for v in out]), "esr_sgns_geometry")
-    return tuple(int(v.value) for v in out)
+    return _geometry("sgns", 4)
 
 
 def sgns_sample(seq_offsets, seq_upos, seq_ipos, nd, ni, window, negatives, noise_keep, noise_alias, seed, step0, K, B):
@@ -2355,9 +2355,8 @@ def sgns_sample(seq_offsets, seq_upos, seq_ipos, nd, ni, window, negatives, nois
     if not 1 <= negatives <= top_negatives:
         raise ValueError("sgns_sample: negatives = %d outside [1, %d]" % (negatives, top_negatives))
     dev = seq_upos.device
-    out = torch.empty((4, K, B), dtype=torch.int32, device=dev)
+    out, dropped = _sample_outputs(4, K, B, dev)
     neg = torch.empty((K, B, negatives), dtype=torch.int32, device=dev)
-    dropped = torch.empty(K, dtype=torch.int32, device=dev)
     check(lib.esr_sgns_sample(_p(seq_offsets), _p(seq_upos), _p(seq_ipos), nnz_seq, nd, ni, window, negatives, _p(noise_keep),
                               _p(noise_alias), int(seed) & (2 ** 64 - 1), int(step0) & 0xFFFFFFFF, K, B, _p(out[0]), _p(out[1]),
                               _p(out[2]), _p(out[3]), _p(neg), _p(dropped), _stream()), "esr_sgns_sample")
@@ -2383,16 +2382,11 @@ def sgns_fwd_bwd(in_table, out_table, c, o, neg, valid, reg, want_grads=True, wa
     K = int(neg.shape[1])
     if not 1 <= K <= sgns_geometry()[1]:
         raise ValueError("sgns_fwd_bwd: negatives = %d outside [1, %d]" % (K, sgns_geometry()[1]))
-    if valid is not None:
-        _req(valid, torch.int32, "valid")
-        if valid.numel() != B:
-            raise ValueError("valid must hold one entry per slot")
+    _check_valid(valid, B, "slot")
     _check_rank4(D, *sgns_geometry()[2:])
     dev = in_table.device
     failed = _failed_word(failed, dev)
-    loss_t = torch.empty(B, dtype=torch.float32, device=dev)
-    diff_t = torch.empty((B, 1 + K), dtype=torch.float32, device=dev) if want_diff else None
-    grads = torch.empty(((2 + K) * B, D), dtype=torch.float32, device=dev) if want_grads else None
+    loss_t, diff_t, grads = _step_outputs(B, (2 + K) * B, D, dev, want_grads, want_diff, scores=1 + K)
     if B:
         check(lib.esr_sgns_fwd_bwd(_p(in_table), _p(out_table), in_table.shape[0], D, _p(c), _p(o), _p(neg), _p(valid), B, K,
                                    float(reg), _p(loss_t), _p(diff_t), _p(grads), _p(failed), _stream()), "esr_sgns_fwd_bwd")

@@ -1,12 +1,14 @@
 """Generates tests/golden/factorization_parent.json (run from the repo root on an MI355X:
-``python tests/golden/make_factorization_golden.py [--out FILE]``).
+``python tests/golden/make_factorization_golden.py [--out FILE] [--families fpmc,sgns]``; with ``--families`` only those
+are trained and the other entries of the committed file are carried over unchanged).
 
-The five models of esrecsys_amd/factorization.py are functions of their inputs and the seed, so the fixture holds no
+The models of esrecsys_amd/factorization.py are functions of their inputs and the seed, so the fixture holds no
 numbers, only SHA-256 digests: per small model, of every factor / embedding / accumulator table, of the returned loss
 lists (as float64 bytes) and of a few outputs (recommend, auc, fold_in).  It was written once, at the commit BEFORE the
 models were given one base class, and pins that the rewrite trains bit for bit what its parent trained: the same
-generator draws, the same ops calls in the same order.  tests/test_gpu_factorization_golden.py retrains the models through
-``compute()`` below and compares.
+generator draws, the same ops calls in the same order.  The families ``fpmc`` and ``sgns`` were appended at the commit
+BEFORE the sampled-SGD models were given one sampler shell, one logistic and one trainer base, and pin that rewrite in the
+same way.  tests/test_gpu_factorization_golden.py retrains the models through ``compute()`` below and compares.
 
 Data: a seeded NumPy generator, 40 users over 1300 items.  User 0 has about 1100 items (longer than a workgroup's
 ``chunk * chunks_per_workgroup`` of ``ops.als_geometry()``), users 1-4 have 300 to 900 (more than one chunk) and the rest are
@@ -154,7 +156,66 @@ def hybrid_models(out):
             ("recommend ids", digest(rec[0])), ("recommend scores", digest(rec[1])), ("recommend lengths", digest(rec[2]))]
 
 
-FAMILIES = {"als": als_models, "bpr": bpr_models, "warp": warp_models, "hybrid": hybrid_models}
+def _sequences(item):
+    """Given sequences over the known items: five ids, an empty one, one with an id that is no item (4), one unknown id
+    alone and a long one (more than any window); as (indices, doc_offsets)."""
+    items = np.unique(item)
+    docs = [items[:5], items[:0], np.concatenate([items[10:12], [4], items[40:41]]), np.array([4], np.int64), items[100:130]]
+    return np.concatenate(docs).astype(np.int64), np.concatenate([[0], np.cumsum([d.size for d in docs])]).astype(np.int64)
+
+
+def fpmc_models(out):
+    """``pairs()`` read as sequences (the shuffled order is the order of events, or `time` with ties decides)."""
+    from esrecsys_amd import factorization as fz
+    user, item, rng = pairs()
+    time = rng.integers(0, 50, user.size)
+    seq, seq_off = _sequences(item)
+    seq_users = np.array([np.unique(user)[1], 1, np.unique(user)[7], np.unique(user)[8], 1], np.int64)    # (1 is no user)
+    for rank, window, optimizer, timed in ((4, 1, "adagrad", False), (20, 3, "adagrad", True), (20, 3, "sgd", False),
+                                           (64, 8, "adagrad", True), (128, 3, "adagrad", False)):
+        m = fz.FPMC(user, item, time=time if timed else None, window=window, rank=rank, reg=0.02, lr=0.05,
+                    optimizer=optimizer, batch=300, seed=8)
+        losses = m.train_steps(3) + m.train_steps(2)
+        name = "FPMC rank=%d window=%d optimizer=%s time=%s" % (rank, window, optimizer, timed)
+        out[name] = _triple_tables(m, losses) + [
+            ("next_factors", digest(m.next_factors)), ("prev_factors", digest(m.prev_factors)),
+            ("next_accum", digest(m.next_accum)), ("prev_accum", digest(m.prev_accum))]
+        if rank <= fz.predict_max_rank() // 2:                                   # (serving re-scores rows of 2 rank)
+            rec = m.recommend(_queries(user), k=20)
+            by_seq = m.recommend_sequences(seq, seq_off, k=20, users=seq_users)
+            session = m.recommend_sequences(seq, seq_off, k=20, exclude_seen=False)
+            out[name] += [("recommend ids", digest(rec[0])), ("recommend scores", digest(rec[1])),
+                          ("recommend lengths", digest(rec[2]))]
+            out[name] += [("recommend_sequences %s %s" % (how, what), digest(t)) for how, r in
+                          (("users", by_seq), ("session", session)) for what, t in zip(("ids", "scores", "lengths"), r)]
+
+
+def sgns_models(out):
+    """``pairs()`` read as documents: the user is the document."""
+    from esrecsys_amd import factorization as fz
+    user, item, rng = pairs()
+    time = rng.integers(0, 50, user.size)
+    seq, seq_off = _sequences(item)
+    similar_to = np.concatenate([np.unique(item)[[0, 3, 700, -1]], [4]])       # (id 4 is no item)
+    for rank, negatives, window, optimizer, timed in ((4, 1, 1, "adagrad", False), (20, 5, 5, "adagrad", True),
+                                                      (20, 5, 5, "sgd", False), (64, 16, 5, "adagrad", False),
+                                                      (128, 5, 1, "adagrad", True)):
+        m = fz.SGNS(user, item, time=time if timed else None, window=window, negatives=negatives, rank=rank, reg=0.02,
+                    lr=0.05, optimizer=optimizer, batch=300, seed=9)
+        losses = m.train_steps(3) + m.train_steps(2)
+        sim = m.similar_items(similar_to, k=20)
+        rec = m.recommend_sequences(seq, seq_off, k=20)
+        out["SGNS rank=%d negatives=%d window=%d optimizer=%s time=%s" % (rank, negatives, window, optimizer, timed)] = [
+            ("in_factors", digest(m.in_factors)), ("out_factors", digest(m.out_factors)),
+            ("in_accum", digest(m.in_accum)), ("out_accum", digest(m.out_accum)), ("losses", digest(losses)),
+            ("step", digest(float(m.step))), ("accuracy", digest(m.accuracy())),
+            ("similar_items ids", digest(sim[0])), ("similar_items scores", digest(sim[1])),
+            ("similar_items lengths", digest(sim[2])), ("recommend_sequences ids", digest(rec[0])),
+            ("recommend_sequences scores", digest(rec[1])), ("recommend_sequences lengths", digest(rec[2]))]
+
+
+FAMILIES = {"als": als_models, "bpr": bpr_models, "warp": warp_models, "hybrid": hybrid_models, "fpmc": fpmc_models,
+            "sgns": sgns_models}
 
 
 def compute(family):
@@ -168,7 +229,12 @@ if __name__ == "__main__":
     sys.path.insert(0, ROOT)
     path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT
     result = {}
-    for name in FAMILIES:
+    families = list(FAMILIES)
+    if "--families" in sys.argv:                       # only these are trained; the file's other entries stay as they are
+        families = sys.argv[sys.argv.index("--families") + 1].split(",")
+        with open(OUT) as f:
+            result = {k: [tuple(p) for p in v] for k, v in json.load(f).items()}
+    for name in families:
         result.update(compute(name))
     with open(path, "w") as f:
         json.dump({k: [list(p) for p in v] for k, v in result.items()}, f, indent=1)

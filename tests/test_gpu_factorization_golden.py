@@ -1,6 +1,6 @@
-"""GPU: the five models of esrecsys_amd/factorization.py train bit for bit what they trained before they were given one
-base class.  tests/golden/make_factorization_golden.py trains small models (every rank layout, row-length class, optimiser
-and launch slicing) and digests every table, loss list and a few outputs with SHA-256; tests/golden/factorization_parent.json
+"""GPU: the models of esrecsys_amd/factorization.py train bit for bit what they trained before they were given one
+base class (FPMC and SGNS: before the sampled-SGD family was given one sampler shell, one logistic and one trainer base).
+tests/golden/make_factorization_golden.py trains small models (every rank layout, row-length class, optimiser and launch slicing) and digests every table, loss list and a few outputs with SHA-256; tests/golden/factorization_parent.json
 holds those digests as written at the parent commit (stable between two runs there).  The models are functions of their
 inputs and the seed, so equality is the assertion: a reordered generator draw or ops call shows as a different table.
 (The digests of the two ALS models were written again when the pivot's square root in esr_als.hip became the correctly
@@ -32,7 +32,8 @@ def parent():
         return json.load(f)
 
 
-FAMILIES = {"als": ("RatingsALS", "ImplicitALS"), "bpr": ("BPR",), "warp": ("WARP",), "hybrid": ("HybridBPR",)}
+FAMILIES = {"als": ("RatingsALS", "ImplicitALS"), "bpr": ("BPR",), "warp": ("WARP",), "hybrid": ("HybridBPR",),
+            "fpmc": ("FPMC",), "sgns": ("SGNS",)}
 
 
 @pytest.mark.parametrize("family", sorted(FAMILIES))

@@ -31,7 +31,7 @@ pytestmark = pytest.mark.gpu
 
 MAX_GRID = 2048                 # kMaxGrid of esr_common.h: the workgroups of bpr_fwd_bwd
 BLOCK = 256                     # kBlock
-MAX_BLOCKS = 16 * MAX_GRID      # kWarpMaxBlocks and k{Bpr,Fpmc,Sgns}MaxSampleBlocks
+MAX_BLOCKS = 16 * MAX_GRID      # kSampledMaxBlocks (esr_sampled.h): warp_step and the three samplers
 TAIL = 257
 MEASURED = {}
 
@@ -256,7 +256,7 @@ def test_default_hybrid_train_step_equals_the_ops_composed_by_hand(dev, optimize
     assert not torch.equal(a.item_embeddings, model().item_embeddings)
 
 
-# ---- 3. warp_step past kWarpMaxBlocks ----------------------------------------------------------------------------------------
+# ---- 3. warp_step past kSampledMaxBlocks ----------------------------------------------------------------------------------------
 WARP_ONE_PASS = MAX_BLOCKS * (BLOCK // 32)          # 262 144 slots: 32 768 workgroups of 8 groups of 32 lanes
 WARP_T = 5
 _WARP = {}
